@@ -28,6 +28,8 @@ roofline     the dominant device stage of the apply, timed live with HIP events 
 host_path    what a caller of the numpy-in / numpy-out surface sees (N = 1): hessian_slice, vis2dirty, dirty2vis per call.
 cpu_baseline ducc0 when importable on this box (kind "ducc0"), else the oracle's CPU restatement (kind "port") of the
              same apply on this box's host cores.
+--dump-outputs DIR  after the timed steps, what the last step computed (the arrays a caller of the timed path receives) as
+             DIR/<name>.npy, float64, 64 MB at most in all; the inputs are seeded, so two builds can be compared file by file.
 """
 
 import argparse
@@ -46,6 +48,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
 F64_PEAK_TFLOPS = 78.6  # f64 vector FMA: 256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz (the chip holds ~2.0 GHz under this load)
 # stage timer -> the kernel it brackets (name as rocprofv3 lists it); the record scatter / row-walk gather / transposing
 # first-axis FFT replace k_grid_blk / k_degrid_mp / k_rowfft_plain + k_a2b / k_b2a where the plan admits them
+DUMP_BYTES = 64 << 20  # --dump-outputs: the .npy files of one run together stay below this
 KERNEL_OF = {"grid": "k_grid_rec", "degrid": "k_degrid_rw", "fft_rows": "k_rowfft_a2b / k_rowfft_b2a", "pad": "k_b2a",
              "crop": "k_a2b", "fft_crop": "k_fused_fft_crop", "pad_fft": "k_fused_pad_fft"}
 
@@ -103,6 +106,30 @@ def algorithmic_bytes(info, nx, ny, nrow, nactive):
         launches.update({"fft_rows": 4 * P, "pad": 2 * P, "crop": 2 * P})
     other = P * Au  # clearing the used cells of the scatter's planes (on a side stream in single-pass plans)
     return b_vis + b_grid, per_launch, launches, other
+
+
+def dump_outputs(d, arrays):
+    """Writes every float64 / float32 array of ``arrays`` ({name: ndarray}) to ``d/<name>.npy``, smallest first, each within an
+    equal share of what DUMP_BYTES has left.  One larger than its share is written as a sample of its flattened elements at
+    fixed positions (a seeded draw, the same on every run); returns {name: what was written} for the result line."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BYTES
+    written = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].nbytes)):
+        a = np.ascontiguousarray(arrays[name])
+        if a.dtype not in (np.float64, np.float32):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float64 / float32")
+        share = left // (len(arrays) - i) - 4096  # (room for the .npy header)
+        left -= min(a.nbytes, share) + 4096
+        what = f"{a.dtype} {list(a.shape)}"
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+            what = f"{n} elements of {what} at seeded positions (np.random.default_rng(0).choice(size, {n}, replace=False), sorted)"
+        np.save(os.path.join(d, name + ".npy"), a)
+        written[name] = what
+    return written
 
 
 def host_threads():
@@ -258,7 +285,12 @@ def main():
     ap.add_argument("--allow-no-rccl", action="store_true",
                     help="N > 1 only: if the RCCL communicator cannot be created, measure the per-band work without the band "
                          "exchange instead of failing (the line then says so; it is NOT a scaling measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, <= 64 MB in all; a seeded sample of "
+                         "larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the JSON of rank 0: native libraries (RCCL prints a version banner on fd 1 when
     # a communicator is created) write to stderr for the lifetime of the process, the JSON goes to the saved descriptor
@@ -407,6 +439,14 @@ def bench_gridder(args, comm, use_rccl, rccl_error, synth, Gridder, DeviceArray,
     _lib.check(_lib.lib().pfbhip_synchronize())
     comm.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the image the last step left in HBM (the CG solution for C3), and the band sum root receives when that step reduced
+        dumped = {"solution" if solve else "image": out_dev.download()}
+        if use_rccl and not split and (solve or args.steps % reduce_every == 0):
+            dumped["band_sum"] = red_dev.download()
+        if solve:
+            dumped["cg_info"] = np.array([g.last_cg[k] for k in ("iters", "status", "eps", "phi")], dtype=np.float64)
     if two_pass:
         g.profile(True)
         g.profile_get(reset=True)
@@ -581,6 +621,8 @@ def bench_gridder(args, comm, use_rccl, rccl_error, synth, Gridder, DeviceArray,
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "Mvis/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {type(e).__name__}: {e}"}
+        if dumped is not None:
+            out["outputs"] = dump_outputs(args.dump_outputs, dumped)
     g.close()
     return out
 
@@ -618,14 +660,14 @@ def bench_c4(args, comm, use_rccl, rccl_error):
         pd.set_grad(PsfGrad(hess, xtilde, 1.0))
         if pd._device_path() is None:
             raise SystemExit("C4: the device-resident primal-dual loop is not available for this layout")
-        pd.solve(model.copy(), 0.01)
-        return pd.last
+        x = pd.solve(model.copy(), 0.01)
+        return x, pd.last
 
     if args.warmup > 0:
         run(args.warmup)
     comm.barrier()
     t0 = time.perf_counter()
-    last = run(args.steps)
+    x_last, last = run(args.steps)
     comm.barrier()
     wall = comm.max_over_ranks(time.perf_counter() - t0)
     loop_s = comm.max_over_ranks(float(last.get("loop_ms", 0.0)) * 1e-3) or wall
@@ -697,6 +739,9 @@ def bench_c4(args, comm, use_rccl, rccl_error):
             out["roofline"] = roof
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if args.dump_outputs:
+            info = np.array([last[k] for k in ("iters", "status", "eps")], dtype=np.float64)
+            out["outputs"] = dump_outputs(args.dump_outputs, {"model": x_last, "pd_info": info})
     return out
 
 
