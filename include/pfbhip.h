@@ -143,9 +143,6 @@ typedef struct pfbhip_gridder_info {
      * functions per axis; phase centre on axis only).  Replaces the nderiv planes wmode 1 would use. */
     int32_t nderiv;
     double smax;
-    /* Hessian applies replayed from a captured hipGraph so far (opt-in: PFBHIP_GRAPH=1; measured at parity with eager
-     * launches even at C1's size, see gridder.hip) */
-    int64_t graph_replays;
     /* edge (cells) of the blocks the register-footprint scatters anchor their frame on: 4 (the tile sort's 4 x 4-cell blocks), or 2
      * for the one-plane scatter at W = 14, 15 (16 x 16-cell frame on 4 x 16 lanes; the sort key then carries the 2 x 2 block) */
     int32_t scatter_block;
@@ -213,10 +210,6 @@ int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, dou
 #define PFBHIP_NSTAGES 8
 int pfbhip_gridder_profile(pfbhip_gridder *g, int enable);
 int pfbhip_gridder_profile_get(pfbhip_gridder *g, double *ms /* [PFBHIP_NSTAGES] */, int64_t *calls, int reset);
-/* Diagnostic (plans created with PFBHIP_STAMP=1 in the environment): in-kernel phase stamps (shader cycles) of the last
- * record-scatter pass, 8 words per colour work item: prologue, wave 0 visibility loop, wave 0 barrier wait, tile flush,
- * visibilities, last wave's loop, last wave's wait, tile.  *nitems = 0 when stamping is off. */
-int pfbhip_gridder_debug_stamps(pfbhip_gridder *g, unsigned long long *out_host, int64_t capacity_items, int64_t *nitems);
 
 /* ---- FFT (replaces ducc0.fft.r2c / c2r) ---------------------------- */
 /* r2c(forward=True, inorm=0) and c2r(forward=False, inorm=2, lastsize) over the last two axes of a

@@ -40,7 +40,7 @@ class GridderInfo(ct.Structure):
         ("nshift", f64), ("lshift", f64), ("mshift", f64), ("kernel_eps", f64),
         ("wmode", i32), ("occ_rows", i32), ("wcenter", f64), ("whalf", f64), ("device_bytes", ct.c_size_t),
         ("fft_mode", i32), ("screen_poly", i32), ("scatter_mode", i32), ("scatter_launches", i32),
-        ("used_cells", i64), ("screen_composite", i32), ("screen_separable", i32), ("nderiv", i32), ("smax", f64), ("graph_replays", i64),
+        ("used_cells", i64), ("screen_composite", i32), ("screen_separable", i32), ("nderiv", i32), ("smax", f64),
         ("scatter_block", i32), ("reserved0", i32),
     ]
 
@@ -77,7 +77,6 @@ SYMBOLS = (
     "pfbhip_gridder_set_weights", "pfbhip_gridder_hessian", "pfbhip_gridder_hessian_dev", "pfbhip_gridder_residual_dev",
     "pfbhip_gridder_vis2dirty_sp", "pfbhip_gridder_dirty2vis_sp", "pfbhip_gridder_set_weights_sp", "pfbhip_gridder_hessian_sp",
     "pfbhip_gridder_degrid_dev", "pfbhip_gridder_grid_dev", "pfbhip_gridder_profile", "pfbhip_gridder_profile_get",
-    "pfbhip_gridder_debug_stamps",
     "pfbhip_gridder_cg", "pfbhip_gridder_cg_dev",
     "pfbhip_r2c_2d", "pfbhip_r2c_2d_centred", "pfbhip_c2r_2d", "pfbhip_debug_rowfft",
     "pfbhip_psi_create", "pfbhip_psi_destroy", "pfbhip_psi_shape", "pfbhip_psi_dot", "pfbhip_psi_hdot",

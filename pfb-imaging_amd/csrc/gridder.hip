@@ -578,22 +578,6 @@ struct pfbhip_gridder {
     rocfft_plan fftB_fwd = nullptr, fftB_bwd = nullptr;  // ny rows of length nu
     rocfft_execution_info fft_info = nullptr;
     StageTimer timer;
-    // Captured Hessian applies, OPT-IN (PFBHIP_GRAPH=1).  Measured at C1 (round 4, gpurun_out/r04: 50 applies, no stage timers):
-    // eager 0.216 ms per apply for 0.211 ms of kernels, replayed 0.224 -- the host issues an apply's ~8 launches faster than
-    // the device runs them, and a dependent kernel boundary costs the same inside a graph.  (The "25 % of launch gaps" of
-    // round 3's C1 line were the stage timers' own events: 16 hipEventRecords per apply.)  Kept for hosts that cannot keep
-    // up (many bands per process).  Keyed by what a capture bakes in: the image pointers and the scalars; the device buffers the kernels read
-    // (weights, records, planes) keep their addresses for the life of the plan, so new weights or a new x need no new graph.
-    struct ApplyGraph {
-        const double *x, *beam;
-        double *out;
-        double eta, wsum;
-        int seen;              // calls with this key (the second one captures: the first has warmed every lazy set-up)
-        hipGraphExec_t exec;
-    };
-    std::vector<ApplyGraph> graphs;
-    int graph_mode = -1;       // -1 undecided, 0 off, 1 on (PFBHIP_GRAPH=1 on the hand-written FFT path)
-    int64_t graph_replays = 0;
     std::vector<double> wplanes;  // w of every plane (wavelengths)
     std::vector<double> nodes, lagr_coef;  // wmode 1: Chebyshev nodes and Lagrange denominators
 
@@ -606,8 +590,6 @@ struct pfbhip_gridder {
         if (fftB_fwd) rocfft_plan_destroy(fftB_fwd);
         if (fftB_bwd) rocfft_plan_destroy(fftB_bwd);
         if (fft_info) rocfft_execution_info_destroy(fft_info);
-        for (auto &ag : graphs)
-            if (ag.exec) (void)hipGraphExecDestroy(ag.exec);
         if (stream) (void)hipStreamDestroy(stream);
         if (clear_stream) (void)hipStreamDestroy(clear_stream);
         if (ev_clear) (void)hipEventDestroy(ev_clear);
@@ -683,7 +665,6 @@ struct pfbhip_gridder {
         for (int k = 0; k < KP_MAX; ++k)
             ga.coefk[k] = (info.wmode == 1 && k < kp) ? lagr_coef[size_t(plane0 + k)] : 1.0;
         ga.plane_stride = plane_stride;
-        ga.dbg = nullptr;
         for (int q = 0; q < 3; ++q) ga.wshare[q] = wshare[q];
         return ga;
     }
@@ -749,9 +730,7 @@ struct pfbhip_gridder {
     // row-walk gather (k_degrid_rw): same plans as the record scatter; d_kw: plane weights of every visibility (plan time)
     bool gather_rw = false;
     DevBuf<double> d_kw;
-    float wshare[3] = {1.3f / 3, 1.f / 3, 0.7f / 3};  // see GroupArgs::wshare: measured optimum on C2 (equal shares: +7 % scatter time); PFBHIP_WSHARE=a,b,c overrides
-    int stamp_mode = 0;  // PFBHIP_STAMP: 1 = record scatter, 2 = row-walk gather
-    DevBuf<unsigned long long> d_stamps;  // PFBHIP_STAMP=1: in-kernel phase stamps of the record scatter (8 words per colour work item)
+    float wshare[3] = {1.3f / 3, 1.f / 3, 0.7f / 3};  // see GroupArgs::wshare: measured optimum on C2 (equal shares: +7 % scatter time)
     DevBuf<double2> d_pval;
     template <int W, int KP, int BC>
     void launch_grid_rec_wkb(const GroupArgs &ga)
@@ -794,13 +773,11 @@ struct pfbhip_gridder {
                 if (ga.a.nwork == 0) continue;
                 timer.begin(0);
                 if (info.wmode == 2) {
-                    if (stamp_mode == 1 && d_stamps.p != nullptr) ga.dbg = d_stamps.p + (col_off[grp * 4 + size_t(col)]) * 8;
                     wd_launch_grid(ga, wd, d_rec.p, d_pval.p, grid_cur, stream);
                     timer.end();
                     continue;
                 }
                 if (scatter_rec) {
-                    if (stamp_mode == 1 && d_stamps.p != nullptr) ga.dbg = d_stamps.p + (col_off[grp * 4 + size_t(col)]) * 8;
                     switch (kp) {
                         case 1: launch_grid_rec_wk<W, 1>(ga); break;
                         case 2: launch_grid_rec_wk<W, 2>(ga); break;
@@ -836,29 +813,13 @@ struct pfbhip_gridder {
         hipLaunchKernelGGL((k_degrid_mp<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds_bytes_mp<W>(), stream, ga,
                            grid_cur, sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr);
     }
-    int rw_depth = 0;  // PFBHIP_RW_DEPTH (experiment): explicit LDS prefetch distance of the row-walk gather, (W, KP) = (16, 3) only
-    template <int W, int KP, int PD>
-    void launch_degrid_rw_d(const GroupArgs &ga, double2 *sacc)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_rw<W, KP, PD>), 160 * 1024);
-        const size_t lds = size_t(KP) * RW_LS * RW_LS * sizeof(double2);
-        GroupArgs gs = ga;
-        if (stamp_mode == 2 && d_stamps.p != nullptr) gs.dbg = d_stamps.p;
-        hipLaunchKernelGGL((k_degrid_rw<W, KP, PD>), dim3(ga.a.nwork), dim3(MP_THREADS), lds, stream, gs, d_rec.p, d_kw.p, grid_cur,
-                           sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr);
-    }
     template <int W, int KP>
     void launch_degrid_rw_wk(const GroupArgs &ga, double2 *sacc)
     {
-        if constexpr (W == 16 && KP == 3) {
-            switch (rw_depth) {
-                case 1: launch_degrid_rw_d<W, KP, 1>(ga, sacc); return;
-                case 2: launch_degrid_rw_d<W, KP, 2>(ga, sacc); return;
-                case 3: launch_degrid_rw_d<W, KP, 3>(ga, sacc); return;
-                default: break;
-            }
-        }
-        launch_degrid_rw_d<W, KP, 0>(ga, sacc);
+        allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_rw<W, KP>), 160 * 1024);
+        const size_t lds = size_t(KP) * RW_LS * RW_LS * sizeof(double2);
+        hipLaunchKernelGGL((k_degrid_rw<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds, stream, ga, d_rec.p, d_kw.p, grid_cur,
+                           sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr);
     }
     template <int W>
     void launch_degrid_mp_w(int plane0, int kp, double2 *sacc)
@@ -866,7 +827,6 @@ struct pfbhip_gridder {
         GroupArgs ga = group_args(plane0, kp);
         if (ga.a.nwork == 0) return;
         if (info.wmode == 2) {
-            if (stamp_mode == 2 && d_stamps.p != nullptr) ga.dbg = d_stamps.p;
             wd_launch_degrid(ga, wd, d_rec.p, grid_cur, sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr, stream);
             return;
         }
@@ -1052,16 +1012,12 @@ struct pfbhip_gridder {
     void prepare_and_degrid(const double *x, const double *beam, double2 *sacc)
     {
         // The side-stream clear of the scatter's planes starts with the apply, under the degridding side's row transforms (round
-        // 4b; PFBHIP_CLEAR_EARLY=0: in front of the gather, as before).  The gather's workgroups fill every CU's registers (three
+        // 4b; before that: in front of the gather).  The gather's workgroups fill every CU's registers (three
         // waves of 168 VGPRs per SIMD), so a clear issued next to it only got onto the chip as the gather drained and ran into
         // the scatter; the fused row-FFT kernels leave room.  C2: degrid 1.647 -> 1.594 ms, pad_fft + 0.01, apply 5.91 -> 5.86 ms.
-        static const bool clear_early = [] {
-            const char *e = std::getenv("PFBHIP_CLEAR_EARLY");
-            return !(e != nullptr && e[0] == '0');
-        }();
         // (one plane only: with the three planes of the polynomial scheme the clear's 0.9 GB cost pad_fft what they save the gather,
         // 9.73 against 9.77 ms)
-        if (clear_early && side_clear_pending && info.nplanes == 1) side_clear();
+        if (side_clear_pending && info.nplanes == 1) side_clear();
         if (fused && info.nactive != 0 && info.nwork != 0 && fused_pad_takes_prep(rowfft_u, fgeom)) {
             FusedPrep p;
             p.x = x;
@@ -1195,7 +1151,61 @@ static int poly_planes_needed(double omega, double eps)
     return k;
 }
 
-static void choose_kernel(pfbhip_gridder *g, double wlo, double whi, double tmax, double nmin)
+// The switches that override the plan's choices.  Read once at the start of every plan creation,
+// never cached for the process: the tests set them between plans to keep the alternative kernels covered.
+enum class ScatterForce { Auto, Walk, Block, Rec, RecEs };  // PFBHIP_SCATTER=auto / walk / block / rec / rec_es
+struct PlanSwitches {
+    ScatterForce scatter = ScatterForce::Auto;
+    bool wmode2 = true;       // PFBHIP_WMODE2=0: keep the multi-plane w-schemes
+    bool wd_block4 = false;   // PFBHIP_WD_BLOCK=4: 4 x 4-cell anchoring at W = 14, 15
+    int wd_colours = -1;      // PFBHIP_WD_COLOURS: -1 plan decides, 0 one launch (atomic flush), 1 four colour launches
+    uint32_t chunk = 0;       // PFBHIP_CHUNK (256..CHUNK; 0: plan decides)
+    uint32_t wd_chunk = 0;    // PFBHIP_WD_CHUNK (64..CHUNK; 0: plan decides)
+    bool rowfft = true;       // PFBHIP_ROWFFT=0: rocFFT row plans
+    bool fused_fft = true;    // PFBHIP_FUSED_FFT=0: unfused second axis
+    int fused_doubled = -1;   // PFBHIP_FUSED_DOUBLED: -1 plan decides, 0 / 1 forced
+    bool sepscreen = true;    // PFBHIP_SEPSCREEN=0: no separable w-screen form
+    int tpad = 40;            // PFBHIP_TPAD
+    int tfft = 1;             // PFBHIP_TFFT
+    bool colruns = true;      // PFBHIP_COLRUNS=0: whole rows in the first-axis transforms
+    bool async_clear = true;  // PFBHIP_ASYNC_CLEAR=0: in-stream plane clear
+};
+
+static PlanSwitches read_plan_switches()
+{
+    PlanSwitches sw;
+    auto first = [](const char *name) -> int {  // first character of the value, -1 when unset
+        const char *e = std::getenv(name);
+        return e == nullptr ? -1 : e[0];
+    };
+    if (const char *e = std::getenv("PFBHIP_SCATTER")) {
+        const std::string v(e);
+        if (v == "auto") sw.scatter = ScatterForce::Auto;
+        else if (v == "walk") sw.scatter = ScatterForce::Walk;
+        else if (v == "block") sw.scatter = ScatterForce::Block;
+        else if (v == "rec") sw.scatter = ScatterForce::Rec;
+        else if (v == "rec_es") sw.scatter = ScatterForce::RecEs;
+        else PFB_REQUIRE(false, "PFBHIP_SCATTER=%s: expected auto, walk, block, rec or rec_es", e);
+    }
+    sw.wmode2 = first("PFBHIP_WMODE2") != '0';
+    sw.wd_block4 = first("PFBHIP_WD_BLOCK") == '4';
+    const int wc = first("PFBHIP_WD_COLOURS");
+    sw.wd_colours = wc == '0' ? 0 : (wc == '1' ? 1 : -1);
+    if (const char *e = std::getenv("PFBHIP_CHUNK")) sw.chunk = uint32_t(std::max(256, std::min(int(CHUNK), std::atoi(e))));
+    if (const char *e = std::getenv("PFBHIP_WD_CHUNK")) sw.wd_chunk = uint32_t(std::max(64, std::min(int(CHUNK), std::atoi(e))));
+    sw.rowfft = first("PFBHIP_ROWFFT") != '0';
+    sw.fused_fft = first("PFBHIP_FUSED_FFT") != '0';
+    const int fd = first("PFBHIP_FUSED_DOUBLED");
+    sw.fused_doubled = fd < 0 ? -1 : (fd == '1' ? 1 : 0);
+    sw.sepscreen = first("PFBHIP_SEPSCREEN") != '0';
+    if (const char *e = std::getenv("PFBHIP_TPAD")) sw.tpad = std::atoi(e);
+    if (const char *e = std::getenv("PFBHIP_TFFT")) sw.tfft = std::atoi(e);
+    sw.colruns = first("PFBHIP_COLRUNS") != '0';
+    sw.async_clear = first("PFBHIP_ASYNC_CLEAR") != '0';
+    return sw;
+}
+
+static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo, double whi, double tmax, double nmin)
 {
     const auto &prm = g->prm;
     size_t nrows = 0;
@@ -1225,13 +1235,8 @@ static void choose_kernel(pfbhip_gridder *g, double wlo, double whi, double tmax
     double bdw = 1.0;
     int bmode = 0, bnder = 0;
     // one-plane scheme (wmode 2): phase centre on axis, the record kernels available, not switched off
-    const char *wd_env = std::getenv("PFBHIP_WMODE2");
-    const char *sc_env = std::getenv("PFBHIP_SCATTER");
-    const char *ga_env = std::getenv("PFBHIP_GATHER");
-    const bool wd_allowed = !(wd_env != nullptr && wd_env[0] == '0') && g->info.lshift == 0.0 && g->info.mshift == 0.0 &&
-                            !(sc_env != nullptr && (std::string(sc_env) == "walk" || std::string(sc_env) == "block" ||
-                                                    std::string(sc_env) == "rec_es")) &&
-                            !(ga_env != nullptr && std::string(ga_env) == "walk");
+    const bool wd_allowed = sw.wmode2 && g->info.lshift == 0.0 && g->info.mshift == 0.0 &&
+                            (sw.scatter == ScatterForce::Auto || sw.scatter == ScatterForce::Rec);
     for (size_t i = 0; i < nrows; ++i) {
         const KernelRow &r = tab[i];
         if (prm.force_W > 0) {
@@ -1420,6 +1425,7 @@ static void nm1_range(const pfbhip_gridder_params &p, double lshift, double mshi
 static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq, const uint8_t *mask)
 {
     auto &prm = g->prm;
+    const PlanSwitches sw = read_plan_switches();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {  // verbosity >= 1: wall-clock of the plan-creation phases
         if (prm.verbosity < 1) return;
@@ -1501,7 +1507,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     }
 
     lap("upload + w range");
-    choose_kernel(g, wlo, whi, tmax, 1.0 + nm1min);
+    choose_kernel(g, sw, wlo, whi, tmax, 1.0 + nm1min);
     PFB_REQUIRE(info.nplanes >= 1 && info.nplanes < 100000, "unreasonable number of w-planes (%lld)",
                 (long long)info.nplanes);
 
@@ -1538,18 +1544,13 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // register-footprint scatter (k_grid_blk): runs of visibilities whose footprint origins share a 4 x 4-cell block
     // PFBHIP_SCATTER = walk | block forces the kernel; by default the register-footprint form is used when the plan has
     // enough work items to fill the GPU in each of its four colour launches (decided below, once the work list exists)
-    const char *senv = std::getenv("PFBHIP_SCATTER");
-    const std::string smode = senv != nullptr ? std::string(senv) : std::string("auto");
-    g->scatter_blk = smode != "walk";
+    g->scatter_blk = sw.scatter != ScatterForce::Walk;
     m.key_sub = (g->scatter_blk && nkeys * 64 < (int64_t(1) << 32) - 2) ? 64 : 1;
     // register-footprint scatters at W = 14 / 15: a 16 x 16-cell register frame anchored on 2 x 2-cell blocks (k_grid_blk,
     // k_grid_rec, k_grid_wd); PFBHIP_WD_BLOCK=4 keeps the 4 x 4 anchoring (17 / 18-cell frame on 3 x 20 lanes).  ES-plane plans whose
     // (tile, plane, block) key would not fit 32 bits (C5: 409 600 tiles x 64 planes) stay on 4 x 4 blocks.
-    {
-        const char *benv = std::getenv("PFBHIP_WD_BLOCK");
-        const bool want2 = (info.W == 14 || info.W == 15) && !(benv != nullptr && benv[0] == '4');
-        if (m.key_sub == 64 && want2 && nkeys * 256 < (int64_t(1) << 32) - 2) m.key_sub = 256;
-    }
+    const bool want2 = (info.W == 14 || info.W == 15) && !sw.wd_block4;
+    if (m.key_sub == 64 && want2 && nkeys * 256 < (int64_t(1) << 32) - 2) m.key_sub = 256;
     g->wd_bc = wd_block_edge(int(info.W), m.key_sub == 256);
     g->scatter_blk = m.key_sub > 1;  // without the block order in the 32-bit key the runs are ~1 long: the walk kernel is cheaper
     std::vector<WorkItem> work;
@@ -1586,7 +1587,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             chunk = 512;
             while (chunk < CHUNK && double(chunk) * 1.5 < double(info.nactive) / (3.0 * 768.0)) chunk *= 2;
         }
-        if (const char *cenv = std::getenv("PFBHIP_CHUNK")) chunk = uint32_t(std::max(256, std::min(int(CHUNK), std::atoi(cenv))));
+        if (sw.chunk != 0) chunk = sw.chunk;
         chunk_used = chunk;
         for (int64_t grp = 0; grp < (plane_sorted ? ngroups : 1); ++grp) {
             // planes [q, q + kp) are touched by visibilities whose first plane lies in [q - W + 1, q + kp - 1]
@@ -1636,10 +1637,8 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         if (info.wmode == 2) {
             PFB_REQUIRE(g->scatter_blk, "the one-plane w-scheme needs the block-ordered sort");
             // (PFBHIP_WD_COLOURS=1: the four colour launches whatever the size -- tests; 0: one launch with the atomic flush)
-            const char *cenv = std::getenv("PFBHIP_WD_COLOURS");
-            g->wd_small = coarse_items / std::max<size_t>(g->work_cnt.size(), 1) < size_t(8192) && !(cenv != nullptr && cenv[0] == '1');
-            if (cenv != nullptr && cenv[0] == '0') g->wd_small = true;
-        } else if (g->scatter_blk && smode != "block" && smode != "rec" && smode != "rec_es" && per_pass < size_t(2048)) g->scatter_blk = false;
+            g->wd_small = sw.wd_colours < 0 ? coarse_items / std::max<size_t>(g->work_cnt.size(), 1) < size_t(8192) : sw.wd_colours == 0;
+        } else if (g->scatter_blk && sw.scatter == ScatterForce::Auto && per_pass < size_t(2048)) g->scatter_blk = false;
     }
     {
         // colour slices of every group's list (LPT order kept inside a slice); chunks of a tile that has several in the
@@ -1655,7 +1654,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             const double per_launch = double(info.nactive) / (g->coloured ? 4.0 : 1.0);
             uint32_t c = 512;
             while (c < 2048 && double(c) * 1.5 < per_launch / (3.0 * 768.0)) c *= 2;
-            if (const char *cenv = std::getenv("PFBHIP_WD_CHUNK")) c = uint32_t(std::max(64, std::min(int(CHUNK), std::atoi(cenv))));
+            if (sw.wd_chunk != 0) c = sw.wd_chunk;
             schunk = std::min(c, chunk_used);
         }
         std::vector<WorkItem> wcol;
@@ -1707,21 +1706,17 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // its paired kernel evaluation the record form is 16 % ahead of k_grid_blk at 8192^2 / 19 planes (17.2 + 1.5 against 20.4 ms, apply
     // 69.9 against 72.2); at C5 (4 x 4 blocks: the key does not fit) it is 6.5 % ahead and the plane values eat that (1038.6 against
     // 1033.3 ms).  Default: the record form where the 16 x 16 frame applies and the plan is not C5's size; k_grid_blk otherwise.
-    const bool rec_es_auto = smode == "auto" && blk_frame16(int(info.W), g->wd_bc) && info.nactive <= int64_t(30000000);
+    const bool rec_es_auto = sw.scatter == ScatterForce::Auto && blk_frame16(int(info.W), g->wd_bc) && info.nactive <= int64_t(30000000);
     // (polynomial planes in several passes -- 5 to 10 planes, moderate omega -- can take the same route, k_plane_values in front of each
     // pass's scatter, on request only: 4096^2 / 10 planes, grid 3.70 + 0.37 ms of plane values against 4.20 for k_grid_blk, apply 13.05
     // against 13.02 ms -- every visibility is in every pass there, so the values pass costs what the kernel gains)
     const bool multi_poly = info.wmode == 1 && info.nplanes > g->kp_max;
     const bool rec_es = prm.do_wgridding && info.nactive > 0 && !work.empty() &&
-                        ((info.wmode == 0 && (smode == "rec_es" || rec_es_auto)) || (multi_poly && smode == "rec_es"));
-    g->scatter_rec = (rec_mode || rec_es) && g->scatter_blk && smode != "block";
+                        ((info.wmode == 0 && (sw.scatter == ScatterForce::RecEs || rec_es_auto)) ||
+                         (multi_poly && sw.scatter == ScatterForce::RecEs));
+    g->scatter_rec = (rec_mode || rec_es) && g->scatter_blk && sw.scatter != ScatterForce::Block;
     g->pval_from_gather = rec_mode && g->scatter_rec;
-    {
-        const char *genv = std::getenv("PFBHIP_GATHER");
-        g->gather_rw = rec_mode && (info.wmode == 2 || !(genv != nullptr && std::string(genv) == "walk"));
-        const char *denv = std::getenv("PFBHIP_RW_DEPTH");
-        g->rw_depth = denv != nullptr ? std::max(0, std::min(3, std::atoi(denv))) : 0;
-    }
+    g->gather_rw = rec_mode;
     if (rec_mode || g->scatter_rec) {
         g->d_rec.alloc(size_t(info.nactive) + REC_PAD);
         g->d_pval.alloc((size_t(info.nactive) + REC_PAD) * size_t(info.wmode == 2 ? info.nderiv : g->kp_max));
@@ -1756,22 +1751,6 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             PFB_HIP(hipGetLastError());
         }
         PFB_HIP(hipStreamSynchronize(st));
-        if (const char *wenv = std::getenv("PFBHIP_WSHARE")) {
-            float a = 1, b = 1, c = 1;
-            if (sscanf(wenv, "%f,%f,%f", &a, &b, &c) == 3 && a > 0 && b > 0 && c > 0) {
-                g->wshare[0] = a / (a + b + c);
-                g->wshare[1] = b / (a + b + c);
-                g->wshare[2] = c / (a + b + c);
-            }
-        }
-        const char *stenv = std::getenv("PFBHIP_STAMP");
-        if (stenv != nullptr && (stenv[0] == '1' || stenv[0] == '2')) {
-            g->stamp_mode = stenv[0] - '0';
-            size_t nitems = 0;
-            for (size_t c : g->col_cnt) nitems += c;
-            g->d_stamps.alloc(std::max<size_t>(nitems, 1) * 8);
-            PFB_HIP(hipMemset(g->d_stamps.p, 0, g->d_stamps.bytes()));
-        }
     }
     info.scatter_launches = (g->scatter_blk && g->coloured) ? 4 : 1;
     info.nwork = int64_t(work.size());
@@ -1893,19 +1872,15 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // (row pitch of the uv-plane buffer: see the B pitch below; rocFFT row plans on A need the dense pitch)
     {
         RowFFTPlan probe;
-        const char *renv0 = std::getenv("PFBHIP_ROWFFT");
-        const bool own_v = !(renv0 != nullptr && renv0[0] == '0') && rowfft_make_plan(info.nv, &probe);
-        const char *aenv = std::getenv("PFBHIP_APAD");
-        g->geom.apitch = int(info.nv) + (own_v ? (aenv != nullptr ? std::max(0, std::atoi(aenv)) : 8) : 0);
+        const bool own_v = sw.rowfft && rowfft_make_plan(info.nv, &probe);
+        g->geom.apitch = int(info.nv) + (own_v ? 8 : 0);
     }
     g->plane_stride = size_t(info.nu) * size_t(g->geom.apitch);
     g->d_grid.alloc(g->plane_stride * size_t(g->kp_max));
     g->grid_cur = g->d_grid.p;
     {
-        const char *aenv = std::getenv("PFBHIP_ASYNC_CLEAR");
-        const bool want = !(aenv != nullptr && aenv[0] == '0');
         // one pass over the planes (otherwise the buffer is reused inside the apply) and a second buffer of <= 40 GB
-        g->async_clear = want && info.nplanes <= g->kp_max && info.nactive > 0 && g->d_grid.bytes() <= (size_t(40) << 30);
+        g->async_clear = sw.async_clear && info.nplanes <= g->kp_max && info.nactive > 0 && g->d_grid.bytes() <= (size_t(40) << 30);
         if (g->async_clear) {
             g->d_grid2.alloc(g->plane_stride * size_t(g->kp_max));
             PFB_HIP(hipStreamCreateWithFlags(&g->clear_stream, hipStreamNonBlocking));
@@ -1923,10 +1898,8 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // {1,3,5} x 2^a (every size grid_size() prefers), with the pad / crop / w-screen of the second axis
     // fused into its load / store; rocFFT row plans otherwise.  PFBHIP_FUSED_FFT=0 / PFBHIP_ROWFFT=0
     // force the rocFFT paths (used by the tests to keep both alive).
-    const char *fenv = std::getenv("PFBHIP_FUSED_FFT");
-    const char *renv = std::getenv("PFBHIP_ROWFFT");
-    const bool own_rows = !(renv != nullptr && renv[0] == '0');
-    const bool want_fused = !(fenv != nullptr && fenv[0] == '0');
+    const bool own_rows = sw.rowfft;
+    const bool want_fused = sw.fused_fft;
     if (own_rows || want_fused) (void)g->rowfft_u.init(info.nu);
     // Doubled shapes (20480, 24576, 32768 points) run the plain row kernel on both axes and keep the separate pad / crop
     // kernels.  Their dedicated fused kernels (k_fused_fft_crop2 / k_fused_pad_fft2: even / odd half transforms combined
@@ -1935,8 +1908,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // a 16384^2 image / 20480^2 grid with 4 planes, so they stay behind PFBHIP_FUSED_DOUBLED=1 (tests keep them alive).
     // Round 3: at 20480 points the waiting half is parked in LDS (k_fused_fft_crop2 / k_fused_pad_fft2, STASH) and the fused
     // kernels are the default; PFBHIP_FUSED_DOUBLED=0 / 1 forces the choice for every doubled shape.
-    const char *denv = std::getenv("PFBHIP_FUSED_DOUBLED");
-    const bool fuse_doubled = denv != nullptr ? denv[0] == '1' : fused_doubled_stashes(g->rowfft_u);
+    const bool fuse_doubled = sw.fused_doubled >= 0 ? sw.fused_doubled == 1 : fused_doubled_stashes(g->rowfft_u);
     {  // the screen geometry serves the fused kernels and the separate pad / crop kernels alike
         FusedGeom &fg = g->fgeom;
         fg.nx = int(prm.nx);
@@ -1959,21 +1931,16 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     g->plane_groups.clear();
     g->d_tau.release();
     if (g->fused) {
-        // screen form per pass: composite polynomials of the whole phase where it is small (PFBHIP_SCREENPOLY=0 disables), else
-        // the separable form (column table x row factor x residual polynomials; PFBHIP_SEPSCREEN=0 disables), else n - 1 and
-        // sincos per pixel and plane
-        const char *penv = std::getenv("PFBHIP_SCREENPOLY");
-        const bool want = !(penv != nullptr && penv[0] == '0');
-        const char *qenv = std::getenv("PFBHIP_SEPSCREEN");
-        const bool want_sep = !(qenv != nullptr && qenv[0] == '0');
+        // screen form per pass: composite polynomials of the whole phase where it is small, else the separable form (column
+        // table x row factor x residual polynomials; PFBHIP_SEPSCREEN=0 disables), else n - 1 and sincos per pixel and plane
         bool any_sep = false;
         for (int p0 = 0; p0 < info.nplanes; p0 += g->kp_max) {
             FusedPlanes fp;
             fp.kp = int(std::min<int64_t>(g->kp_max, info.nplanes - p0));
             for (int k = 0; k < FUSED_MAXPLANES; ++k) fp.w[k] = k < fp.kp ? g->wplanes[size_t(p0 + k)] : 0.0;
             // (the doubled shapes' kernels have the separable and the general form only)
-            if (want && prm.do_wgridding && !g->rowfft_u.pl.doubled) fused_planes_fit(g->fgeom, fp);
-            if (fp.nsc == 0 && want_sep && prm.do_wgridding) fused_planes_fit(g->fgeom, fp, true);
+            if (prm.do_wgridding && !g->rowfft_u.pl.doubled) fused_planes_fit(g->fgeom, fp);
+            if (fp.nsc == 0 && sw.sepscreen && prm.do_wgridding) fused_planes_fit(g->fgeom, fp, true);
             any_sep = any_sep || fp.sep != 0;
             g->plane_groups.push_back(fp);
         }
@@ -1986,7 +1953,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             for (size_t grp = 0; grp < g->plane_groups.size(); ++grp)
                 g->plane_groups[grp].tau = g->d_tau.p + grp * size_t(g->kp_max) * size_t(prm.nx);
         }
-        if ((prm.verbosity > 0 || std::getenv("PFBHIP_DEBUG_SCREEN") != nullptr) && !g->plane_groups.empty()) {
+        if (prm.verbosity > 0 && !g->plane_groups.empty()) {
             int n_sc = 0, n_sep = 0, nsc_max = 0;
             for (const FusedPlanes &fp : g->plane_groups) {
                 n_sc += fp.nsc > 0 && !fp.sep;
@@ -2008,27 +1975,18 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     info.scatter_mode = g->scatter_rec ? 2 : (g->scatter_blk ? 1 : 0);
     // Row pitch of B.  A workgroup of the transposing first-axis FFT touches B[y][u] for one u and every y: with a pitch of
     // nu * 16 bytes (a multiple of 2^15 for every size the plan picks) all of a row's 16-byte pieces fall on one L2 /
-    // memory channel.  8 more elements (128 bytes) per row walk the channels instead (PFBHIP_BPAD overrides; the rocFFT
-    // second axis needs the dense pitch).
-    {
-        const char *benv = std::getenv("PFBHIP_BPAD");
-        const int bpad = g->fused ? (benv != nullptr ? std::max(0, std::atoi(benv)) : 8) : 0;
-        g->geom.bpitch = int(info.nu) + bpad;
-        g->fgeom.bpitch = g->geom.bpitch;
-    }
+    // memory channel.  8 more elements (128 bytes) per row walk the channels instead (the rocFFT second axis needs the dense
+    // pitch).
+    g->geom.bpitch = int(info.nu) + (g->fused ? 8 : 0);
+    g->fgeom.bpitch = g->geom.bpitch;
     g->bstride = size_t(prm.ny) * size_t(g->geom.bpitch);
     // Degridding side of the transposing first-axis FFT: the fused pad kernel stores Bt[u][y] (scattered 16-byte stores that
     // meet in L2, as on the gridding side) and the first-axis transform of row u reads its row of Bt contiguously -- a
     // 16-byte GATHER in that transform's load phase cost 0.3 ms per plane at C2, scattered stores cost 0.1.  The pitch is
     // kept off the power of two for the same reason as bpitch (PFBHIP_TPAD elements, multiple of 8 = whole lines; 0 = off).
     g->fgeom.tpitch = 0;
-    {
-        const char *tenv = std::getenv("PFBHIP_TPAD");
-        const int tpad = tenv != nullptr ? std::atoi(tenv) : 40;
-        if (g->fused && g->rowfft_v.ok && g->rowfft_u.ok && tpad > 0 &&
-            (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v)))
-            g->fgeom.tpitch = int(prm.ny) + ((tpad + 7) / 8) * 8;
-    }
+    if (g->fused && g->rowfft_v.ok && g->rowfft_u.ok && sw.tpad > 0 && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v)))
+        g->fgeom.tpitch = int(prm.ny) + ((sw.tpad + 7) / 8) * 8;
     g->bstride = std::max(g->bstride, size_t(info.nu) * size_t(g->fgeom.tpitch));
     lap("row-FFT tables + w-screens");
     g->d_gridB.alloc(g->bstride * size_t(g->fused ? g->kp_max : 1));
@@ -2102,8 +2060,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                 info.used_cells += std::min<int64_t>(TILE, info.nu - tu * TILE) * (int64_t(r.y - r.x) + int64_t(r.w - r.z));
             }
         }
-        if (std::getenv("PFBHIP_COLRUNS") != nullptr && std::getenv("PFBHIP_COLRUNS")[0] == '0')
-        {
+        if (!sw.colruns) {
             std::fill(runs_t.begin(), runs_t.end(), make_int4(0, int(info.nv), 0, 0));
             info.used_cells = 0;
             colruns_off = true;
@@ -2205,8 +2162,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     }
     info.occ_rows = int32_t(g->occ_rows);
     {
-        const char *tenv = std::getenv("PFBHIP_TFFT");
-        const int want = tenv != nullptr ? std::atoi(tenv) : 1;
+        const int want = sw.tfft;
         // (doubled first-axis shapes: only where the waiting half transform is parked in LDS -- 20480 points --, unless forced)
         const bool v_ok = g->rowfft_v.ok && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v));
         g->tfft = (want != 0 && g->fused && v_ok && g->occ_rows > 0) ? want : 0;
@@ -2289,7 +2245,6 @@ int pfbhip_gridder_get_info(const pfbhip_gridder *g, pfbhip_gridder_info *info)
         std::swap(info->nu, info->nv);          // report the caller's orientation (the plan holds the transposed problem)
         std::swap(info->lshift, info->mshift);
         info->device_bytes = g->device_bytes();
-        info->graph_replays = g->graph_replays;
         info->scatter_block = g->wd_bc;
         info->reserved0 = 0;
     });
@@ -2439,77 +2394,9 @@ int pfbhip_gridder_set_weights(pfbhip_gridder *g, const double *wgt_host)
     });
 }
 
-static void hessian_dev_eager(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
-                              double *out_dev);
-static void apply_eager(pfbhip_gridder *g, const double *x_dev, const double *beam_in_dev, const double *beam_out_dev, double scale,
-                        double eta, const double *addend_dev, double *out_dev);
-
-// The apply, replayed from a captured graph where that pays (see pfbhip_gridder::ApplyGraph).
-static void hessian_dev_impl(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
-                             double *out_dev)
-{
-    if (g->graph_mode < 0) {
-        const char *e = std::getenv("PFBHIP_GRAPH");
-        g->graph_mode = (e != nullptr && e[0] == '1' && g->fft_info == nullptr) ? 1 : 0;  // (rocFFT plans: not captured)
-    }
-    if (g->graph_mode == 0 || g->timer.enabled || g->stamp_mode != 0 || g->info.nwork == 0) {
-        hessian_dev_eager(g, x_dev, beam_dev, eta, wsum, out_dev);
-        return;
-    }
-    PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the Hessian");
-    pfbhip_gridder::ApplyGraph *slot = nullptr;
-    for (auto &ag : g->graphs)
-        if (ag.x == x_dev && ag.beam == beam_dev && ag.out == out_dev && ag.eta == eta && ag.wsum == wsum) slot = &ag;
-    if (slot == nullptr) {
-        if (g->graphs.size() >= 8) {  // (a caller cycling through many buffers: forget the oldest)
-            if (g->graphs.front().exec) (void)hipGraphExecDestroy(g->graphs.front().exec);
-            g->graphs.erase(g->graphs.begin());
-        }
-        g->graphs.push_back(pfbhip_gridder::ApplyGraph{x_dev, beam_dev, out_dev, eta, wsum, 0, nullptr});
-        slot = &g->graphs.back();
-    }
-    if (slot->exec != nullptr) {
-        PFB_HIP(hipGraphLaunch(slot->exec, g->stream));
-        ++g->graph_replays;
-        return;
-    }
-    if (slot->seen++ == 0) {  // first call with this key: eager (allocations, kernel attributes, plan-lazy state)
-        hessian_dev_eager(g, x_dev, beam_dev, eta, wsum, out_dev);
-        return;
-    }
-    hipGraph_t graph = nullptr;
-    PFB_HIP(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-    try {
-        hessian_dev_eager(g, x_dev, beam_dev, eta, wsum, out_dev);
-    } catch (...) {
-        (void)hipStreamEndCapture(g->stream, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        g->graph_mode = 0;
-        throw;
-    }
-    hipError_t err = hipStreamEndCapture(g->stream, &graph);
-    if (err == hipSuccess && graph != nullptr) err = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (err != hipSuccess || slot->exec == nullptr) {  // capture not possible on this path: stay eager for good
-        (void)hipGetLastError();
-        slot->exec = nullptr;
-        g->graph_mode = 0;
-        hessian_dev_eager(g, x_dev, beam_dev, eta, wsum, out_dev);
-        return;
-    }
-    PFB_HIP(hipGraphLaunch(slot->exec, g->stream));  // (the capture itself ran nothing)
-    ++g->graph_replays;
-}
-
-static void hessian_dev_eager(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
-                              double *out_dev)
-{
-    apply_eager(g, x_dev, beam_dev, beam_dev, wsum > 0.0 ? 1.0 / wsum : 1.0, eta, eta != 0.0 ? x_dev : nullptr, out_dev);
-}
-
 // out = beam_out * R^H W R (beam_in * x) * scale + eta * addend   (every image resident in HBM; beams and addend may be NULL)
-static void apply_eager(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, const double *beam_out_dev, double scale,
-                        double eta, const double *addend_dev, double *out_dev)
+static void apply_op(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, const double *beam_out_dev, double scale,
+                     double eta, const double *addend_dev, double *out_dev)
 {
     PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the Hessian");
     hipStream_t st = g->stream;
@@ -2555,6 +2442,12 @@ static void apply_eager(pfbhip_gridder *g, const double *x_dev, const double *be
     (void)npix;
 }
 
+static void hessian_dev_impl(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
+                             double *out_dev)
+{
+    apply_op(g, x_dev, beam_dev, beam_dev, wsum > 0.0 ? 1.0 / wsum : 1.0, eta, eta != 0.0 ? x_dev : nullptr, out_dev);
+}
+
 // The exact residual of one partition (gridder.py:962-1016 of the reference: dirty2vis of beam * model, vis2dirty with the
 // imaging weights, subtracted from the dirty image): out = acc - R^H W R (beam * model), every image resident in HBM -- the
 // subtraction is the eta * addend term of the fused second-axis kernel's epilogue (scale -1, eta 1), not another pass.
@@ -2564,7 +2457,7 @@ int pfbhip_gridder_residual_dev(pfbhip_gridder *g, const double *model_dev, cons
     return guarded([&] {
         PFB_REQUIRE(g && model_dev && acc_dev && out_dev, "NULL argument");
         PFB_REQUIRE(model_dev != out_dev, "the residual cannot overwrite the model image");
-        apply_eager(g, model_dev, beam_dev, nullptr, -1.0, 1.0, acc_dev, out_dev);
+        apply_op(g, model_dev, beam_dev, nullptr, -1.0, 1.0, acc_dev, out_dev);
         PFB_HIP(hipStreamSynchronize(g->stream));
     });
 }
@@ -2760,22 +2653,6 @@ int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, dou
         PFB_REQUIRE(g && dirty_dev && vis_sorted_dev, "NULL argument");
         g->grid_and_finalize(reinterpret_cast<const double2 *>(vis_sorted_dev), nullptr, 1.0, 0.0, nullptr, dirty_dev);
         PFB_HIP(hipStreamSynchronize(g->stream));
-    });
-}
-
-// Diagnostic (PFBHIP_STAMP=1 at plan creation): the in-kernel phase stamps of the last record-scatter pass, 8 words per
-// colour work item; returns the number of items through *nitems (0: stamping is off).
-int pfbhip_gridder_debug_stamps(pfbhip_gridder *g, unsigned long long *out_host, int64_t capacity_items, int64_t *nitems)
-{
-    return guarded([&] {
-        PFB_REQUIRE(g && nitems, "NULL argument");
-        const int64_t n = g->d_stamps.p ? int64_t(g->d_stamps.n / 8) : 0;
-        *nitems = n;
-        if (n && out_host) {
-            PFB_HIP(hipStreamSynchronize(g->stream));
-            PFB_HIP(hipMemcpy(out_host, g->d_stamps.p, size_t(std::min(n, capacity_items)) * 8 * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost));
-        }
     });
 }
 

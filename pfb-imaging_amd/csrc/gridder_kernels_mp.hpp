@@ -43,7 +43,6 @@ struct GroupArgs {
     // oldest on their SIMDs), 1 and 2.  The SIMD arbitrates VALU issue by age, so equal shares finish 37K / 50K / 62K
     // cycles apart (stamps, C2) and the barrier waits for the youngest.
     float wshare[3];
-    unsigned long long *dbg; // diagnostic build / PFBHIP_STAMP=1 only: 8 words per work item of in-kernel phase stamps (else NULL)
 };
 
 // weight of plane `plane` for abscissa/coordinate pw
@@ -497,7 +496,7 @@ __global__ void __launch_bounds__(blk_threads(KP)) k_grid_blk(GroupArgs ga, cons
 // Scatter, register-footprint form driven by per-visibility RECORDS (k_grid_rec): single-pass plans with polynomial
 // w-planes (every visibility touches every plane of the one pass).
 //
-// What the in-kernel stamps of k_grid_blk / the first k_grid_rec showed (tools/stamp_scatter.py, C2): a wave issues at
+// What in-kernel phase stamps of k_grid_blk / the first k_grid_rec showed (C2): a wave issues at
 // most ONE instruction -- vector, scalar, LDS, branch or wait -- per 4 cycles, so a visibility costs a wave 4 x (all its
 // instructions), not 4 x (its FMAs); the three waves of a SIMD overlap, but the SIMD arbitrates by age, so with equal
 // shares the oldest wave of a SIMD finishes at 60 % of the youngest wave's time and the barrier waits for the youngest.
@@ -551,8 +550,6 @@ __global__ void __launch_bounds__(blk_threads(KP)) k_grid_rec(GroupArgs ga, cons
 
     const uint32_t item = blockIdx.x;
     if (item >= a.nwork) return;
-    const bool stamp = ga.dbg != nullptr;
-    const unsigned long long ts0 = stamp ? __builtin_readcyclecounter() : 0ull;
     const WorkItem wi = a.work[item];
     const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const uint32_t n = wi.end - wi.begin;
@@ -660,7 +657,6 @@ __global__ void __launch_bounds__(blk_threads(KP)) k_grid_rec(GroupArgs ga, cons
         return (D & 1) ? fma(o, z, e) : fma(o, z, e);
     };
     static_assert((D & 1) == 0, "kernel_value assumes an even polynomial degree");
-    const unsigned long long ts1 = stamp ? __builtin_readcyclecounter() : 0ull;
     if (nmine > 0) {  // pair 0 -> lines 0, 1
         *reinterpret_cast<double *>(wq[2]) = kernel_value(zq[0]);
         zq[0] = *reinterpret_cast<const double *>(zptr);
@@ -764,27 +760,8 @@ __global__ void __launch_bounds__(blk_threads(KP)) k_grid_rec(GroupArgs ga, cons
     }
     asm volatile("" ::"v"(warm));
     if (cur >= 0) flush(cur);
-    const unsigned long long ts2 = stamp ? __builtin_readcyclecounter() : 0ull;
     __syncthreads();
-    const unsigned long long ts3 = stamp ? __builtin_readcyclecounter() : 0ull;
     blk_tile_to_grid<W, KP>(ga, wi, lds, bu, bv, grid);
-    if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long ts4 = __builtin_readcyclecounter();
-        unsigned long long *d = ga.dbg + size_t(item) * 8;
-        if (threadIdx.x == 0) {
-            d[0] = ts1 - ts0;  // prologue (records requested, tile cleared, tables, barrier)
-            d[1] = ts2 - ts1;  // wave 0: its share of the visibilities
-            d[2] = ts3 - ts2;  // wave 0: wait for the slowest wave
-            d[3] = ts4 - ts3;  // tile -> uv-grid
-            d[4] = n;
-            d[7] = wi.tile;
-        }
-        if (threadIdx.x == uint32_t(BLK_THREADS) - 64) {
-            d[5] = ts2 - ts1;  // last wave's share
-            d[6] = ts3 - ts2;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -821,27 +798,6 @@ __device__ __forceinline__ void rw_load_row(const char *base, const char *base2,
     }
 }
 
-// Prefetch distance of the row walk, in footprint rows (experiment, round 3).  Left to itself the compiler keeps TWO
-// ds_read_b128 in flight (issue 2, wait for the first, 2 FMAs ...).  With D > 0 the reads of row I + D are issued before the
-// FMAs of row I, D * KP reads in flight (at most 15: lgkmcnt is a 4-bit counter), in D + 1 static register sets.
-// MEASURED on C2 (W = 16, KP = 3): D = 3 is 26 % SLOWER (2.24 vs 1.77 ms) -- see DESIGN.md section 5.2; D = 0 (the compiler's
-// schedule) stays the default, PFBHIP_RW_DEPTH selects 1..3 for the (16, 3) instantiation.
-template <int KP, int D, int I>
-__device__ __forceinline__ void rw_steps(const char *base, const char *base2, double ku, double (&sr)[KP], double (&si)[KP],
-                                         double2 (&buf)[D + 1][KP])
-{
-    if constexpr (I < 16) {
-        if constexpr (I + D < 16) rw_load_row<KP, I + D>(base, base2, buf[(I + D) % (D + 1)]);
-        __builtin_amdgcn_sched_barrier(0);  // keeps the requests above in front of the FMAs below
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            fmac_row_bcast<I>(sr[k], ku, buf[I % (D + 1)][k].x);  // (v_mul_f64 has no DPP form: the accumulators start from zero)
-            fmac_row_bcast<I>(si[k], ku, buf[I % (D + 1)][k].y);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        rw_steps<KP, D, I + 1>(base, base2, ku, sr, si, buf);
-    }
-}
 // (NS = W steps: the rows past the support carry zero kernel values)
 template <int NS, int KP, int I>
 __device__ __forceinline__ void rw_steps0(const char *base, const char *base2, double ku, double (&sr)[KP], double (&si)[KP])
@@ -857,15 +813,6 @@ __device__ __forceinline__ void rw_steps0(const char *base, const char *base2, d
         rw_steps0<NS, KP, I + 1>(base, base2, ku, sr, si);
     }
 }
-template <int KP, int D, int I>
-__device__ __forceinline__ void rw_prologue(const char *base, const char *base2, double2 (&buf)[D + 1][KP])
-{
-    if constexpr (I < D) {
-        rw_load_row<KP, I>(base, base2, buf[I]);
-        rw_prologue<KP, D, I + 1>(base, base2, buf);
-    }
-}
-
 // sum over the 8 lanes of this lane's half row (lanes 0..7 / 8..15 of a 16-lane row), left in every lane of the half
 __device__ __forceinline__ double half_row_sum(double v)
 {
@@ -881,7 +828,7 @@ __device__ __forceinline__ double half_row_sum(double v)
     return v;
 }
 
-template <int W, int KP, int PD = 0>
+template <int W, int KP>
 __global__ void __launch_bounds__(MP_THREADS) k_degrid_rw(GroupArgs ga, const VisRec *__restrict__ rec,
                                                            const double *__restrict__ kwtab, const double2 *__restrict__ grid,
                                                            double2 *__restrict__ sacc, const double *__restrict__ swgt,
@@ -896,8 +843,6 @@ __global__ void __launch_bounds__(MP_THREADS) k_degrid_rw(GroupArgs ga, const Vi
 
     const uint32_t item = blockIdx.x;
     if (item >= a.nwork) return;
-    const bool stamp = ga.dbg != nullptr;
-    const unsigned long long ts0 = stamp ? __builtin_readcyclecounter() : 0ull;
     const WorkItem wi = a.work[item];
     const int bu = int(wi.tile / uint32_t(a.ntv)) * TILE;
     const int bv = int(wi.tile % uint32_t(a.ntv)) * TILE;
@@ -962,7 +907,6 @@ __global__ void __launch_bounds__(MP_THREADS) k_degrid_rw(GroupArgs ga, const Vi
     };
     static_assert((D & 1) == 0, "kernel_value assumes an even polynomial degree");
     __syncthreads();
-    const unsigned long long ts1 = stamp ? __builtin_readcyclecounter() : 0ull;
 
     const char *tbase = reinterpret_cast<const char *>(tiles);
     for (uint32_t jb = wi.begin + wave * 4; jb < wi.end; jb += stride) {
@@ -988,13 +932,7 @@ __global__ void __launch_bounds__(MP_THREADS) k_degrid_rw(GroupArgs ga, const Vi
 #pragma unroll
             for (int k = 0; k < KP; ++k) sr[k] = si[k] = 0.0;
             asm volatile("s_nop 1" : "+v"(ku));  // VALU write -> DPP read of the same register needs 2 wait states
-            if constexpr (PD == 0) {
-                rw_steps0<W, KP, 0>(base, base2, ku, sr, si);
-            } else {
-                double2 cells[PD + 1][KP];
-                rw_prologue<KP, PD, 0>(base, base2, cells);
-                rw_steps<KP, PD, 0>(base, base2, ku, sr, si, cells);
-            }
+            rw_steps0<W, KP, 0>(base, base2, ku, sr, si);
             double tr = 0.0, ti = 0.0;
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
@@ -1031,23 +969,6 @@ __global__ void __launch_bounds__(MP_THREADS) k_degrid_rw(GroupArgs ga, const Vi
         key = nkey;
 #pragma unroll
         for (int k = 0; k < KP; ++k) kw[k] = nkw[k];
-    }
-    if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long ts2 = __builtin_readcyclecounter();
-        unsigned long long *d = ga.dbg + size_t(item) * 8;
-        if (threadIdx.x == 0) {
-            d[0] = ts1 - ts0;  // tile load
-            d[1] = ts2 - ts1;  // wave 0: its rounds
-            d[2] = 0;
-            d[3] = 0;
-            d[4] = wi.end - wi.begin;
-            d[7] = wi.tile;
-        }
-        if (threadIdx.x == MP_THREADS - 64) {
-            d[5] = ts2 - ts1;  // last wave's rounds
-            d[6] = ts2 - ts0;
-        }
     }
 }
 

@@ -128,8 +128,6 @@ __global__ void __launch_bounds__(wd_threads()) k_grid_wd(GroupArgs ga, WdArgs w
 
     const uint32_t item = blockIdx.x;
     if (item >= a.nwork) return;
-    const bool stamp = ga.dbg != nullptr;
-    const unsigned long long ts0 = stamp ? __builtin_readcyclecounter() : 0ull;
     const WorkItem wi = a.work[item];
     const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const uint32_t n = wi.end - wi.begin;
@@ -273,7 +271,6 @@ __global__ void __launch_bounds__(wd_threads()) k_grid_wd(GroupArgs ga, WdArgs w
                 *reinterpret_cast<double *>(wptr2 + line * (WD_LINE * 8)) = evens(c2, std::integral_constant<int, D2>{}, z, z2);
         }
     };
-    const unsigned long long ts1 = stamp ? __builtin_readcyclecounter() : 0ull;
     if (nmine > 0) {
         if constexpr (PAIR) {  // pair 0 -> lines 0, 1
             eval_pair(zq[0], wq[2]);
@@ -412,27 +409,8 @@ __global__ void __launch_bounds__(wd_threads()) k_grid_wd(GroupArgs ga, WdArgs w
     }
     asm volatile("" ::"v"(warm));
     if (cur >= 0) flush(cur);
-    const unsigned long long ts2 = stamp ? __builtin_readcyclecounter() : 0ull;
     __syncthreads();
-    const unsigned long long ts3 = stamp ? __builtin_readcyclecounter() : 0ull;
     blk_tile_to_grid<W, 1, LS, 256>(ga, wi, lds, bu, bv, grid);
-    if (stamp) {  // PFBHIP_STAMP=1: phase stamps (tools/stamp_scatter.py), the layout of k_grid_rec
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long ts4 = __builtin_readcyclecounter();
-        unsigned long long *d = ga.dbg + size_t(item) * 8;
-        if (threadIdx.x == 0) {
-            d[0] = ts1 - ts0;
-            d[1] = ts2 - ts1;
-            d[2] = ts3 - ts2;
-            d[3] = ts4 - ts3;
-            d[4] = n;
-            d[7] = wi.tile;
-        }
-        if (threadIdx.x == uint32_t(BLK_THREADS) - 64) {
-            d[5] = ts2 - ts1;
-            d[6] = ts3 - ts2;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -473,8 +451,6 @@ __global__ void __launch_bounds__(wd_gather_threads(NJ)) k_degrid_wd(GroupArgs g
 
     const uint32_t item = blockIdx.x;
     if (item >= a.nwork) return;
-    const bool stamp = ga.dbg != nullptr;
-    const unsigned long long ts0 = stamp ? __builtin_readcyclecounter() : 0ull;
     const WorkItem wi = a.work[item];
     const int bu = int(wi.tile / uint32_t(a.ntv)) * TILE;
     const int bv = int(wi.tile % uint32_t(a.ntv)) * TILE;
@@ -547,7 +523,6 @@ __global__ void __launch_bounds__(wd_gather_threads(NJ)) k_degrid_wd(GroupArgs g
     };
     const int bsel = (b & 7) < NJ ? (b & 7) : 0;
     __syncthreads();
-    const unsigned long long ts1 = stamp ? __builtin_readcyclecounter() : 0ull;
 
     const char *tbase = reinterpret_cast<const char *>(tiles);
     for (uint32_t jb = wi.begin + wave * 4; jb < wi.end; jb += stride) {
@@ -622,23 +597,6 @@ __global__ void __launch_bounds__(wd_gather_threads(NJ)) k_degrid_wd(GroupArgs g
         key = nkey;
 #pragma unroll
         for (int k = 0; k < NJ; ++k) cwv[k] = ncw[k];
-    }
-    if (stamp) {  // PFBHIP_STAMP=2
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long ts2 = __builtin_readcyclecounter();
-        unsigned long long *d = ga.dbg + size_t(item) * 8;
-        if (threadIdx.x == 0) {
-            d[0] = ts1 - ts0;
-            d[1] = ts2 - ts1;
-            d[2] = 0;
-            d[3] = 0;
-            d[4] = wi.end - wi.begin;
-            d[7] = wi.tile;
-        }
-        if (threadIdx.x == uint32_t(NT) - 64) {
-            d[5] = ts2 - ts1;
-            d[6] = ts2 - ts0;
-        }
     }
 }
 

@@ -1366,43 +1366,6 @@ void fused_pad_fft(const RowFFT &f, const FusedGeom &g, const uint8_t *occ_dev, 
 
 using namespace pfbhip;
 
-// Diagnostic: the plain row transform with its global loads (MODE & 1) and / or stores (MODE & 2) taken out -- what is left
-// of the row time tells how much of it is the passes themselves.  PFBHIP_RF_MODE selects it in pfbhip_debug_rowfft's timing.
-template <int MODE>
-struct DbgLoad {
-    const double2 *row;
-    __device__ __forceinline__ double2 operator()(int i, int) const
-    {
-        return (MODE & 1) ? make_double2(double(i), 1.0) : row[i];
-    }
-};
-template <int MODE>
-struct DbgStore {
-    double2 *row;
-    __device__ __forceinline__ void operator()(int i, double2 v) const
-    {
-        if (!(MODE & 2) || v.x == 1.2345e300) row[i] = v;
-    }
-};
-template <class S, int MODE>
-__global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_rowfft_dbg(const double2 *tw, double2 *data, int nrows, size_t pitch)
-{
-    extern __shared__ double rf_lds[];
-    const int row = blockIdx.x;
-    if (row >= nrows) return;
-    DbgLoad<MODE> ld{data + size_t(row) * pitch};
-    DbgStore<MODE> st{data + size_t(row) * pitch};
-    rf_row<S>(tw, ld, st, true, rf_lds);
-}
-template <class S, int MODE>
-static void launch_dbg(const RowFFTPlan &pl, double2 *d, int nrows, size_t pitch)
-{
-    static bool attr = false;
-    rf_allow_lds(&k_rowfft_dbg<S, MODE>, &attr);
-    hipLaunchKernelGGL((k_rowfft_dbg<S, MODE>), dim3(uint32_t(nrows)), dim3(S::T), size_t(S::LDS_BYTES), nullptr, pl.twiddle, d,
-                       nrows, pitch);
-}
-
 extern "C" {
 
 // Debug / benchmark entry: in-place batched row transform of (nrows, n) complex doubles on the host.
@@ -1425,18 +1388,7 @@ int pfbhip_debug_rowfft(double *data_host, int64_t n, int64_t nrows, int inverse
             PFB_HIP(hipMemcpy(s.p, d.p, tot * sizeof(double2), hipMemcpyDeviceToDevice));
             rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
             PFB_HIP(hipEventRecord(a, nullptr));
-            const char *dm = std::getenv("PFBHIP_RF_MODE");
-            if (dm != nullptr && n == 10240) {
-                using S = RfShape<5, 11>;
-                for (int r = 0; r < reps; ++r) switch (std::atoi(dm)) {
-                        case 0: launch_dbg<S, 0>(pl, s.p, int(nrows), size_t(n)); break;
-                        case 1: launch_dbg<S, 1>(pl, s.p, int(nrows), size_t(n)); break;
-                        case 2: launch_dbg<S, 2>(pl, s.p, int(nrows), size_t(n)); break;
-                        default: launch_dbg<S, 3>(pl, s.p, int(nrows), size_t(n)); break;
-                    }
-            } else {
-                for (int r = 0; r < reps; ++r) rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
-            }
+            for (int r = 0; r < reps; ++r) rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
             PFB_HIP(hipEventRecord(b, nullptr));
             PFB_HIP(hipEventSynchronize(b));
             float ms = 0;

@@ -257,7 +257,7 @@ class Gridder:
                     tile=i["tile"], wmode=i["wmode"], wcenter=i["wcenter"], whalf=i["whalf"], nderiv=i["nderiv"])
 
     def refresh_info(self):
-        """Re-read the plan's info (counters such as ``graph_replays`` change over its life)."""
+        """Re-read the plan's info."""
         info = GridderInfo()
         check(lib().pfbhip_gridder_get_info(self._h, ct.byref(info)))
         self.info = info.asdict()

@@ -84,6 +84,20 @@ def test_no_gpu_paths_fail_loudly_or_work_on_host():
                       pixsize_x=1e-5, pixsize_y=1e-5, epsilon=1e-5, do_wgridding=True)
 
 
+def test_unknown_scatter_switch_fails_plan_creation(monkeypatch):
+    """PFBHIP_SCATTER is read before any device work: a value the plan does not know is refused, naming the valid ones."""
+    from pfb_imaging_amd import _lib
+
+    monkeypatch.setenv("PFBHIP_SCATTER", "records")
+    p = _lib.GridderParams(nrow=1, nchan=1, nx=16, ny=16, pixsize_x=1e-5, pixsize_y=1e-5, epsilon=1e-5, sigma_min=1.1,
+                           sigma_max=2.6, do_wgridding=1)
+    uvw, freq, h = np.zeros((1, 3)), np.ones(1), ct.c_void_p()
+    st = _lib.lib().pfbhip_gridder_create(ct.byref(p), uvw.ctypes.data_as(ct.c_void_p), freq.ctypes.data_as(ct.c_void_p),
+                                          None, ct.byref(h))
+    assert st != 0 and not h.value
+    assert "PFBHIP_SCATTER=records: expected auto, walk, block, rec or rec_es" in _lib.last_error()
+
+
 def test_product_never_imports_oracle():
     """The product path must not reach into the oracle (or any CPU fallback)."""
     pkg = os.path.join(ROOT, "pfb-imaging_amd")
