@@ -210,7 +210,8 @@ def w_range(uvw, freq, mask, flip_w):
 
 
 def choose_params(uvw, freq, mask, nx, ny, px, py, center_x, center_y, epsilon, do_wgridding, flip_u=False,
-                  flip_v=False, flip_w=False, sigma_min=1.1, sigma_max=2.6, force=None, force_wmode=None):
+                  flip_v=False, flip_w=False, sigma_min=1.1, sigma_max=2.6, force=None, force_wmode=None,
+                  divide_by_n=False):
     """Pick (sigma, W, beta), grid size and w-plane layout.
 
     ``force=(sigma, W)`` pins the kernel row (tests use it to mirror the product's
@@ -224,9 +225,12 @@ def choose_params(uvw, freq, mask, nx, ny, px, py, center_x, center_y, epsilon, 
     tmax = max(abs(nm1max + nshift), abs(nm1min + nshift))
     wlo, whi = w_range(uvw, freq, mask, flip_w) if do_wgridding else (0.0, 0.0)
     nvis = uvw.shape[0] * freq.size
-    # (admissibility on the worst-sub-cell-position error with the product's margins, see choose_kernel in csrc/gridder.hip)
-    eps_w = epsilon / 3.0
-    eps1 = 0.8 / 1.25 * epsilon / (3.0 if do_wgridding else 2.0)
+    # (admissibility on the worst-sub-cell-position error with the product's margins, see choose_kernel in csrc/gridder.hip;
+    # divide_by_n weights a pixel's error with 1 / n: both shares shrink by the smallest n of the image)
+    nscale = min(1.0, max(0.25, 1.0 + nm1min)) if divide_by_n else 1.0
+    eps_w = epsilon / 3.0 * nscale
+    eps1 = 0.8 / 1.25 * epsilon / (3.0 if do_wgridding else 2.0) * (nscale if do_wgridding else 1.0)
+    wd_K = None  # wmode 2: K admitted by the measured interpolation error (row independent, found on first use)
     best = None
     for r in kernel_table():
         if force is not None:
@@ -259,11 +263,18 @@ def choose_params(uvw, freq, mask, nx, ny, px, py, center_x, center_y, epsilon, 
                         continue
                     touched = npl
                     if wmode == 2:
-                        # one plane with K = npl kernel functions per axis: phase centre on axis only (t a function of
-                        # l^2 + m^2), 2 <= K <= 4, and the aliases of the differentiated kernels -- amplified by
-                        # ((1 + 2 sigma) l_max)^(2k) against l_max^(2k) -- still inside the row's share
-                        if lshift != 0.0 or mshift != 0.0 or not 2 <= npl <= WD_MAX_K:
+                        # one plane with K kernel functions per axis: phase centre on axis only (t a function of
+                        # l^2 + m^2), the image inside the horizon, the smallest K in [npl, 4] whose measured
+                        # interpolation error in s passes 2 eps_w (wd_choose_K), and the aliases of the differentiated
+                        # kernels -- amplified by ((1 + 2 sigma) l_max)^(2k) against l_max^(2k) -- still inside the
+                        # row's share
+                        if lshift != 0.0 or mshift != 0.0 or npl < 2:
                             continue
+                        if wd_K is None:
+                            wd_K = wd_choose_K(npl, wd_smax(nx, ny, px, py), 0.5 * (whi - wlo), nshift, 2.0 * eps_w) or 0
+                        if wd_K == 0:
+                            continue
+                        npl = touched = wd_K
                         if force is None and r.get("eps_sup", r["eps_max"]) * wd_alias_amplification(omega, npl, nu / nx, nv / ny) > eps1:
                             continue
                         nder, npl = npl, 1
@@ -299,6 +310,37 @@ def wd_alias_amplification(omega, K, sig_u, sig_v):
 def wd_smax(nx, ny, px, py):
     """Largest l^2 + m^2 over the pixel lattice of an on-axis image (pixel i sits at (i - n // 2) pixsize)."""
     return ((nx // 2) * px) ** 2 + ((ny // 2) * py) ** 2
+
+
+def wd_interp_error(K, smax, whalf, nshift):
+    """wmode 2: worst error of the K-node interpolation in s of exp(-2 pi i dw (t(s) + nshift)), t(s) = sqrt(1 - s) - 1,
+    over a dense grid of |dw| <= whalf and 0 <= s <= smax (the same samples as wd_interp_error in csrc/gridder.hip).  inf
+    when the image reaches the horizon (smax >= 1) or a sample is not finite."""
+    if not (0.0 <= smax < 1.0):
+        return np.inf
+    xq = wd_nodes(K, 1.0)
+    sq = xq * smax
+    tq = -sq / (1.0 + np.sqrt(1.0 - sq)) + nshift
+    M = wd_matrix(K)
+    dwv = whalf * (np.arange(WD_ERR_NW + 1) / (0.5 * WD_ERR_NW) - 1.0)
+    x = np.arange(WD_ERR_NS + 1) / WD_ERR_NS
+    sv = x * smax
+    tt = -sv / (1.0 + np.sqrt(1.0 - sv)) + nshift
+    coef = np.exp(-2j * np.pi * dwv[:, None] * tq[None, :]) @ M.T          # (dw, k)
+    approx = coef @ (x[None, :] ** np.arange(K)[:, None])                 # (dw, s)
+    err = np.abs(approx - np.exp(-2j * np.pi * dwv[:, None] * tt[None, :]))
+    return float(err.max()) if np.all(np.isfinite(err)) else np.inf
+
+
+def wd_choose_K(K0, smax, whalf, nshift, bound):
+    """Smallest K in [K0, WD_MAX_K] whose measured interpolation error is <= bound (None if there is none)."""
+    for K in range(K0, WD_MAX_K + 1):
+        if wd_interp_error(K, smax, whalf, nshift) <= bound:
+            return K
+    return None
+
+
+WD_ERR_NW, WD_ERR_NS = 16, 128  # samples of the interpolation check: 2 WD_ERR_NW / 2 + 1 in dw, WD_ERR_NS + 1 in s
 
 
 def wd_nodes(K, smax):
@@ -369,7 +411,7 @@ class Plan:
         if params is None:
             params = choose_params(self.uvw, self.freq, self.mask, self.nx, self.ny, self.px, self.py, center_x,
                                    center_y, epsilon, self.do_w, flip_u, flip_v, flip_w, sigma_min, sigma_max, force,
-                                   force_wmode)
+                                   force_wmode, self.divide_by_n)
         elif isinstance(params, dict):
             params = GridParams(**params)
         self.p = p = params

@@ -1151,6 +1151,85 @@ static int poly_planes_needed(double omega, double eps)
     return k;
 }
 
+// One-plane w-scheme (wmode 2): t_q = n(s_q) - 1 + nshift at the K Chebyshev nodes s_q of [0, smax], and M[k][q], the
+// coefficient of (s / smax)^k in the Lagrange basis polynomial of node q.
+static void wd_interp_nodes(int K, double smax, double nshift, double *tq, double (*M)[WD_MAX_K])
+{
+    double xq[WD_MAX_K];
+    for (int q = 0; q < K; ++q) {
+        xq[q] = 0.5 * (1.0 - std::cos(pi_const * (2.0 * double(q) + 1.0) / (2.0 * double(K))));  // nodes on [0, 1]
+        const double sq = xq[q] * smax;
+        tq[q] = -sq / (1.0 + std::sqrt(1.0 - sq)) + nshift;
+    }
+    for (int q = 0; q < K; ++q) {  // monomial coefficients of the Lagrange basis polynomial of node q
+        long double c[WD_MAX_K + 1] = {1.0L, 0, 0, 0, 0};
+        int deg = 0;
+        long double den = 1.0L;
+        for (int m2 = 0; m2 < K; ++m2) {
+            if (m2 == q) continue;
+            for (int d = deg + 1; d >= 1; --d) c[d] = c[d - 1] - (long double)xq[m2] * c[d];
+            c[0] = -(long double)xq[m2] * c[0];
+            ++deg;
+            den *= (long double)xq[q] - (long double)xq[m2];
+        }
+        for (int k = 0; k < K; ++k) M[k][q] = double(c[k] / den);
+    }
+}
+
+// Worst error of the one-plane scheme's interpolation in s = l^2 + m^2 of exp(-2 pi i dw (t(s) + nshift)), t(s) = sqrt(1 - s) - 1,
+// K nodes, over WD_ERR_NW + 1 values of dw in [-whalf, whalf] and WD_ERR_NS + 1 values of s in [0, smax].  Measured, not
+// bounded: poly_planes_needed bounds the interpolation in a variable linear in t, and t(s) is curved -- the curvature term grows
+// like omega smax^K, not (omega smax)^K, and dominates for a wide field with a small w range.  Infinite once the image reaches
+// the horizon (smax >= 1: the nodes past s = 1 have no real n) or a sample is not finite, so a test `!(err <= bound)` rejects.
+// (oracle/wgridder.py: wd_interp_error takes the same samples)
+constexpr int WD_ERR_NW = 16, WD_ERR_NS = 128;
+static double wd_interp_error(int K, double smax, double whalf, double nshift)
+{
+    if (!(smax >= 0.0 && smax < 1.0)) return HUGE_VAL;
+    double tq[WD_MAX_K], M[WD_MAX_K][WD_MAX_K];
+    wd_interp_nodes(K, smax, nshift, tq, M);
+    double worst = 0.0;
+    for (int iw = 0; iw <= WD_ERR_NW; ++iw) {
+        const double dwv = whalf * (double(iw) / (0.5 * WD_ERR_NW) - 1.0);
+        double cr[WD_MAX_K], ci[WD_MAX_K];
+        for (int k = 0; k < K; ++k) {
+            cr[k] = ci[k] = 0.0;
+            for (int q = 0; q < K; ++q) {
+                cr[k] += M[k][q] * std::cos(2.0 * pi_const * dwv * tq[q]);
+                ci[k] -= M[k][q] * std::sin(2.0 * pi_const * dwv * tq[q]);
+            }
+        }
+        for (int is = 0; is <= WD_ERR_NS; ++is) {
+            const double x = double(is) / double(WD_ERR_NS), sv = x * smax;
+            const double tt = -sv / (1.0 + std::sqrt(1.0 - sv)) + nshift;
+            double ar = 0.0, ai = 0.0, xp = 1.0;
+            for (int k = 0; k < K; ++k) {
+                ar += cr[k] * xp;
+                ai += ci[k] * xp;
+                xp *= x;
+            }
+            const double e = std::hypot(ar - std::cos(2.0 * pi_const * dwv * tt), ai + std::sin(2.0 * pi_const * dwv * tt));
+            if (!std::isfinite(e)) return HUGE_VAL;
+            worst = std::max(worst, e);
+        }
+    }
+    return worst;
+}
+
+// largest l^2 + m^2 of the pixel lattice of an on-axis image (pixel 0 sits at -(n / 2) pixsize)
+static double wd_smax(const pfbhip_gridder_params &p)
+{
+    const double xe = double(p.nx / 2) * p.pixsize_x, ye = double(p.ny / 2) * p.pixsize_y;
+    return xe * xe + ye * ye;
+}
+
+// The share of epsilon the w-interpolation of the polynomial and one-plane schemes may take: 2 eps_w, eps_w = epsilon / 3, times
+// the smallest n of the image (>= 0.25) with divide_by_n, which weights a pixel's error with 1 / n
+static double w_interp_budget(const pfbhip_gridder_params &p, double nmin)
+{
+    return 2.0 * p.epsilon / 3.0 * (p.divide_by_n ? std::max(0.25, std::min(1.0, nmin)) : 1.0);
+}
+
 // The switches that override the plan's choices.  Read once at the start of every plan creation,
 // never cached for the process: the tests set them between plans to keep the alternative kernels covered.
 enum class ScatterForce { Auto, Walk, Block, Rec, RecEs };  // PFBHIP_SCATTER=auto / walk / block / rec / rec_es
@@ -1225,7 +1304,7 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
     const double eps1 = 0.8 / 1.25 * prm.epsilon / (prm.do_wgridding ? 3.0 : 2.0) *
                         ((prm.do_wgridding && prm.divide_by_n) ? std::max(0.25, std::min(1.0, nmin)) : 1.0);
     // (the interpolation bound of the polynomial w-planes is a true maximum already: it keeps its 2/3 epsilon)
-    const double eps_w = prm.epsilon / 3.0 * (prm.divide_by_n ? std::max(0.25, std::min(1.0, nmin)) : 1.0);
+    const double eps_w = 0.5 * w_interp_budget(prm, nmin);
     const double nvis = double(g->nvis);
     const bool wgrid = prm.do_wgridding && tmax > 0.0;
     const double pi = 3.14159265358979323846;
@@ -1237,6 +1316,18 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
     // one-plane scheme (wmode 2): phase centre on axis, the record kernels available, not switched off
     const bool wd_allowed = sw.wmode2 && g->info.lshift == 0.0 && g->info.mshift == 0.0 &&
                             (sw.scatter == ScatterForce::Auto || sw.scatter == ScatterForce::Rec);
+    // its K depends on the geometry alone: the smallest K from the estimate of the polynomial scheme (at least 2) up to
+    // WD_MAX_K whose measured interpolation error in s passes 2 eps_w.  0: none does, or the image reaches the horizon
+    const double wd_omega = 2.0 * pi * 0.5 * (whi - wlo) * tmax;
+    int wd_K = 0;
+    if (wgrid && wd_allowed) {
+        const int K0 = poly_planes_needed(wd_omega, 2.0 * eps_w);
+        for (int K = K0; K >= 2 && K <= WD_MAX_K; ++K)
+            if (wd_interp_error(K, wd_smax(prm), 0.5 * (whi - wlo), g->info.nshift) <= 2.0 * eps_w) {  // (NaN: not admitted)
+                wd_K = K;
+                break;
+            }
+    }
     for (size_t i = 0; i < nrows; ++i) {
         const KernelRow &r = tab[i];
         if (prm.force_W > 0) {
@@ -1284,14 +1375,13 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
                 int nder = 0;
                 if (wgrid) {
                     if (mode == 2) {
-                        // ONE plane, K kernel functions per axis (gridder_kernels_wd.hpp): the K of the polynomial scheme --
-                        // the same interpolation bound, in s = l^2 + m^2 instead of w -- while 2 <= K <= 4; the aliases of
-                        // the k-th derivative term carry ((1 + 2 sigma) l_max)^(2k) where the wanted term has <= l_max^(2k)
-                        // at weight omega^k / k!: the row's worst-position error times that sum must still pass
-                        if (!wd_allowed) continue;
-                        const double omega = 2.0 * pi * 0.5 * (whi - wlo) * tmax;
-                        const int K = poly_planes_needed(omega, 2.0 * eps_w);
-                        if (K < 2 || K > WD_MAX_K) continue;
+                        // ONE plane, K kernel functions per axis (gridder_kernels_wd.hpp): K = wd_K, the interpolation in
+                        // s = l^2 + m^2 measured above; the aliases of the k-th derivative term carry ((1 + 2 sigma) l_max)^(2k)
+                        // where the wanted term has <= l_max^(2k) at weight omega^k / k!: the row's worst-position error times
+                        // that sum must still pass
+                        if (wd_K == 0) continue;
+                        const double omega = wd_omega;
+                        const int K = wd_K;
                         const double gg = std::pow(std::max(1.0 + 2.0 * double(nu) / double(prm.nx), 1.0 + 2.0 * double(nv) / double(prm.ny)), 2);
                         double amp = 0.0, term = 1.0;
                         for (int k = 0; k < K; ++k) {
@@ -1357,8 +1447,9 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
         }
     }
     PFB_REQUIRE(best != nullptr || !(wgrid && prm.force_wmode == 3),
-                "force_wmode=2: the one-plane w-scheme needs the phase centre on axis and 2..%d kernel functions for this field "
-                "of view and w range (epsilon=%g); leave the scheme to the plan", WD_MAX_K, prm.epsilon);
+                "force_wmode=2: the one-plane w-scheme needs the phase centre on axis, a field of view inside the horizon "
+                "(max l^2 + m^2 = %g, must be < 1) and 2..%d kernel functions for this field of view and w range (epsilon=%g); "
+                "leave the scheme to the plan", wd_smax(prm), WD_MAX_K, prm.epsilon);
     PFB_REQUIRE(best != nullptr || !(wgrid && prm.force_wmode == 2),  // (C-ABI encoding: 0 = plan decides, wmode + 1 otherwise)
                 "force_wmode=1: the polynomial w-plane scheme needs more than %d planes for this field of view and w range "
                 "(epsilon=%g); leave the scheme to the plan", MAX_POLY_PLANES, prm.epsilon);
@@ -1789,56 +1880,23 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             g->d_dtab.alloc(dtab.size());
             PFB_HIP(hipMemcpyAsync(g->d_dtab.p, dtab.data(), dtab.size() * sizeof(double), hipMemcpyHostToDevice, st));
             wa.dtab = g->d_dtab.p;
-            const double xe = double(prm.nx / 2) * prm.pixsize_x, ye = double(prm.ny / 2) * prm.pixsize_y;
-            const double smax = xe * xe + ye * ye;  // largest l^2 + m^2 of the pixel lattice (pixel 0 sits at -(n / 2) pixsize)
+            const double smax = wd_smax(prm);
             info.smax = smax;
             const double au = std::pow(double(info.nu) * prm.pixsize_x / (pi_const * double(W)), 2) / smax;
             const double av = std::pow(double(info.nv) * prm.pixsize_y / (pi_const * double(W)), 2) / smax;
-            double xq[WD_MAX_K];
             for (int q = 0; q < K; ++q) {
-                xq[q] = 0.5 * (1.0 - std::cos(pi_const * (2.0 * double(q) + 1.0) / (2.0 * double(K))));  // nodes on [0, 1]
-                const double sq = xq[q] * smax;
-                wa.tq[q] = -sq / (1.0 + std::sqrt(1.0 - sq)) + info.nshift;
                 wa.su[q] = std::pow(-au, q);
                 wa.sv[q] = std::pow(-av, q);
             }
-            for (int q = 0; q < K; ++q) {  // monomial coefficients of the Lagrange basis polynomial of node q
-                long double c[WD_MAX_K + 1] = {1.0L, 0, 0, 0, 0};
-                int deg = 0;
-                long double den = 1.0L;
-                for (int m2 = 0; m2 < K; ++m2) {
-                    if (m2 == q) continue;
-                    for (int d = deg + 1; d >= 1; --d) c[d] = c[d - 1] - (long double)xq[m2] * c[d];
-                    c[0] = -(long double)xq[m2] * c[0];
-                    ++deg;
-                    den *= (long double)xq[q] - (long double)xq[m2];
-                }
-                for (int k = 0; k < K; ++k) wa.M[k][q] = double(c[k] / den);
-            }
+            wd_interp_nodes(K, smax, info.nshift, wa.tq, wa.M);
             g->d_cw.alloc((size_t(info.nactive) + REC_PAD) * size_t(K));
             wa.cw = g->d_cw.p;
             wd_launch_coeffs(wa, info.nactive, g->d_pw.p, g->d_cw.p, st);
-            // check the interpolation in s on a dense grid of (dw, s) against the closed form (what the plan promised: 2 eps_w)
-            double worst = 0.0;
-            for (int iw = 0; iw <= 8; ++iw)
-                for (int is = 0; is <= 64; ++is) {
-                    const double dwv = info.whalf * (double(iw) / 4.0 - 1.0), x = double(is) / 64.0, sv_ = x * smax;
-                    const double tt = -sv_ / (1.0 + std::sqrt(1.0 - sv_)) + info.nshift;
-                    double ar = 0.0, ai = 0.0, xp = 1.0;
-                    for (int k = 0; k < K; ++k) {
-                        double cr = 0.0, ci = 0.0;
-                        for (int q = 0; q < K; ++q) {
-                            cr += wa.M[k][q] * std::cos(2.0 * pi_const * dwv * wa.tq[q]);
-                            ci -= wa.M[k][q] * std::sin(2.0 * pi_const * dwv * wa.tq[q]);
-                        }
-                        ar += cr * xp;
-                        ai += ci * xp;
-                        xp *= x;
-                    }
-                    worst = std::max(worst, std::hypot(ar - std::cos(2.0 * pi_const * dwv * tt), ai + std::sin(2.0 * pi_const * dwv * tt)));
-                }
+            // the interpolation in s on a dense grid of (dw, s) against the closed form: what choose_kernel admitted the plan on
+            const double worst = wd_interp_error(K, smax, info.whalf, info.nshift), bound = w_interp_budget(prm, 1.0 + nm1min);
             if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] one-plane w-scheme: K = %d, interpolation error %.3g\n", K, worst);
-            PFB_REQUIRE(worst <= prm.epsilon, "one-plane w-scheme: interpolation error %g exceeds epsilon %g", worst, prm.epsilon);
+            PFB_REQUIRE(worst <= bound, "one-plane w-scheme: interpolation error %g exceeds its share %g of epsilon %g", worst, bound,
+                        prm.epsilon);
         }
         PFB_HIP(hipStreamSynchronize(st));
     }

@@ -80,6 +80,130 @@ def test_mode_choice_and_exact_kernel_option():
     assert rel(q.vis2dirty(wide["vis"], wide["wgt"]), q2.vis2dirty(wide["vis"], wide["wgt"])) < 1e-9
 
 
+# ---- wide, near-coplanar fields (shared with tests/test_gpu_wide_field.py) ----------------------------------------------------
+
+
+def compact_case(nx, ny, half, dw, eps, w0=0.0, center=(0.0, 0.0), divide_by_n=False, nrow=600, seed=0):
+    """A compact array observed at one channel of 100 MHz: uv uniform with max |u| cell ~ 0.4, |w| uniform over
+    [w0, w0 + dw] wavelengths (random signs: the Hermitian fold runs), 5 % of the rows masked.  The image is nx x ny with the
+    larger axis reaching `half` off its centre (pixel i at (i - n // 2) cell).  Returns the data, the geometry keywords of
+    owg.Plan / Gridder (flip_v=True) and the largest l^2 + m^2 of an on-axis image (smax)."""
+    rng = np.random.default_rng(seed)
+    cell = half / (max(nx, ny) // 2)
+    lam = owg.SPEED_OF_LIGHT / 1e8
+    uv = rng.uniform(-0.4 / cell, 0.4 / cell, (nrow, 2))
+    w = (w0 + dw * rng.random(nrow)) * rng.choice([-1.0, 1.0], nrow)
+    kw = dict(npix_x=nx, npix_y=ny, pixsize_x=cell, pixsize_y=cell, center_x=center[0], center_y=center[1], epsilon=eps,
+              flip_u=False, flip_v=True, flip_w=False, do_wgridding=True, divide_by_n=divide_by_n)
+    if divide_by_n:  # n = 0 (the horizon) gives inf on both sides: keep every pixel well off it
+        ls, ms = center[0], -center[1]
+        r2 = ((ls + (np.arange(nx) - nx // 2) * cell)[:, None] ** 2 + (ms + (np.arange(ny) - ny // 2) * cell)[None, :] ** 2)
+        assert np.abs(1.0 - r2).min() > 1e-6, "divide_by_n geometry with a pixel on the horizon"
+    return dict(uvw=np.column_stack([uv, w]) * lam, freq=np.array([1e8]), vis=(rng.standard_normal((nrow, 1)) +
+                1j * rng.standard_normal((nrow, 1))), wgt=np.exp(rng.standard_normal((nrow, 1))),
+                mask=(rng.random((nrow, 1)) > 0.05).astype(np.uint8), x=rng.standard_normal((nx, ny)), kw=kw,
+                smax=owg.wd_smax(nx, ny, cell, cell))
+
+
+# (nx, ny, half-field, w spread dw, w0, epsilon, centre, divide_by_n).  Half-fields 0.8 and 0.9 (and 0.75 at the corners) reach
+# past the horizon; the first five rows were wrong under the one-plane admission by the linear-phase bound alone (NaN images:
+# nodes past s = 1; 1.2-8 epsilon: the curvature of n(s) for a small w spread); the last two put the image corner at
+# l^2 + m^2 = 0.49 and 0.51, either side of the fitted n - 1 screen's gate (rowfft.hip: fused_geom_fit).
+WIDE_FIELD_CASES = [
+    (64, 64, 0.8, 3e-3, 0.0, 1e-3, (0.0, 0.0), False),
+    (64, 64, 0.9, 0.03, 0.0, 1e-3, (0.0, 0.0), False),
+    (64, 64, 0.5, 1e-4, 0.0, 1e-7, (0.0, 0.0), False),
+    (48, 48, 0.2, 0.3, 0.0, 1e-9, (0.0, 0.0), False),
+    (64, 64, 0.6, 0.36, 0.0, 1e-4, (0.0, 0.0), False),
+    (64, 64, 0.75, 30.0, 0.0, 1e-5, (0.0, 0.0), False),
+    (64, 64, 0.9, 3.0, 0.0, 1e-7, (0.0, 0.0), True),
+    (50, 41, 0.3, 10.0, 0.0, 1e-6, (0.3, -0.4), False),
+    (64, 64, 0.05, 0.5, 0.0, 1e-7, (0.0, 0.0), False),
+    (63, 63, 0.05, 0.0, 0.0, 1e-5, (0.0, 0.0), False),
+    (64, 48, 0.2, 0.0, 5.0, 1e-6, (0.0, 0.0), False),
+    (64, 64, 0.35, 1.0, 0.0, 1e-7, (0.0, 0.0), False),
+    (64, 64, 0.35, 0.05, 0.0, 1e-9, (0.0, 0.0), False),
+    (48, 64, 0.5, 2.0, 0.0, 1e-5, (0.0, 0.0), True),
+    (64, 64, 0.69, 0.1, 0.0, 1e-6, (0.0, 0.0), True),
+    (64, 64, 0.69, 1.0, 0.0, 1e-3, (0.0, 0.0), False),
+    (64, 64, 0.75, 0.01, 0.0, 1e-7, (0.0, 0.0), False),
+    (64, 64, 0.8, 30.0, 0.0, 1e-4, (0.0, 0.0), False),
+    (65, 65, 0.9, 0.3, 0.0, 1e-5, (0.0, 0.0), False),
+    (64, 64, 0.2, 5.0, 0.0, 1e-6, (0.2, 0.1), False),
+    (64, 64, 0.35, 0.3, 0.0, 1e-4, (0.2, 0.1), True),
+    (64, 64, 0.5, 0.0, 0.0, 1e-7, (0.0, 0.0), False),
+    (64, 64, 0.5, 0.0, 2.0, 1e-7, (0.0, 0.0), False),
+    (64, 64, 0.5, 0.02, 0.0, 1e-9, (0.0, 0.0), True),
+    (64, 64, float(np.sqrt(0.245)), 0.5, 3.0, 1e-7, (0.0, 0.0), False),
+    (64, 64, float(np.sqrt(0.255)), 0.5, 3.0, 1e-7, (0.0, 0.0), False),
+]
+
+
+def wide_field_id(g):
+    nx, ny, half, dw, w0, eps, center, divn = g
+    return (f"{nx}x{ny}-h{half:.3g}-dw{dw:g}" + (f"-w0{w0:g}" if w0 else "") + f"-eps{eps:g}" +
+            (f"-c{center[0]:g},{center[1]:g}" if center != (0.0, 0.0) else "") + ("-divn" if divn else ""))
+
+
+def wide_field_refs(c):
+    """DFT dirty image (weighted, masked) and masked visibilities of c["x"]."""
+    k = c["kw"]
+    geo = (k["pixsize_x"], k["pixsize_y"], k["center_x"], k["center_y"], k["flip_u"], k["flip_v"], k["flip_w"], True,
+           k["divide_by_n"])
+    ref = dft.dft_vis2dirty(c["uvw"], c["freq"], c["vis"], c["wgt"], c["mask"], k["npix_x"], k["npix_y"], *geo)
+    refv = dft.dft_dirty2vis(c["uvw"], c["freq"], c["x"], *geo)
+    refv[c["mask"] == 0] = 0
+    return ref, refv
+
+
+@pytest.mark.parametrize("geom", WIDE_FIELD_CASES, ids=wide_field_id)
+def test_wide_field_schemes_vs_dft(geom):
+    """The automatic choice and every w-scheme the plan admits meet epsilon against the DFT at wide, near-coplanar fields (up to
+    and past the horizon); the one-plane scheme is refused -- ValueError, never a NaN image -- where its interpolation in
+    s = l^2 + m^2 cannot reach its share of epsilon or the image reaches the horizon."""
+    nx, ny, half, dw, w0, eps, center, divn = geom
+    c = compact_case(nx, ny, half, dw, eps, w0=w0, center=center, divide_by_n=divn)
+    k = c["kw"]
+    ref, refv = wide_field_refs(c)
+    admitted = {}
+    for fw in (None, 0, 1, 2):
+        try:
+            plan = owg.Plan(c["uvw"], c["freq"], c["mask"], k["npix_x"], k["npix_y"], k["pixsize_x"], k["pixsize_y"],
+                            k["center_x"], k["center_y"], eps, k["flip_u"], k["flip_v"], k["flip_w"], True, divn,
+                            force_wmode=fw)
+        except ValueError:
+            assert fw is not None, "the automatic choice must always find a scheme"
+            continue
+        admitted[fw] = plan.p.wmode
+        d = plan.vis2dirty(c["vis"], c["wgt"])
+        v = plan.dirty2vis(c["x"])
+        assert np.isfinite(d).all() and np.isfinite(v).all(), (fw, plan.p)
+        assert rel(d, ref) <= eps, (fw, plan.p, rel(d, ref) / eps)
+        assert rel(v, refv) <= eps, (fw, plan.p, rel(v, refv) / eps)
+        if plan.p.wmode == 2:
+            assert c["smax"] < 1.0 and center == (0.0, 0.0)
+            K = plan.p.nderiv
+            assert owg.wd_interp_error(K, c["smax"], plan.p.whalf, plan.p.nshift) <= 2.0 / 3.0 * eps
+    assert admitted[0] == 0 and admitted[None] in (0, 1, 2)
+    if c["smax"] >= 1.0 or center != (0.0, 0.0) or dw == 0.0:
+        assert 2 not in admitted, "the one-plane scheme admitted past the horizon, off axis or without a w spread"
+
+
+def test_wide_field_one_plane_interp_error():
+    """The measured interpolation error of the one-plane scheme: infinite (inadmissible) at and past the horizon, and for a
+    wide field with a small w spread far above the linear-phase bound poly_planes_needed sized K by."""
+    assert owg.wd_interp_error(2, 1.0, 0.01, 0.0) == np.inf and owg.wd_interp_error(4, 1.28, 0.01, 0.0) == np.inf
+    assert owg.wd_choose_K(2, 1.28, 1e-3, 0.0, 1.0) is None
+    # 64^2, half-field 0.5 (smax 0.5), w spread 1e-4: omega = 2 pi 0.5e-4 tmax ~ 9e-5 -> K = 2 by the bound (~2e-9 < 6.7e-8)
+    lo, hi = owg.nm1_range(64, 64, 0.5 / 32, 0.5 / 32, 0.0, 0.0)
+    nshift = -0.5 * (lo + hi)
+    omega = 2.0 * np.pi * 0.5e-4 * max(abs(lo + nshift), abs(hi + nshift))
+    assert owg.cheb_planes_needed(omega, 2e-7 / 3.0) == 2
+    e2 = owg.wd_interp_error(2, owg.wd_smax(64, 64, 0.5 / 32, 0.5 / 32), 0.5e-4, nshift)
+    assert e2 > 10 * omega ** 2 / 4.0 and e2 > 2e-7 / 3.0
+    assert owg.wd_choose_K(2, owg.wd_smax(64, 64, 0.5 / 32, 0.5 / 32), 0.5e-4, nshift, 2e-7 / 3.0) in (3, 4)
+
+
 def test_adjointness_linearity_no_wgridding():
     c = _case()
     p = owg.Plan(c["uvw"], c["freq"], c["mask"], 48, 48, c["cell"], c["cell"], 0.0, 0.0, 1e-7, False, True, False,
