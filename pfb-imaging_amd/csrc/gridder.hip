@@ -540,7 +540,7 @@ struct pfbhip_gridder {
     // scratch
     DevBuf<double2> d_grid, d_sval, d_sacc, d_vis;
     // Hessian applies clear the scatter's planes on a side stream while the degrid half runs: a second plane buffer
-    // (d_grid2) is zeroed there, the scatter waits for it (single-pass plans only; PFBHIP_ASYNC_CLEAR=0 disables)
+    // (d_grid2) is zeroed there, the scatter waits for it (single-pass plans only)
     DevBuf<double2> d_grid2;
     // The second buffer only ever holds what the scatter flushed into it: the (TILE + W - 1)^2 regions of the tiles that have
     // work.  Clearing those -- per tile row the runs of touched tile columns, 8-row slices -- instead of every occupied row
@@ -559,9 +559,9 @@ struct pfbhip_gridder {
     DevBuf<uint8_t> d_occ;    // occupancy of 32-row blocks of the uv-plane
     // first-axis row FFTs with the crop / pad + transpose folded in (rowfft_a2b / rowfft_b2a): row of every workgroup,
     // ordered so that the 8 rows of a 128-byte line of B run on one XCD at about the same time (PFBHIP_TFFT=0: the
-    // separate k_a2b / k_b2a passes; =2: rows in natural order)
+    // separate k_a2b / k_b2a passes)
     DevBuf<int> d_rowmap;
-    int tfft = 0;
+    bool tfft = false;
     bool weights_bound = false;
     struct RowSpan {
         int64_t row0, nrows;                      // occupied rows [row0, row0 + nrows) of A
@@ -1238,16 +1238,11 @@ struct PlanSwitches {
     bool wmode2 = true;       // PFBHIP_WMODE2=0: keep the multi-plane w-schemes
     bool wd_block4 = false;   // PFBHIP_WD_BLOCK=4: 4 x 4-cell anchoring at W = 14, 15
     int wd_colours = -1;      // PFBHIP_WD_COLOURS: -1 plan decides, 0 one launch (atomic flush), 1 four colour launches
-    uint32_t chunk = 0;       // PFBHIP_CHUNK (256..CHUNK; 0: plan decides)
-    uint32_t wd_chunk = 0;    // PFBHIP_WD_CHUNK (64..CHUNK; 0: plan decides)
     bool rowfft = true;       // PFBHIP_ROWFFT=0: rocFFT row plans
     bool fused_fft = true;    // PFBHIP_FUSED_FFT=0: unfused second axis
     int fused_doubled = -1;   // PFBHIP_FUSED_DOUBLED: -1 plan decides, 0 / 1 forced
     bool sepscreen = true;    // PFBHIP_SEPSCREEN=0: no separable w-screen form
-    int tpad = 40;            // PFBHIP_TPAD
-    int tfft = 1;             // PFBHIP_TFFT
-    bool colruns = true;      // PFBHIP_COLRUNS=0: whole rows in the first-axis transforms
-    bool async_clear = true;  // PFBHIP_ASYNC_CLEAR=0: in-stream plane clear
+    bool tfft = true;         // PFBHIP_TFFT=0: plain first-axis row FFT + separate transpose kernels
 };
 
 static PlanSwitches read_plan_switches()
@@ -1270,17 +1265,12 @@ static PlanSwitches read_plan_switches()
     sw.wd_block4 = first("PFBHIP_WD_BLOCK") == '4';
     const int wc = first("PFBHIP_WD_COLOURS");
     sw.wd_colours = wc == '0' ? 0 : (wc == '1' ? 1 : -1);
-    if (const char *e = std::getenv("PFBHIP_CHUNK")) sw.chunk = uint32_t(std::max(256, std::min(int(CHUNK), std::atoi(e))));
-    if (const char *e = std::getenv("PFBHIP_WD_CHUNK")) sw.wd_chunk = uint32_t(std::max(64, std::min(int(CHUNK), std::atoi(e))));
     sw.rowfft = first("PFBHIP_ROWFFT") != '0';
     sw.fused_fft = first("PFBHIP_FUSED_FFT") != '0';
     const int fd = first("PFBHIP_FUSED_DOUBLED");
     sw.fused_doubled = fd < 0 ? -1 : (fd == '1' ? 1 : 0);
     sw.sepscreen = first("PFBHIP_SEPSCREEN") != '0';
-    if (const char *e = std::getenv("PFBHIP_TPAD")) sw.tpad = std::atoi(e);
-    if (const char *e = std::getenv("PFBHIP_TFFT")) sw.tfft = std::atoi(e);
-    sw.colruns = first("PFBHIP_COLRUNS") != '0';
-    sw.async_clear = first("PFBHIP_ASYNC_CLEAR") != '0';
+    sw.tfft = first("PFBHIP_TFFT") != '0';
     return sw;
 }
 
@@ -1671,14 +1661,13 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         info.nactive = tstart[size_t(nkeys)];
         lap("tile starts");
         const int64_t P = m.key_planes;
-        // visibilities per work item (PFBHIP_CHUNK, 256..4096): smaller items balance the launch tail, larger ones amortise
-        // the per-item prologue / tile flush
+        // visibilities per work item (<= CHUNK): smaller items balance the launch tail, larger ones amortise the per-item
+        // prologue / tile flush
         uint32_t chunk = CHUNK;
         if (info.wmode == 2) {  // the one-plane gather (256-thread workgroups, 768 slots): about three items per slot, 512..4096 each
             chunk = 512;
             while (chunk < CHUNK && double(chunk) * 1.5 < double(info.nactive) / (3.0 * 768.0)) chunk *= 2;
         }
-        if (sw.chunk != 0) chunk = sw.chunk;
         chunk_used = chunk;
         for (int64_t grp = 0; grp < (plane_sorted ? ngroups : 1); ++grp) {
             // planes [q, q + kp) are touched by visibilities whose first plane lies in [q - W + 1, q + kp - 1]
@@ -1739,13 +1728,12 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         // The one-plane scatter runs 256-thread workgroups: an item of 4096 visibilities is 1024 per wave, longer than a whole
         // colour launch of a mid-size plan should take (4096^2, 4e6 visibilities: grid 1.61 ms -> 1.02 with items of <= 1024; C2
         // indifferent between 1024 and 4096).  Its lists are cut finer than the gather's: about three items per workgroup
-        // slot and launch, 512..2048 visibilities each (PFBHIP_WD_CHUNK pins it).
+        // slot and launch, 512..2048 visibilities each.
         uint32_t schunk = chunk_used;
         if (info.wmode == 2) {
             const double per_launch = double(info.nactive) / (g->coloured ? 4.0 : 1.0);
             uint32_t c = 512;
             while (c < 2048 && double(c) * 1.5 < per_launch / (3.0 * 768.0)) c *= 2;
-            if (sw.wd_chunk != 0) c = sw.wd_chunk;
             schunk = std::min(c, chunk_used);
         }
         std::vector<WorkItem> wcol;
@@ -1938,7 +1926,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     g->grid_cur = g->d_grid.p;
     {
         // one pass over the planes (otherwise the buffer is reused inside the apply) and a second buffer of <= 40 GB
-        g->async_clear = sw.async_clear && info.nplanes <= g->kp_max && info.nactive > 0 && g->d_grid.bytes() <= (size_t(40) << 30);
+        g->async_clear = info.nplanes <= g->kp_max && info.nactive > 0 && g->d_grid.bytes() <= (size_t(40) << 30);
         if (g->async_clear) {
             g->d_grid2.alloc(g->plane_stride * size_t(g->kp_max));
             PFB_HIP(hipStreamCreateWithFlags(&g->clear_stream, hipStreamNonBlocking));
@@ -2041,10 +2029,11 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // Degridding side of the transposing first-axis FFT: the fused pad kernel stores Bt[u][y] (scattered 16-byte stores that
     // meet in L2, as on the gridding side) and the first-axis transform of row u reads its row of Bt contiguously -- a
     // 16-byte GATHER in that transform's load phase cost 0.3 ms per plane at C2, scattered stores cost 0.1.  The pitch is
-    // kept off the power of two for the same reason as bpitch (PFBHIP_TPAD elements, multiple of 8 = whole lines; 0 = off).
-    g->fgeom.tpitch = 0;
-    if (g->fused && g->rowfft_v.ok && g->rowfft_u.ok && sw.tpad > 0 && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v)))
-        g->fgeom.tpitch = int(prm.ny) + ((sw.tpad + 7) / 8) * 8;
+    // kept off the power of two for the same reason as bpitch (40 more elements: whole 128-byte lines).  Set wherever the
+    // transposing first axis can run; cleared again below if it does not.  (Doubled first-axis shapes: only where the
+    // waiting half transform is parked in LDS -- 20480 points.)
+    const bool tfft_ok = g->fused && g->rowfft_v.ok && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v));
+    g->fgeom.tpitch = tfft_ok ? int(prm.ny) + 40 : 0;
     g->bstride = std::max(g->bstride, size_t(info.nu) * size_t(g->fgeom.tpitch));
     lap("row-FFT tables + w-screens");
     g->d_gridB.alloc(g->bstride * size_t(g->fused ? g->kp_max : 1));
@@ -2062,7 +2051,6 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         const int64_t tu = wi.tile / uint32_t(m.ntv);
         for (int64_t r = tu * TILE; r <= tu * TILE + TILE + info.W - 2; ++r) occ[size_t((r % info.nu) / TP)] = 1;
     }
-    bool colruns_off = false;
     // tiles a footprint cell of some work item can fall in (the item's own tile and the tiles its (W - 1)-cell halo reaches,
     // wrapped; through a short last tile if the grid size is not a multiple of TILE).  Per TILE with work, and per row /
     // column of its region rather than per cell: the per-cell, per-item form of this loop was 0.1 s of the 0.13 s a C2 plan
@@ -2093,77 +2081,50 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                 for (int b = 0; b < ntc; ++b) touched_tiles[size_t(tr[a] * ntv_t + tc[b])] = 1;
         }
     }
-    {   // column runs per tile row (default: the whole row)
+    // Column runs per tile row: the runs of touched tile columns, the whole row for three or more runs (or without work).
+    // The transposing first-axis transforms load / store only these (d_colruns: RunLoad / RunStore), so they are also what
+    // has to be cleared of the scatter's planes (d_clear_rects: side-stream clear of single-pass plans, clear_planes()).
+    {
         const int64_t ntu_t = ceil_div(info.nu, TILE), ntv_t = m.ntv;
         std::vector<int4> runs_t(size_t(ntu_t), make_int4(0, int(info.nv), 0, 0));
         if (!work.empty()) {
-            const std::vector<uint8_t> &touched = touched_tiles;
+            std::vector<int4> rects;
+            int64_t cells = 0, full = 0;
+            constexpr int SLICE = 8;  // rows per rectangle: enough workgroups to fill the chip
             for (int64_t tu = 0; tu < ntu_t; ++tu) {
                 std::vector<std::pair<int, int>> rr;
                 for (int64_t tv = 0; tv < ntv_t;) {
-                    if (!touched[size_t(tu * ntv_t + tv)]) { ++tv; continue; }
+                    if (!touched_tiles[size_t(tu * ntv_t + tv)]) { ++tv; continue; }
                     int64_t e = tv;
-                    while (e < ntv_t && touched[size_t(tu * ntv_t + e)]) ++e;
+                    while (e < ntv_t && touched_tiles[size_t(tu * ntv_t + e)]) ++e;
                     rr.emplace_back(int(tv * TILE), int(std::min<int64_t>(e * TILE, info.nv)));
                     tv = e;
                 }
-                if (rr.size() == 1) runs_t[size_t(tu)] = make_int4(rr[0].first, rr[0].second, 0, 0);
-                else if (rr.size() == 2) runs_t[size_t(tu)] = make_int4(rr[0].first, rr[0].second, rr[1].first, rr[1].second);
-                else if (rr.empty()) runs_t[size_t(tu)] = make_int4(0, 0, 0, 0);
-                // (three or more runs: the whole row)
+                if (rr.size() >= 3) rr.assign(1, {0, int(info.nv)});
+                const int row0 = int(tu * TILE), nrows = int(std::min<int64_t>(TILE, info.nu - row0));
+                for (auto &run : rr) {
+                    const int col0 = run.first, ncols = run.second - run.first;
+                    for (int q = 0; q < nrows; q += SLICE) rects.push_back(make_int4(row0 + q, std::min(SLICE, nrows - q), col0, ncols));
+                    cells += int64_t(nrows) * ncols;
+                }
+                if (!rr.empty()) full += int64_t(nrows) * info.nv;
+                rr.resize(2, {0, 0});
+                runs_t[size_t(tu)] = make_int4(rr[0].first, rr[0].second, rr[1].first, rr[1].second);
             }
-            info.used_cells = 0;
-            for (int64_t tu = 0; tu < ntu_t; ++tu) {
-                const int4 r = runs_t[size_t(tu)];
-                info.used_cells += std::min<int64_t>(TILE, info.nu - tu * TILE) * (int64_t(r.y - r.x) + int64_t(r.w - r.z));
+            info.used_cells = cells;
+            if (!rects.empty() && cells * 10 < full * 8) {  // (fragmented or nearly full coverage: plain memsets of whole rows)
+                g->d_clear_rects.alloc(rects.size());
+                PFB_HIP(hipMemcpyAsync(g->d_clear_rects.p, rects.data(), rects.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+                PFB_HIP(hipStreamSynchronize(st));
+                g->n_clear_rects = int(rects.size());
             }
-        }
-        if (!sw.colruns) {
-            std::fill(runs_t.begin(), runs_t.end(), make_int4(0, int(info.nv), 0, 0));
-            info.used_cells = 0;
-            colruns_off = true;
+            if (prm.verbosity > 0)
+                fprintf(stderr, "[pfbhip] scatter-plane clear: %lld of %lld cells in %zu rectangles\n", (long long)cells,
+                        (long long)full, rects.size());
         }
         g->d_colruns.alloc(runs_t.size());
         PFB_HIP(hipMemcpyAsync(g->d_colruns.p, runs_t.data(), runs_t.size() * sizeof(int4), hipMemcpyHostToDevice, st));
         PFB_HIP(hipStreamSynchronize(st));
-    }
-    if (!work.empty() && !colruns_off) {  // (side-stream clear of single-pass plans; clear_planes() on the transposing path)
-        const int64_t ntu_t = ceil_div(info.nu, TILE), ntv_t = m.ntv;
-        const std::vector<uint8_t> &touched = touched_tiles;
-        std::vector<int4> rects;
-        int64_t cells = 0, full = 0;
-        constexpr int SLICE = 8;  // rows per rectangle: enough workgroups to fill the chip
-        for (int64_t tu = 0; tu < ntu_t; ++tu) {
-            const int row0 = int(tu * TILE), nrows = int(std::min<int64_t>(TILE, info.nu - row0));
-            bool any = false;
-            // (the same runs as d_colruns above: a tile row with three or more runs is taken whole there -- the first-axis
-            // transforms then read and write the whole row, so the whole row is what has to be cleared)
-            std::vector<std::pair<int, int>> rr;
-            for (int64_t tv = 0; tv < ntv_t;) {
-                if (!touched[size_t(tu * ntv_t + tv)]) { ++tv; continue; }
-                int64_t e = tv;
-                while (e < ntv_t && touched[size_t(tu * ntv_t + e)]) ++e;
-                rr.emplace_back(int(tv * TILE), int(std::min<int64_t>(e * TILE, info.nv)));
-                tv = e;
-            }
-            if (rr.size() >= 3) rr.assign(1, {0, int(info.nv)});
-            for (auto &run : rr) {
-                const int col0 = run.first, ncols = run.second - run.first;
-                for (int r = 0; r < nrows; r += SLICE) rects.push_back(make_int4(row0 + r, std::min(SLICE, nrows - r), col0, ncols));
-                cells += int64_t(nrows) * ncols;
-                any = true;
-            }
-            if (any) full += int64_t(nrows) * info.nv;
-        }
-        if (!rects.empty() && cells * 10 < full * 8) {  // (fragmented or nearly full coverage: plain memsets of whole rows)
-            g->d_clear_rects.alloc(rects.size());
-            PFB_HIP(hipMemcpyAsync(g->d_clear_rects.p, rects.data(), rects.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-            PFB_HIP(hipStreamSynchronize(st));
-            g->n_clear_rects = int(rects.size());
-        }
-        if (prm.verbosity > 0)
-            fprintf(stderr, "[pfbhip] scatter-plane clear: %lld of %lld cells in %zu rectangles\n", (long long)cells, (long long)full,
-                    rects.size());
     }
     // spans of consecutive occupied blocks (at most a handful for a centrally concentrated uv coverage)
     std::vector<std::pair<int64_t, int64_t>> runs;
@@ -2220,10 +2181,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     }
     info.occ_rows = int32_t(g->occ_rows);
     {
-        const int want = sw.tfft;
-        // (doubled first-axis shapes: only where the waiting half transform is parked in LDS -- 20480 points --, unless forced)
-        const bool v_ok = g->rowfft_v.ok && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v));
-        g->tfft = (want != 0 && g->fused && v_ok && g->occ_rows > 0) ? want : 0;
+        g->tfft = sw.tfft && tfft_ok && g->occ_rows > 0;
         if (g->tfft) {
             std::vector<int> rows;
             rows.reserve(size_t(g->occ_rows));
@@ -2232,7 +2190,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             const size_t n = rows.size(), ngroups = n / 8, nfull = ngroups / 8;
             std::vector<int> map(n);
             for (size_t b = 0; b < n; ++b) {
-                if (g->tfft == 1 && b < nfull * 64) {  // super-group of 64 block ids = 8 XCDs x 8 adjacent rows
+                if (b < nfull * 64) {  // super-group of 64 block ids = 8 XCDs x 8 adjacent rows
                     const size_t sg = b / 64, r = b % 64, xcd = r % 8, k = r / 8;
                     map[b] = rows[(sg * 8 + xcd) * 8 + k];
                 } else {

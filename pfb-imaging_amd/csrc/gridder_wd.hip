@@ -3,36 +3,19 @@
 #include "gridder_kernels_wd.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <stdexcept>
 
 #include "common.hpp"
 
 namespace pfbhip {
 
-// Threads per workgroup: 256 -- one wave per SIMD, three workgroups per CU (see gridder_kernels_wd.hpp); PFBHIP_WD_SCATTER_THREADS /
-// PFBHIP_WD_GATHER_THREADS override (measured on C2, ms per apply: scatter 768 x 1: 2.76, 384 x 2: 3.3, 256 x 3: 2.31; gather
-// 768 x 1: 1.90, 384 x 2: 2.33, 256 x 3: 1.64).
-static int env_threads(const char *name, int dflt, int cap)
-{
-    const char *e = std::getenv(name);
-    if (e == nullptr) return dflt;
-    const int v = std::atoi(e);
-    return (v >= 256 && v <= cap && v % 64 == 0) ? v : dflt;  // (>= 256: the tile flush holds its cells in registers, sized for that)
-}
-// Launches of fewer work items than three per CU (C1: ~300) cannot fill the chip with 256-thread workgroups: those take one
-// 768-thread workgroup per item.
-static int scatter_threads_for(uint32_t nwork)
-{
-    static const int t = env_threads("PFBHIP_WD_SCATTER_THREADS", 0, wd_threads());
-    return t > 0 ? t : (nwork < 768u ? wd_threads() : 256);
-}
+// Threads per workgroup: 256 -- one wave per SIMD, three workgroups per CU (see gridder_kernels_wd.hpp; measured on C2, ms per
+// apply: scatter 768 x 1: 2.76, 384 x 2: 3.3, 256 x 3: 2.31; gather 768 x 1: 1.90, 384 x 2: 2.33, 256 x 3: 1.64).  Launches of
+// fewer work items than three per CU (C1: ~300) cannot fill the chip with 256-thread workgroups: those take one 768-thread
+// workgroup per item.
+static int scatter_threads_for(uint32_t nwork) { return nwork < 768u ? wd_threads() : 256; }
 int wd_scatter_threads() { return wd_threads(); }  // (the largest: what the LDS limit is sized for)
-static int wd_gather_threads_rt(int NJ, uint32_t nwork)
-{
-    static const int t = env_threads("PFBHIP_WD_GATHER_THREADS", 0, MP_THREADS);
-    return std::min(t > 0 ? t : (nwork < 768u ? 768 : 256), wd_gather_threads(NJ));
-}
+static int wd_gather_threads_rt(int NJ, uint32_t nwork) { return std::min(nwork < 768u ? 768 : 256, wd_gather_threads(NJ)); }
 size_t wd_scatter_lds_bytes(int W)
 {
     size_t n = 0;

@@ -153,8 +153,9 @@ void rowfft_plain(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inver
 // first-axis passes with the transpose folded in (no separate k_a2b / k_b2a pass over the plane)
 // ---------------------------------------------------------------------------------------
 // grid side:   B[y][u] = IFFT_v(A[u][:])[wrap(y - ny/2, nv)]      (crop + transpose in the store)
-// degrid side: A[u][:] = FFT_v( v -> B[y(v)][u], 0 outside the image )  (pad + transpose in the load)
-// One workgroup owns one row u, so its B accesses are 16-byte pieces nu * 16 bytes apart.  What makes that
+// degrid side: A[u][:] = FFT_v( v -> Bt[u][y(v)], 0 outside the image )  (pad in the load; the fused pad kernel stored Bt
+//              transposed, so the load is contiguous)
+// One workgroup owns one row u, so its B accesses (grid side) are 16-byte pieces nu * 16 bytes apart.  What makes that
 // affordable is WHICH workgroups run together: rowmap[] hands the 8 rows of every 128-byte line of B to 8
 // workgroups that share an XCD (blockIdx equal mod 8) and are dispatched within the same 64 block ids, so the 8
 // pieces of a line meet in that XCD's L2 -- stores leave it as whole lines, loads miss once per line.
@@ -168,14 +169,6 @@ struct CropTStore {
         else if (v >= nv - hy) y = v - (nv - hy);
         if (y >= 0) B[size_t(y) * size_t(nu) + size_t(u)] = val;
     }
-};
-struct PadTLoad {
-    const double2 *B;
-    int u, nu, ny, nv, hy;
-    __device__ __forceinline__ int yof(int v) const { return v < ny - hy ? v + hy : (v >= nv - hy ? v - (nv - hy) : -1); }
-    __device__ __forceinline__ double2 fetch(int v, int) const { return B[size_t(max(yof(v), 0)) * size_t(nu) + size_t(u)]; }
-    __device__ __forceinline__ double2 finish(double2 x, int v, int) const { return yof(v) >= 0 ? x : make_double2(0.0, 0.0); }
-    __device__ __forceinline__ double2 operator()(int v, int s) const { return finish(fetch(v, s), v, s); }
 };
 
 // (Round 3 tried an L2 warm-up here -- every workgroup, once its own requests were out, requested one dword per 128-byte line
@@ -208,7 +201,7 @@ struct PadRowLoad {
     __device__ __forceinline__ double2 operator()(int v, int s) const { return finish(fetch(v, s), v, s); }
 };
 
-template <class S, bool TR>
+template <class S>
 __global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_rowfft_b2a(const double2 *tw, const double2 *B, double2 *A,
                                                                           const int *rowmap, int nrows, int nu, int ny, size_t apitch,
                                                                           int tpitch, size_t astride, size_t bstride, const int4 *colruns)
@@ -219,13 +212,8 @@ __global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_rowfft_b2a(const do
     A += size_t(blockIdx.y) * astride;
     B += size_t(blockIdx.y) * bstride;
     RunStore st{A + size_t(u) * apitch, colruns[u >> 5]};
-    if constexpr (TR) {
-        PadRowLoad ld{B + size_t(u) * size_t(tpitch), ny, S::N, ny / 2};
-        rf_row<S>(tw, ld, st, false, rf_lds);
-    } else {
-        PadTLoad ld{B, u, nu, ny, S::N, ny / 2};
-        rf_row<S>(tw, ld, st, false, rf_lds);
-    }
+    PadRowLoad ld{B + size_t(u) * size_t(tpitch), ny, S::N, ny / 2};
+    rf_row<S>(tw, ld, st, false, rf_lds);
 }
 
 // slots of the waiting half that fit behind the exchange buffer (the rest stay in registers); 0: no stash
@@ -289,7 +277,7 @@ __global__ void __launch_bounds__(S1::T, ((S1::T + 63) / 64 + 3) / 4) k_rowfft_a
     CropTStore st{B, u, nu, ny, 2 * S1::N, ny / 2};
     rf_row2<S1, STASH>(tw, ld, st, true, rf_lds);
 }
-template <class S1, bool TR, bool STASH>
+template <class S1, bool STASH>
 __global__ void __launch_bounds__(S1::T, ((S1::T + 63) / 64 + 3) / 4) k_rowfft_b2a2(const double2 *tw, const double2 *B, double2 *A,
                                                                                     const int *rowmap, int nrows, int nu, int ny,
                                                                                     size_t apitch, int tpitch, size_t astride,
@@ -301,13 +289,8 @@ __global__ void __launch_bounds__(S1::T, ((S1::T + 63) / 64 + 3) / 4) k_rowfft_b
     A += size_t(blockIdx.y) * astride;
     B += size_t(blockIdx.y) * bstride;
     RunStore st{A + size_t(u) * apitch, colruns[u >> 5]};
-    if constexpr (TR) {
-        PadRowLoad ld{B + size_t(u) * size_t(tpitch), ny, 2 * S1::N, ny / 2};
-        rf_row2<S1, STASH>(tw, ld, st, false, rf_lds);
-    } else {
-        PadTLoad ld{B, u, nu, ny, 2 * S1::N, ny / 2};
-        rf_row2<S1, STASH>(tw, ld, st, false, rf_lds);
-    }
+    PadRowLoad ld{B + size_t(u) * size_t(tpitch), ny, 2 * S1::N, ny / 2};
+    rf_row2<S1, STASH>(tw, ld, st, false, rf_lds);
 }
 template <class S1>
 static void launch_a2b2(const RowFFTPlan &pl, const double2 *A, double2 *B, const int *rowmap, int nrows, int nu, int ny,
@@ -324,19 +307,12 @@ template <class S1>
 static void launch_b2a2(const RowFFTPlan &pl, const double2 *B, double2 *A, const int *rowmap, int nrows, int nu, int ny,
                         size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false, attr_t = false;
+    static bool attr = false;
     constexpr bool STASH = rf_stash_slots<S1>() > 0;
-    const dim3 grid(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes));
-    const size_t lds = size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double);
-    if (tpitch > 0) {
-        rf_allow_lds(&k_rowfft_b2a2<S1, true, STASH>, &attr_t);
-        hipLaunchKernelGGL((k_rowfft_b2a2<S1, true, STASH>), grid, dim3(S1::T), lds, stream, pl.twiddle, B, A, rowmap, nrows, nu, ny,
-                           apitch, tpitch, astride, bstride, colruns);
-        return;
-    }
-    rf_allow_lds(&k_rowfft_b2a2<S1, false, STASH>, &attr);
-    hipLaunchKernelGGL((k_rowfft_b2a2<S1, false, STASH>), grid, dim3(S1::T), lds, stream, pl.twiddle, B, A, rowmap, nrows, nu, ny, apitch,
-                       0, astride, bstride, colruns);
+    rf_allow_lds(&k_rowfft_b2a2<S1, STASH>, &attr);
+    hipLaunchKernelGGL((k_rowfft_b2a2<S1, STASH>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S1::T),
+                       size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double), stream, pl.twiddle, B, A, rowmap,
+                       nrows, nu, ny, apitch, tpitch, astride, bstride, colruns);
 }
 
 template <class S>
@@ -353,17 +329,10 @@ template <class S>
 static void launch_b2a(const RowFFTPlan &pl, const double2 *B, double2 *A, const int *rowmap, int nrows, int nu, int ny,
                        size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false, attr_t = false;
-    const dim3 grid(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes));
-    if (tpitch > 0) {
-        rf_allow_lds(&k_rowfft_b2a<S, true>, &attr_t);
-        hipLaunchKernelGGL((k_rowfft_b2a<S, true>), grid, dim3(S::T), size_t(S::LDS_BYTES), stream, pl.twiddle, B, A, rowmap, nrows,
-                           nu, ny, apitch, tpitch, astride, bstride, colruns);
-        return;
-    }
-    rf_allow_lds(&k_rowfft_b2a<S, false>, &attr);
-    hipLaunchKernelGGL((k_rowfft_b2a<S, false>), grid, dim3(S::T), size_t(S::LDS_BYTES), stream, pl.twiddle, B, A, rowmap, nrows, nu,
-                       ny, apitch, 0, astride, bstride, colruns);
+    static bool attr = false;
+    rf_allow_lds(&k_rowfft_b2a<S>, &attr);
+    hipLaunchKernelGGL((k_rowfft_b2a<S>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S::T), size_t(S::LDS_BYTES),
+                       stream, pl.twiddle, B, A, rowmap, nrows, nu, ny, apitch, tpitch, astride, bstride, colruns);
 }
 
 void rowfft_a2b(const RowFFTPlan &pl, const double2 *A_dev, double2 *B_dev, const int *rowmap_dev, int nrows, int nu, int ny,
@@ -386,6 +355,7 @@ void rowfft_a2b(const RowFFTPlan &pl, const double2 *A_dev, double2 *B_dev, cons
 void rowfft_b2a(const RowFFTPlan &pl, const double2 *B_dev, double2 *A_dev, const int *rowmap_dev, int nrows, int nu, int ny,
                 size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
+    PFB_REQUIRE(tpitch > 0, "rowfft_b2a reads the transposed plane Bt (tpitch %d): the fused pad kernel must store it", tpitch);
     switch (pl.N) {
 #define RF_X(L, K)                                                                       \
     case (L << K): launch_b2a<RfShape<L, K>>(pl, B_dev, A_dev, rowmap_dev, nrows, nu, ny, apitch, tpitch, nplanes, astride, bstride, colruns, stream); break;
@@ -646,7 +616,7 @@ __global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_fused_pad_fft(const
             rf_row_compute<S>(tw, ld, false, rf_lds, t, re, im);
             rf_opaque(t);
             __builtin_amdgcn_sched_barrier(0);
-            if (g.tpitch > 0) {  // Bt[u][y]: the first-axis transform of row u then reads contiguously (k_rowfft_b2a<S, true>)
+            if (g.tpitch > 0) {  // Bt[u][y]: the first-axis transform of row u then reads contiguously (k_rowfft_b2a)
                 double2 *bcol = B + size_t(k) * bstride + size_t(y);
 #pragma unroll
                 for (int e = 0; e < S::E; ++e)
@@ -1261,29 +1231,26 @@ static void launch_pad(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t *
     const bool row = fused_row_fits(S::LDS_BYTES, g.nx);
     PFB_REQUIRE(row || prep.x == nullptr, "fused pad kernel without an LDS row needs a prepared image (fused_pad_takes_prep)");
     const size_t lds = size_t(S::LDS_BYTES) + (row ? size_t(g.nx) * sizeof(double) : 0);
-    {   // single-plane launches on the raw image: the persistent form (PFBHIP_PAD_PERSIST=0 keeps one workgroup per row)
-        static const bool persist = [] { const char *e = std::getenv("PFBHIP_PAD_PERSIST"); return !(e != nullptr && e[0] == '0'); }();
-        if (persist && row && planes.kp == 1 && prep.x != nullptr) {
-            int dev = 0, ncu = 256;
-            PFB_HIP(hipGetDevice(&dev));
-            PFB_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-            // one workgroup per CU, a multiple of 64 of them (the row -> block map groups blocks in 64s)
-            const uint32_t nwg = uint32_t(std::min<int>(g.ny, std::max(64, (ncu / 64) * 64)));
-            const bool sc = planes.nsc > 0 && !planes.sep && do_w, beam = prep.beam != nullptr;
-            static bool ap[4] = {false, false, false, false};
+    if (row && planes.kp == 1 && prep.x != nullptr) {  // single-plane launches on the raw image: the persistent form
+        int dev = 0, ncu = 256;
+        PFB_HIP(hipGetDevice(&dev));
+        PFB_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        // one workgroup per CU, a multiple of 64 of them (the row -> block map groups blocks in 64s)
+        const uint32_t nwg = uint32_t(std::min<int>(g.ny, std::max(64, (ncu / 64) * 64)));
+        const bool sc = planes.nsc > 0 && !planes.sep && do_w, beam = prep.beam != nullptr;
+        static bool ap[4] = {false, false, false, false};
 #define PFB_PADP(SCV, BV)                                                                                                        \
     do {                                                                                                                         \
         rf_allow_lds(&k_fused_pad_fft_p<S, SCV, BV>, &ap[(SCV ? 2 : 0) + (BV ? 1 : 0)]);                                          \
         hipLaunchKernelGGL((k_fused_pad_fft_p<S, SCV, BV>), dim3(nwg), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, prep, planes, \
                            do_w, B_dev);                                                                                         \
     } while (0)
-            if (sc && beam) PFB_PADP(true, true);
-            else if (sc) PFB_PADP(true, false);
-            else if (beam) PFB_PADP(false, true);
-            else PFB_PADP(false, false);
+        if (sc && beam) PFB_PADP(true, true);
+        else if (sc) PFB_PADP(true, false);
+        else if (beam) PFB_PADP(false, true);
+        else PFB_PADP(false, false);
 #undef PFB_PADP
-            return;
-        }
+        return;
     }
     if (planes.nsc > 0 && !planes.sep && do_w) {
         rf_allow_lds(&k_fused_pad_fft<S, true>, &attr_sc);
