@@ -726,6 +726,9 @@ struct pfbhip_gridder {
     bool wd_small = false;  // few work items: one scatter launch with the atomic tile flush instead of four colour launches
     int pval_per_vis() const { return info.wmode == 2 ? wd.K : kp_max; }
     bool pval_from_gather = false;  // single-pass plans: the gather's epilogue writes the scatter's values inside a Hessian apply
+    // one-plane coloured plans (wd_hessian_supported): a Hessian apply runs k_hess_wd per colour instead of the gather and the
+    // four scatter launches (hess_fused: inside such an apply)
+    bool hess_fused_ok = false, hess_fused = false;
     DevBuf<VisRec> d_rec;
     // row-walk gather (k_degrid_rw): same plans as the record scatter; d_kw: plane weights of every visibility (plan time)
     bool gather_rw = false;
@@ -773,7 +776,10 @@ struct pfbhip_gridder {
                 if (ga.a.nwork == 0) continue;
                 timer.begin(0);
                 if (info.wmode == 2) {
-                    wd_launch_grid(ga, wd, d_rec.p, d_pval.p, grid_cur, stream);
+                    if (hess_fused)  // (the gather's plane is d_grid, the output grid_cur = d_grid2)
+                        wd_launch_hessian(ga, wd, d_rec.p, d_swgt.p, d_grid.p, grid_cur, stream);
+                    else
+                        wd_launch_grid(ga, wd, d_rec.p, d_pval.p, grid_cur, stream);
                     timer.end();
                     continue;
                 }
@@ -1034,7 +1040,7 @@ struct pfbhip_gridder {
     // `prep` (fused path only): the fused pad kernel reads x * corr [* beam] itself instead of a prepared accT
     void degrid_all_planes(double2 *sacc, const FusedPrep *prep = nullptr)
     {
-        if (!want_pval) PFB_HIP(hipMemsetAsync(sacc, 0, size_t(std::max<int64_t>(info.nactive, 1)) * sizeof(double2), stream));
+        if (!want_pval && !hess_fused) PFB_HIP(hipMemsetAsync(sacc, 0, size_t(std::max<int64_t>(info.nactive, 1)) * sizeof(double2), stream));
         if (info.nactive == 0 || info.nwork == 0) return;
         for (int p0 = 0; p0 < info.nplanes; p0 += kp_max) {
             const int kp = int(std::min<int64_t>(kp_max, info.nplanes - p0));
@@ -1069,6 +1075,7 @@ struct pfbhip_gridder {
                 fft_rows_A(true, k);
             }
             if (side_clear_pending) side_clear();
+            if (hess_fused) continue;  // (the fused launches of the scatter half gather)
             timer.begin(1);
             PFB_W_DISPATCH(launch_degrid_mp_w, p0, kp, sacc);
             PFB_HIP(hipGetLastError());
@@ -1243,6 +1250,7 @@ struct PlanSwitches {
     int fused_doubled = -1;   // PFBHIP_FUSED_DOUBLED: -1 plan decides, 0 / 1 forced
     bool sepscreen = true;    // PFBHIP_SEPSCREEN=0: no separable w-screen form
     bool tfft = true;         // PFBHIP_TFFT=0: plain first-axis row FFT + separate transpose kernels
+    bool wd_fused = true;     // PFBHIP_WD_FUSED=0: one-plane Hessian applies keep the gather / scatter pair
 };
 
 static PlanSwitches read_plan_switches()
@@ -1271,6 +1279,7 @@ static PlanSwitches read_plan_switches()
     sw.fused_doubled = fd < 0 ? -1 : (fd == '1' ? 1 : 0);
     sw.sepscreen = first("PFBHIP_SEPSCREEN") != '0';
     sw.tfft = first("PFBHIP_TFFT") != '0';
+    sw.wd_fused = first("PFBHIP_WD_FUSED") != '0';
     return sw;
 }
 
@@ -1934,6 +1943,8 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             PFB_HIP(hipEventCreateWithFlags(&g->ev_start, hipEventDisableTiming));
             PFB_HIP(hipMemsetAsync(g->d_grid2.p, 0, g->d_grid2.bytes(), st));
         }
+        g->hess_fused_ok = sw.wd_fused && info.wmode == 2 && g->coloured && !g->wd_small && g->async_clear && info.nplanes == 1 &&
+                           wd_hessian_supported(int(info.W), g->wd.bc);
     }
     lap("uv-plane buffers");
     g->d_img.alloc(size_t(npix));
@@ -2423,14 +2434,19 @@ static void apply_op(pfbhip_gridder *g, const double *x_dev, const double *beam_
     g->side_clear_pending = side;
     g->side_clear_done = false;
     // record scatter: the gather's epilogue writes the weighted, plane-weighted model visibilities (no sacc, no scaling pass)
-    g->want_pval = g->pval_from_gather && g->info.nwork > 0;
+    // one-plane coloured plans: no gather launch; the scatter half's launches gather from d_grid themselves (k_hess_wd)
+    g->hess_fused = g->hess_fused_ok && side;
+    g->want_pval = !g->hess_fused && g->pval_from_gather && g->info.nwork > 0;
     struct ClearFlags {
         pfbhip_gridder *g;
-        ~ClearFlags() { g->want_pval = g->pval_ready = false; }
+        ~ClearFlags() { g->want_pval = g->pval_ready = g->hess_fused = false; }
     } clear_flags{g};
     g->prepare_and_degrid(x_dev, beam_dev, g->d_sacc.p);
     g->side_clear_pending = false;
-    if (g->want_pval) {
+    if (g->hess_fused) {
+        PFB_REQUIRE(g->side_clear_done, "fused Hessian: the output plane was not cleared");
+        g->pval_ready = true;
+    } else if (g->want_pval) {
         g->want_pval = false;
         g->pval_ready = true;
     } else {

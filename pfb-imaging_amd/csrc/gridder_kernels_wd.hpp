@@ -432,6 +432,21 @@ __device__ __forceinline__ void wd_steps(const char *base, const double (&ku)[NJ
     }
 }
 
+// frame row f of the fused Hessian kernel: += a_r(f - du) (lane f of the row) P_r(column)
+template <int FP, int NJ, int F>
+__device__ __forceinline__ void hess_frame_steps(const double (&ks)[NJ], const double (&pr)[NJ], const double (&pim)[NJ],
+                                                 double (&fre)[FP], double (&fim)[FP])
+{
+    if constexpr (F < FP) {
+#pragma unroll
+        for (int r = 0; r < NJ; ++r) {
+            fmac_row_bcast<F>(fre[F], ks[r], pr[r]);
+            fmac_row_bcast<F>(fim[F], ks[r], pim[r]);
+        }
+        hess_frame_steps<FP, NJ, F + 1>(ks, pr, pim, fre, fim);
+    }
+}
+
 // register budget of the gather: 768 threads per CU (168 VGPRs: the three / four coefficient sets of K >= 3 do not fit the 128 of
 // 1024 threads), launched as three workgroups of 256 (one wave per SIMD each: a workgroup's tile load -- 19 % of an item's
 // cycles -- overlaps the other two's rounds; C2: 1.90 -> 1.64 ms)
@@ -598,6 +613,217 @@ __global__ void __launch_bounds__(wd_gather_threads(NJ)) k_degrid_wd(GroupArgs g
 #pragma unroll
         for (int k = 0; k < NJ; ++k) cwv[k] = ncw[k];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Hessian apply in one pass (R^H W R on one plane): for every visibility of a scatter work item, the gather's value from the
+// input plane and, weighted, its scatter into the output plane.  Both halves run in the GATHER's lane layout: four
+// visibilities per wave, one per 16-lane row, and lane b on frame column b -- the column c0 + b of the tile, where (r0, c0) is
+// the corner of the visibility's BC x BC block.  Row g of a wave walks a contiguous quarter of the wave's share (the sort's
+// block runs stay whole).  Per visibility, shared by both halves: the K u- and v-kernel values (Horner on the lane's own
+// coefficient registers, as k_degrid_wd) and S_r(b) = sum_m binom(r + m, r) C_{r+m} b_m(b - dv).
+//   gather:  T_r(b) = sum_i a_r(i) in(lu + i, c0 + b)  (the row walk, a_r broadcast by v_fmac_f64_dpp row_newbcast),
+//            value = sum_b sum_r T_r(b) conj(S_r(b))  (half-row sums, then the other half by one DPP rotation);
+//   scatter: P_r(b) = value swgt S_r(b) (= the S_r of P_k = value swgt C_k), and frame row f (tile row r0 + f) gets
+//            sum_r a_r(f - du) P_r(b): the same broadcast FMA with the u-values moved by du lanes (one ds_bpermute).
+// The frame (W + BC - 1 <= 16 rows of 16 columns, 32 doubles per lane) is flushed into the LDS output tile with ds_add when
+// the row's block changes.  Input plane: the 48 x 48 tile of k_degrid_wd in LDS; output: k_grid_wd's tile and flush.
+// Launched with 256 threads; two workgroups (71 KB of LDS each at W = 15) and two waves per SIMD.  The 512 of __launch_bounds__ is
+// the REGISTER CAP, not the launch size: it holds the compiler to <= 256 VGPRs per lane (two waves per SIMD); with 256 it may
+// allocate up to 512 (one wave per SIMD, and the second workgroup would not fit beside the first).
+__host__ __device__ constexpr bool wd_hess_fits(int W, int BC) { return W + BC - 1 <= 16; }
+__host__ __device__ constexpr size_t wd_hess_lds_bytes(int W)
+{
+    return size_t(2) * blk_tile_rows(W) * wd_stride(W) * sizeof(double) + size_t(RW_LS) * RW_LS * 16;
+}
+
+template <int W, int NJ, int BC>
+__global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const VisRec *__restrict__ rec, const double *__restrict__ swgt,
+                                                 const double2 *__restrict__ gin, double2 *__restrict__ gout)
+{
+    const PlaneArgs &a = ga.a;
+    constexpr int D = kernel_poly_degree_c(W);
+    constexpr int L = TILE + W - 1;
+    constexpr int LS = wd_stride(W);
+    constexpr int LL = blk_tile_rows(W) * LS;
+    constexpr int LLI = RW_LS * RW_LS;
+    constexpr int FP = W + BC - 1;
+    static_assert(BC == 2 || BC == 4, "block edge: 2 or 4 cells");
+    static_assert(wd_hess_fits(W, BC), "frame wider than a 16-lane row");
+    extern __shared__ double lds[];
+    double2 *tin = reinterpret_cast<double2 *>(lds + 2 * LL);
+
+    const uint32_t item = blockIdx.x;
+    if (item >= a.nwork) return;
+    const WorkItem wi = a.work[item];
+    const int bu = int(wi.tile / uint32_t(a.ntv)) * TILE;
+    const int bv = int(wi.tile % uint32_t(a.ntv)) * TILE;
+    const int NT = int(blockDim.x);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = lane & 15, g = lane >> 4, rowl = lane & ~15;
+    // visibilities of this row: stream s = 4 wave + g of NS, a contiguous slice of the item
+    const uint32_t n = wi.end - wi.begin, NS = uint32_t(NT / 64) * 4, sidx = uint32_t(wave) * 4 + uint32_t(g);
+    uint32_t j = wi.begin + uint32_t((uint64_t(n) * sidx) / NS);
+    const uint32_t jend = wi.begin + uint32_t((uint64_t(n) * (sidx + 1)) / NS);
+    const uint32_t niter = (n + NS - 1) / NS;
+    const uint32_t jlast = wi.end - 1;
+    auto load_z = [&](uint32_t jj) { return *reinterpret_cast<const double2 *>(rec + min(jj, jlast)); };
+    auto load_key = [&](uint32_t jj) { return rec[min(jj, jlast)].key; };
+    double2 z = load_z(j);
+    int key = load_key(j);
+    double wv = j < jend ? swgt[min(j, jlast)] : 0.0;
+    double2 cwv[NJ];
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) cwv[k] = wa.cw[size_t(min(j, jlast)) * NJ + k];
+
+    for (int i = threadIdx.x; i < 2 * LL; i += NT) lds[i] = 0.0;
+    for (int i0 = 0; i0 < LLI; i0 += 4 * NT) {  // input tile, as k_degrid_wd
+        double2 v[4];
+        int idx[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = i0 + int(threadIdx.x) + q * NT;
+            idx[q] = i;
+            const int ic = min(i, LLI - 1);
+            const int la = ic / RW_LS, lb = ic - la * RW_LS;
+            int gu = bu + la, gv = bv + lb;
+            gu = gu >= a.nu ? gu % a.nu : gu;
+            gv = gv >= a.nv ? gv % a.nv : gv;
+            const bool in = i < LLI && la < L && lb < L;
+            const double2 t = gin[size_t(gu) * size_t(a.apitch) + size_t(gv)];
+            v[q] = in ? t : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (idx[q] < LLI) tin[idx[q]] = v[q];
+    }
+    double c0[D + 1], c1[D - 1], c2[NJ > 2 ? D - 3 : 1], c3[NJ > 3 ? D - 5 : 1];
+#pragma unroll
+    for (int q = 0; q <= D; ++q) c0[q] = b < W ? wa.dtab[(size_t(0) * W + b) * (D + 1) + q] : 0.0;
+#pragma unroll
+    for (int q = 0; q <= D - 2; ++q) c1[q] = b < W ? wa.dtab[(size_t(1) * W + b) * (D + 1) + q] : 0.0;
+    if constexpr (NJ > 2) {
+#pragma unroll
+        for (int q = 0; q <= D - 4; ++q) c2[q] = b < W ? wa.dtab[(size_t(2) * W + b) * (D + 1) + q] : 0.0;
+    }
+    if constexpr (NJ > 3) {
+#pragma unroll
+        for (int q = 0; q <= D - 6; ++q) c3[q] = b < W ? wa.dtab[(size_t(3) * W + b) * (D + 1) + q] : 0.0;
+    }
+    auto evens = [](const auto &c, auto deg, double zz) {
+        constexpr int DG = decltype(deg)::value;
+        const double z2 = zz * zz;
+        double e = c[DG], o = c[DG - 1];
+#pragma unroll
+        for (int k = DG - 2; k >= 0; k -= 2) {
+            e = fma(e, z2, c[k]);
+            if (k >= 1) o = fma(o, z2, c[k - 1]);
+        }
+        return fma(o, zz, e);
+    };
+    auto kernel_values = [&](double zz, const double *scale, double (&out)[NJ]) {
+        out[0] = evens(c0, std::integral_constant<int, D>{}, zz);
+        out[1] = evens(c1, std::integral_constant<int, D - 2>{}, zz) * scale[1];
+        if constexpr (NJ > 2) out[2] = evens(c2, std::integral_constant<int, D - 4>{}, zz) * scale[2];
+        if constexpr (NJ > 3) out[3] = evens(c3, std::integral_constant<int, D - 6>{}, zz) * scale[3];
+    };
+
+    double fre[FP], fim[FP];  // the row's frame: tile row r0 + f, column c0 + b
+#pragma unroll
+    for (int f = 0; f < FP; ++f) fre[f] = fim[f] = 0.0;
+    int cur = -1;  // block of the frame: (r0 << 8) | c0, -1 empty
+    auto flush = [&]() {
+        const int r0 = cur >> 8, cc = cur & 255;
+        double *o = lds + r0 * LS + cc + b;
+        if (b < FP) {
+#pragma unroll
+            for (int f = 0; f < FP; ++f) {
+                unsafeAtomicAdd(o + f * LS, fre[f]);
+                unsafeAtomicAdd(o + LL + f * LS, fim[f]);
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < FP; ++f) fre[f] = fim[f] = 0.0;
+    };
+    __syncthreads();
+
+    const char *tbase = reinterpret_cast<const char *>(tin);
+    for (uint32_t it = 0; it < niter; ++it) {
+        const bool valid = j < jend;
+        const uint32_t jn = j + 1;
+        const double2 nz = load_z(jn);
+        const int nkey = load_key(jn);
+        const double nwv = jn < jend ? swgt[min(jn, jlast)] : 0.0;
+        double2 ncw[NJ];
+#pragma unroll
+        for (int k = 0; k < NJ; ++k) ncw[k] = wa.cw[size_t(min(jn, jlast)) * NJ + k];
+        {
+            double ku[NJ], kvb[NJ];
+            kernel_values(z.x, wa.su, ku);
+            kernel_values(z.y, wa.sv, kvb);
+            const int lu = key >> 8, lv = key & 255;
+            const int du = lu & (BC - 1), dv = lv & (BC - 1);
+            const int c0c = lv - dv;
+            // taps b - dv / f - du; a negative tap wraps to 16 - d >= W (BC = 2: W <= 15, BC = 4: W <= 13): zero coefficients
+            double B[NJ], ks[NJ];
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) B[r] = __shfl(kvb[r], rowl + ((b - dv) & 15));
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) ks[r] = __shfl(ku[r], rowl + ((b - du) & 15));
+            const char *base = tbase + (lu * RW_LS + c0c + b) * 16;
+            double tr[NJ], ti[NJ];
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) tr[r] = ti[r] = 0.0;
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) asm volatile("s_nop 1" : "+v"(ku[r]));  // VALU write -> DPP read needs 2 wait states
+            wd_steps<W, NJ, 0>(base, ku, tr, ti);
+            double sr[NJ], si[NJ];
+            double vr = 0.0, vi = 0.0;
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) {
+                sr[r] = cwv[r].x * B[0];
+                si[r] = cwv[r].y * B[0];
+#pragma unroll
+                for (int m = 1; r + m < NJ; ++m) {
+                    const double bm = double(wd_binom(r + m, r)) * B[m];
+                    sr[r] = fma(cwv[r + m].x, bm, sr[r]);
+                    si[r] = fma(cwv[r + m].y, bm, si[r]);
+                }
+                vr = fma(tr[r], sr[r], vr);
+                vr = fma(ti[r], si[r], vr);
+                vi = fma(ti[r], sr[r], vi);
+                vi = fma(-tr[r], si[r], vi);
+            }
+            const bool lo = b < 8;
+            const double keep = lo ? vr : vi, give = lo ? vi : vr;
+            const double tot = half_row_sum(keep + rotn_f64<8>(give));  // lanes 0..7: Re, lanes 8..15: Im
+            const double oth = rotn_f64<8>(tot);
+            const double wr = (lo ? tot : oth) * wv, wi_ = (lo ? oth : tot) * wv;  // value x swgt (0 past the row's slice)
+            double pr[NJ], pim[NJ];
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) {
+                pr[r] = wr * sr[r] - wi_ * si[r];
+                pim[r] = wr * si[r] + wi_ * sr[r];
+            }
+            const int blk = valid ? (((lu - du) << 8) | c0c) : cur;
+            if (blk != cur) {
+                if (cur >= 0) flush();
+                cur = blk;
+            }
+#pragma unroll
+            for (int r = 0; r < NJ; ++r) asm volatile("s_nop 1" : "+v"(ks[r]));
+            hess_frame_steps<FP, NJ, 0>(ks, pr, pim, fre, fim);
+        }
+        j = jn;
+        z = nz;
+        key = nkey;
+        wv = nwv;
+#pragma unroll
+        for (int k = 0; k < NJ; ++k) cwv[k] = ncw[k];
+    }
+    if (cur >= 0) flush();
+    __syncthreads();
+    blk_tile_to_grid<W, 1, LS, 256>(ga, wi, lds, bu, bv, gout);
 }
 
 }  // namespace pfbhip

@@ -1,5 +1,5 @@
 // gridder_wd.hip -- the one-plane w-scheme's scatter / gather (gridder_kernels_wd.hpp) in a translation unit of its own:
-// 13 kernel supports x 3 term counts x 2 kernels compile next to gridder.hip, not behind it.
+// 13 kernel supports x 3 term counts x 3 kernels (scatter, gather, fused Hessian) compile next to gridder.hip, not behind it.
 #include "gridder_kernels_wd.hpp"
 
 #include <algorithm>
@@ -112,6 +112,42 @@ void wd_launch_degrid(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, 
         PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
         PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
 #undef PFB_CASE
+        default: throw std::runtime_error("unsupported kernel support");
+    }
+    PFB_HIP(hipGetLastError());
+}
+
+template <int W, int NJ, int BC>
+static void hess_wkb(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
+                     hipStream_t st)
+{
+    allow_dynamic_lds(reinterpret_cast<const void *>(&k_hess_wd<W, NJ, BC>), 160 * 1024);
+    hipLaunchKernelGGL((k_hess_wd<W, NJ, BC>), dim3(ga.a.nwork), dim3(256), wd_hess_lds_bytes(W), st, ga, wa, rec, swgt, gin, gout);
+}
+template <int W, int BC>
+static void hess_wb(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
+                    hipStream_t st)
+{
+    switch (wa.K) {
+        case 2: hess_wkb<W, 2, BC>(ga, wa, rec, swgt, gin, gout, st); break;
+        case 3: hess_wkb<W, 3, BC>(ga, wa, rec, swgt, gin, gout, st); break;
+        case 4: hess_wkb<W, 4, BC>(ga, wa, rec, swgt, gin, gout, st); break;
+        default: throw std::runtime_error("one-plane w-scheme: 2..4 kernel functions");
+    }
+}
+bool wd_hessian_supported(int W, int bc) { return W >= 4 && W <= 16 && (bc == 2 || bc == 4) && wd_hess_fits(W, bc) && (bc == 4 || W >= 14); }
+void wd_launch_hessian(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
+                       hipStream_t st)
+{
+    if (ga.a.nwork == 0) return;
+    if (!wd_hessian_supported(wa.W, wa.bc)) throw std::runtime_error("fused Hessian: W + block edge - 1 must be <= 16");
+    switch (wa.W) {
+#define PFB_CASE(w) case w: hess_wb<w, 4>(ga, wa, rec, swgt, gin, gout, st); break;
+        PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
+        PFB_CASE(12) PFB_CASE(13)
+#undef PFB_CASE
+        case 14: hess_wb<14, 2>(ga, wa, rec, swgt, gin, gout, st); break;
+        case 15: hess_wb<15, 2>(ga, wa, rec, swgt, gin, gout, st); break;
         default: throw std::runtime_error("unsupported kernel support");
     }
     PFB_HIP(hipGetLastError());

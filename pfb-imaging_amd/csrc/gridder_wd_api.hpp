@@ -33,5 +33,11 @@ void wd_launch_plane_values(int K, int64_t nactive, const double2 *cw, const dou
 void wd_launch_grid(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *pval, double2 *grid, hipStream_t st);
 void wd_launch_degrid(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *grid, double2 *sacc,
                       const double *swgt, double2 *pval_out, hipStream_t st);
+// Hessian applies of coloured plans: one colour launch of the fused gather + weighted scatter (k_hess_wd), reading plane gin
+// and adding into plane gout (cleared; a different buffer).  Built where the frame W + bc - 1 fits 16 lanes: W = 4..13 with
+// bc = 4, W = 14, 15 with bc = 2; other plans keep the scatter / gather pair.
+bool wd_hessian_supported(int W, int bc);
+void wd_launch_hessian(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
+                       hipStream_t st);
 
 }  // namespace pfbhip
