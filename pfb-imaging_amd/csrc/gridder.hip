@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "devcg.hpp"
+#include "dispatch.hpp"
 #include "eskernel.hpp"
 #include "gridder_kernels_mp.hpp"
 #include "gridder_wd_api.hpp"
@@ -454,6 +455,10 @@ __global__ void k_narrow_f64(int64_t n, const double *__restrict__ in, float *__
     if (i < n) out[i] = float(in[i]);
 }
 
+// stage indices of the profile, in the order of _lib.STAGE_NAMES
+enum Stage { ST_GRID, ST_DEGRID, ST_FFT_ROWS, ST_PAD, ST_CROP, ST_OTHER, ST_FFT_CROP, ST_PAD_FFT, ST_COUNT };
+static_assert(ST_COUNT == PFBHIP_NSTAGES, "stage list");
+
 struct StageTimer {
     bool enabled = false;
     hipStream_t stream = nullptr;
@@ -511,6 +516,35 @@ struct StageTimer {
     }
 };
 
+// Which kernels and transforms a plan runs.  Decided in three steps of create_impl (sort_key_sub before the sort,
+// choose_kernels after the work lists, choose_transforms after the row-FFT plans), read-only afterwards, and reported as
+// info.scatter_mode / scatter_launches / scatter_block / fft_mode (report_path).
+enum class Scatter { Walk, Block, Rec, OnePlane };   // k_grid_mp, k_grid_blk, k_grid_rec, k_grid_wd
+enum class Gather { Walk, RowWalk, OnePlane };       // k_degrid_mp, k_degrid_rw, k_degrid_wd
+enum class FirstAxis { RocFFT, Rows, Transposing };  // rocFFT rows of A; rowfft_plain + k_a2b / k_b2a; rowfft_a2b / rowfft_b2a
+enum class SecondAxis { RocFFT, Rows, Fused };       // rocFFT rows of B; rowfft_plain + k_crop_screen_T / k_pad_screen_T; fused_*
+struct PlanPath {
+    Scatter scatter = Scatter::Walk;
+    Gather gather = Gather::Walk;
+    int bc = BLK_CELLS;          // block edge of the register-footprint scatters' frame (2: the sort key carries 2 x 2-cell blocks)
+    bool coloured = false;       // four launches per pass, one per tile colour (plain read-add-write tile flush); else one launch
+    bool gather_values = false;  // Hessian applies: the gather's epilogue writes the scatter's values (k_grid_rec, one-plane scatter)
+    bool hess_fused = false;     // one-plane Hessian applies: k_hess_wd per colour instead of the gather and the scatter
+    bool side_clear = false;     // Hessian applies clear the scatter's planes (d_grid2) on a side stream
+    FirstAxis axis1 = FirstAxis::RocFFT;
+    SecondAxis axis2 = SecondAxis::RocFFT;
+};
+
+// What one call runs beyond its plan's path: built by every entry point, passed down the pipeline.  Only Hessian applies
+// (apply_op) set more than the output buffer.
+enum class SideClear { None, Pending, Done };  // Pending: to be issued during the degrid half; Done: issued (ev_clear)
+struct ApplyState {
+    double2 *out;                    // plane buffer the scatter writes: d_grid, or d_grid2 once the side-stream clear is waited for
+    bool gather_values = false;      // the gather writes the scatter's values into d_pval (no sacc, no scaling pass)
+    bool hess_fused = false;         // no gather launch: the scatter half's launches gather from d_grid themselves (k_hess_wd)
+    SideClear side = SideClear::None;
+};
+
 }  // namespace pfbhip
 
 using namespace pfbhip;
@@ -536,7 +570,7 @@ struct pfbhip_gridder {
     // counts are odd -- the periodic wrap would put two tiles of one colour next to each other -- then one slice, all shared)
     DevBuf<WorkItem> d_work_col;
     std::vector<size_t> col_off, col_cnt;  // [group * 4 + colour]
-    bool coloured = false;
+    PlanPath path;
     // scratch
     DevBuf<double2> d_grid, d_sval, d_sacc, d_vis;
     // Hessian applies clear the scatter's planes on a side stream while the degrid half runs: a second plane buffer
@@ -547,11 +581,9 @@ struct pfbhip_gridder {
     // moves a third of the bytes when the uv coverage is a disc (C2: 0.9 of 2.4 GB).
     DevBuf<int4> d_clear_rects;
     DevBuf<int4> d_colruns;  // per tile row: the column runs in use (transposing first-axis FFT: RunLoad / RunStore)
-    int n_clear_rects = 0;
-    double2 *grid_cur = nullptr;  // the plane buffer the pipeline stages work on (d_grid unless a Hessian switched it)
+    int n_clear_rects = 0;  // (> 0 only with the transposing first-axis transform)
     hipStream_t clear_stream = nullptr;
     hipEvent_t ev_clear = nullptr, ev_start = nullptr;
-    bool async_clear = false, planes_cleared = false, side_clear_pending = false, side_clear_done = false;
     DevBuf<double> d_wgt, d_swgt, d_img, d_img2, d_beam;
     DevBuf<char> d_fftwork;
     DevBuf<double2> d_gridB;  // (ny, nu) transposed / cropped plane
@@ -561,7 +593,6 @@ struct pfbhip_gridder {
     // ordered so that the 8 rows of a 128-byte line of B run on one XCD at about the same time (PFBHIP_TFFT=0: the
     // separate k_a2b / k_b2a passes)
     DevBuf<int> d_rowmap;
-    bool tfft = false;
     bool weights_bound = false;
     struct RowSpan {
         int64_t row0, nrows;                      // occupied rows [row0, row0 + nrows) of A
@@ -572,7 +603,6 @@ struct pfbhip_gridder {
     int kp_max = 1;              // planes scattered / gathered per pass (LDS holds kp_max tiles)
     RowFFT rowfft_u;             // hand-written row FFT of length nu with fused pad / crop (if nu is supported)
     RowFFT rowfft_v;             // hand-written row FFT of length nv for the occupied rows of A (if nv is supported)
-    bool fused = false;
     size_t bstride = 0;          // complex elements per plane of d_gridB
     size_t plane_stride = 0;     // complex elements per plane of d_grid
     rocfft_plan fftB_fwd = nullptr, fftB_bwd = nullptr;  // ny rows of length nu
@@ -628,13 +658,13 @@ struct pfbhip_gridder {
         return a;
     }
 
-    // batched row transforms of the occupied rows of A (length nv)
-    void fft_rows_A(bool forward, int k = 0)
+    // batched row transforms of the occupied rows of plane k of `planes` (length nv)
+    void fft_rows_A(double2 *planes, bool forward, int k = 0)
     {
-        timer.begin(2);
+        timer.begin(ST_FFT_ROWS);
         for (auto &sp : spans) {
-            double2 *rows = grid_cur + size_t(k) * plane_stride + size_t(sp.row0) * size_t(geom.apitch);
-            if (rowfft_v.ok) {
+            double2 *rows = planes + size_t(k) * plane_stride + size_t(sp.row0) * size_t(geom.apitch);
+            if (path.axis1 == FirstAxis::Rows) {
                 rowfft_plain(rowfft_v.pl, rows, int(sp.nrows), !forward, stream, size_t(geom.apitch));
             } else {
                 void *buf[1] = {rows};
@@ -646,8 +676,8 @@ struct pfbhip_gridder {
     // ny row transforms of B (length nu)
     void fft_rows_B(bool forward)
     {
-        timer.begin(2);
-        if (rowfft_u.ok) {  // unfused second axis on the hand-written FFT (doubled shapes, PFBHIP_FUSED_FFT=0 + PFBHIP_ROWFFT=1)
+        timer.begin(ST_FFT_ROWS);
+        if (path.axis2 == SecondAxis::Rows) {  // unfused second axis on the hand-written FFT (doubled shapes, PFBHIP_FUSED_FFT=0 + PFBHIP_ROWFFT=1)
             rowfft_plain(rowfft_u.pl, d_gridB.p, int(prm.ny), !forward, stream);
         } else {
             void *buf[1] = {d_gridB.p};
@@ -683,84 +713,44 @@ struct pfbhip_gridder {
         return (size_t(2) * KP_MAX * tile_rows(W) * tile_stride(W) + size_t(W) * (D + 1)) * sizeof(double);
     }
     template <int W, int KP>
-    void launch_grid_mp_wk(const GroupArgs &ga, const double2 *sval)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_mp<W, KP>), int(lds_bytes_mp_max<W>()));
-        hipLaunchKernelGGL((k_grid_mp<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds_bytes_mp<W>(), stream, ga, sval,
-                           grid_cur);
-    }
-    template <int W, int KP>
     size_t lds_bytes_blk() const
     {
         return (size_t(2) * KP * blk_tile_rows(W) * blk_stride(W, KP) + blk_fixed_doubles(W, blk_threads(kp_max) / 64)) * sizeof(double);
     }
-    template <int W, int KP, int BC>
-    void launch_grid_blk_wkb(const GroupArgs &ga, const double2 *sval)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_blk<W, KP, BC>), 160 * 1024);
-        const size_t lds = lds_bytes_blk<W, KP>();
-        PFB_REQUIRE(lds <= size_t(160) * 1024, "block scatter needs %zu bytes of LDS", lds);
-        hipLaunchKernelGGL((k_grid_blk<W, KP, BC>), dim3(ga.a.nwork), dim3(blk_threads(kp_max)), lds, stream, ga, sval, grid_cur);
-    }
-    template <int W, int KP>
-    void launch_grid_blk_wk(const GroupArgs &ga, const double2 *sval)
-    {
-        // (block edge 2: W = 14, 15 on a sort key that carries the 2 x 2-cell blocks -- the 16 x 16-cell frame, see k_grid_blk)
-        if constexpr (W == 14 || W == 15) {
-            if (wd_bc == 2) return launch_grid_blk_wkb<W, KP, 2>(ga, sval);
-        }
-        launch_grid_blk_wkb<W, KP, 4>(ga, sval);
-    }
-    bool scatter_blk = true;  // register-footprint scatter (k_grid_blk); PFBHIP_SCATTER=walk selects k_grid_mp
-    // record-driven register-footprint scatter (k_grid_rec): single-pass plans without ES-kernel w-planes
-    // (PFBHIP_SCATTER=block keeps k_grid_blk).  d_rec: static per-visibility records; d_pval: the plane-weighted values
-    // of the current apply (kp_max per visibility), written by the gather inside a Hessian apply (pval_ready) or by
-    // k_plane_values in front of the scatter
-    bool scatter_rec = false, pval_ready = false, want_pval = false;
+    // record-driven register-footprint scatter (k_grid_rec) and one-plane scatter: d_rec, static per-visibility records; d_pval,
+    // the plane-weighted values of the current apply (kp_max, or wd.K, per visibility), written by the gather inside a Hessian
+    // apply (ApplyState::gather_values) or by k_plane_values* in front of the scatter
     // one-plane w-scheme (info.wmode == 2, gridder_wd_api.hpp): K kernel functions per axis, their derivative tables, the K
-    // complex coefficients of every sorted visibility; d_pval then holds K values per visibility
+    // complex coefficients of every sorted visibility
     WdArgs wd{};
-    int wd_bc = 4;  // block edge of the register-footprint scatters' frame (2: the sort key carries 2 x 2-cell blocks; W = 14, 15)
     DevBuf<double> d_dtab;
     DevBuf<double2> d_cw;
-    bool wd_small = false;  // few work items: one scatter launch with the atomic tile flush instead of four colour launches
-    int pval_per_vis() const { return info.wmode == 2 ? wd.K : kp_max; }
-    bool pval_from_gather = false;  // single-pass plans: the gather's epilogue writes the scatter's values inside a Hessian apply
-    // one-plane coloured plans (wd_hessian_supported): a Hessian apply runs k_hess_wd per colour instead of the gather and the
-    // four scatter launches (hess_fused: inside such an apply)
-    bool hess_fused_ok = false, hess_fused = false;
     DevBuf<VisRec> d_rec;
-    // row-walk gather (k_degrid_rw): same plans as the record scatter; d_kw: plane weights of every visibility (plan time)
-    bool gather_rw = false;
+    // row-walk gather (k_degrid_rw): d_kw, plane weights of every visibility (plan time)
     DevBuf<double> d_kw;
     float wshare[3] = {1.3f / 3, 1.f / 3, 0.7f / 3};  // see GroupArgs::wshare: measured optimum on C2 (equal shares: +7 % scatter time)
     DevBuf<double2> d_pval;
-    template <int W, int KP, int BC>
-    void launch_grid_rec_wkb(const GroupArgs &ga)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_rec<W, KP, BC>), 160 * 1024);
-        const size_t lds = lds_bytes_blk<W, KP>();
-        PFB_REQUIRE(lds <= size_t(160) * 1024, "record scatter needs %zu bytes of LDS", lds);
-        hipLaunchKernelGGL((k_grid_rec<W, KP, BC>), dim3(ga.a.nwork), dim3(blk_threads(kp_max)), lds, stream, ga, d_rec.p, d_pval.p,
-                           grid_cur);
-    }
-    template <int W, int KP>
-    void launch_grid_rec_wk(const GroupArgs &ga)
-    {
-        if constexpr (W == 14 || W == 15) {
-            if (wd_bc == 2) return launch_grid_rec_wkb<W, KP, 2>(ga);
-        }
-        launch_grid_rec_wkb<W, KP, 4>(ga);
-    }
-    template <int W>
-    void launch_grid_mp_w(int plane0, int kp, const double2 *sval)
+
+    // the scatter of planes [plane0, plane0 + kp) of sval into a.out: one launch, or one per tile colour (see blk_tile_to_grid)
+    void launch_grid(const ApplyState &a, int plane0, int kp, const double2 *sval)
     {
         GroupArgs ga = group_args(plane0, kp);
         if (ga.a.nwork == 0) return;
-        if (scatter_blk) {
-            const size_t grp = work_off.size() > 1 ? size_t(plane0 / kp_max) : 0;
-            if (scatter_rec && !pval_ready) {
-                timer.begin(5);
+        with_W(int(info.W), [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            if (path.scatter == Scatter::Walk) {
+                timer.begin(ST_GRID);
+                with_KP(kp, [&](auto k) {
+                    constexpr int KP = decltype(k)::value;
+                    allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_mp<W, KP>), int(lds_bytes_mp_max<W>()));
+                    hipLaunchKernelGGL((k_grid_mp<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds_bytes_mp<W>(), stream, ga, sval, a.out);
+                });
+                timer.end();
+                return;
+            }
+            const bool from_values = path.scatter == Scatter::Rec || path.scatter == Scatter::OnePlane;
+            if (from_values && !a.gather_values && !a.hess_fused) {
+                timer.begin(ST_OTHER);
                 if (info.wmode == 2)
                     wd_launch_plane_values(wd.K, info.nactive, d_cw.p, sval, d_pval.p, stream);
                 else if (prm.do_wgridding && info.wmode == 0)
@@ -770,182 +760,132 @@ struct pfbhip_gridder {
                                        info.nactive, sval, d_pval.p);
                 timer.end();
             }
-            for (int col = 0; col < 4; ++col) {  // one launch per tile colour (see blk_tile_to_grid)
+            const size_t grp = work_off.size() > 1 ? size_t(plane0 / kp_max) : 0;
+            for (int col = 0; col < 4; ++col) {
                 ga.a.work = d_work_col.p + col_off[grp * 4 + size_t(col)];
                 ga.a.nwork = uint32_t(col_cnt[grp * 4 + size_t(col)]);
                 if (ga.a.nwork == 0) continue;
-                timer.begin(0);
-                if (info.wmode == 2) {
-                    if (hess_fused)  // (the gather's plane is d_grid, the output grid_cur = d_grid2)
-                        wd_launch_hessian(ga, wd, d_rec.p, d_swgt.p, d_grid.p, grid_cur, stream);
+                timer.begin(ST_GRID);
+                if (path.scatter == Scatter::OnePlane) {
+                    if (a.hess_fused)  // (the gather's plane is d_grid, the output a.out = d_grid2)
+                        wd_launch_hessian(ga, wd, d_rec.p, d_swgt.p, d_grid.p, a.out, stream);
                     else
-                        wd_launch_grid(ga, wd, d_rec.p, d_pval.p, grid_cur, stream);
-                    timer.end();
-                    continue;
-                }
-                if (scatter_rec) {
-                    switch (kp) {
-                        case 1: launch_grid_rec_wk<W, 1>(ga); break;
-                        case 2: launch_grid_rec_wk<W, 2>(ga); break;
-                        case 3: launch_grid_rec_wk<W, 3>(ga); break;
-                        default: launch_grid_rec_wk<W, 4>(ga); break;
-                    }
-                    timer.end();
-                    continue;
-                }
-                switch (kp) {
-                    case 1: launch_grid_blk_wk<W, 1>(ga, sval); break;
-                    case 2: launch_grid_blk_wk<W, 2>(ga, sval); break;
-                    case 3: launch_grid_blk_wk<W, 3>(ga, sval); break;
-                    default: launch_grid_blk_wk<W, 4>(ga, sval); break;
+                        wd_launch_grid(ga, wd, d_rec.p, d_pval.p, a.out, stream);
+                } else {
+                    with_KP(kp, [&](auto k) {
+                        with_BC<W>(path.bc, [&](auto bc) {
+                            constexpr int KP = decltype(k)::value, BC = decltype(bc)::value;
+                            const size_t lds = lds_bytes_blk<W, KP>();
+                            const dim3 grid(ga.a.nwork), block(blk_threads(kp_max));
+                            if (path.scatter == Scatter::Rec) {
+                                allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_rec<W, KP, BC>), 160 * 1024);
+                                PFB_REQUIRE(lds <= size_t(160) * 1024, "record scatter needs %zu bytes of LDS", lds);
+                                hipLaunchKernelGGL((k_grid_rec<W, KP, BC>), grid, block, lds, stream, ga, d_rec.p, d_pval.p, a.out);
+                            } else {
+                                allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_blk<W, KP, BC>), 160 * 1024);
+                                PFB_REQUIRE(lds <= size_t(160) * 1024, "block scatter needs %zu bytes of LDS", lds);
+                                hipLaunchKernelGGL((k_grid_blk<W, KP, BC>), grid, block, lds, stream, ga, sval, a.out);
+                            }
+                        });
+                    });
                 }
                 timer.end();
             }
-            return;
-        }
-        timer.begin(0);
-        switch (kp) {
-            case 1: launch_grid_mp_wk<W, 1>(ga, sval); break;
-            case 2: launch_grid_mp_wk<W, 2>(ga, sval); break;
-            case 3: launch_grid_mp_wk<W, 3>(ga, sval); break;
-            default: launch_grid_mp_wk<W, 4>(ga, sval); break;
-        }
-        timer.end();
+        });
     }
-    template <int W, int KP>
-    void launch_degrid_mp_wk(const GroupArgs &ga, double2 *sacc)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_mp<W, KP>), int(lds_bytes_mp_max<W>()));
-        hipLaunchKernelGGL((k_degrid_mp<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds_bytes_mp<W>(), stream, ga,
-                           grid_cur, sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr);
-    }
-    template <int W, int KP>
-    void launch_degrid_rw_wk(const GroupArgs &ga, double2 *sacc)
-    {
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_rw<W, KP>), 160 * 1024);
-        const size_t lds = size_t(KP) * RW_LS * RW_LS * sizeof(double2);
-        hipLaunchKernelGGL((k_degrid_rw<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds, stream, ga, d_rec.p, d_kw.p, grid_cur,
-                           sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr);
-    }
-    template <int W>
-    void launch_degrid_mp_w(int plane0, int kp, double2 *sacc)
+    // the gather of planes [plane0, plane0 + kp) of d_grid into sacc (or, with a.gather_values, the scatter's values into d_pval)
+    void launch_degrid(const ApplyState &a, int plane0, int kp, double2 *sacc)
     {
         GroupArgs ga = group_args(plane0, kp);
         if (ga.a.nwork == 0) return;
-        if (info.wmode == 2) {
-            wd_launch_degrid(ga, wd, d_rec.p, grid_cur, sacc, want_pval ? d_swgt.p : nullptr, want_pval ? d_pval.p : nullptr, stream);
-            return;
-        }
-        if (gather_rw) {
-            switch (kp) {
-                case 1: launch_degrid_rw_wk<W, 1>(ga, sacc); break;
-                case 2: launch_degrid_rw_wk<W, 2>(ga, sacc); break;
-                case 3: launch_degrid_rw_wk<W, 3>(ga, sacc); break;
-                default: launch_degrid_rw_wk<W, 4>(ga, sacc); break;
-            }
-            return;
-        }
-        switch (kp) {
-            case 1: launch_degrid_mp_wk<W, 1>(ga, sacc); break;
-            case 2: launch_degrid_mp_wk<W, 2>(ga, sacc); break;
-            case 3: launch_degrid_mp_wk<W, 3>(ga, sacc); break;
-            default: launch_degrid_mp_wk<W, 4>(ga, sacc); break;
-        }
-    }
-#define PFB_W_DISPATCH(fn, ...)                                          \
-    switch (info.W) {                                                    \
-        case 4: fn<4>(__VA_ARGS__); break;                               \
-        case 5: fn<5>(__VA_ARGS__); break;                               \
-        case 6: fn<6>(__VA_ARGS__); break;                               \
-        case 7: fn<7>(__VA_ARGS__); break;                               \
-        case 8: fn<8>(__VA_ARGS__); break;                               \
-        case 9: fn<9>(__VA_ARGS__); break;                               \
-        case 10: fn<10>(__VA_ARGS__); break;                             \
-        case 11: fn<11>(__VA_ARGS__); break;                             \
-        case 12: fn<12>(__VA_ARGS__); break;                             \
-        case 13: fn<13>(__VA_ARGS__); break;                             \
-        case 14: fn<14>(__VA_ARGS__); break;                             \
-        case 15: fn<15>(__VA_ARGS__); break;                             \
-        case 16: fn<16>(__VA_ARGS__); break;                             \
-        default: throw std::runtime_error("unsupported kernel support"); \
+        const double *swgt = a.gather_values ? d_swgt.p : nullptr;
+        double2 *pval = a.gather_values ? d_pval.p : nullptr;
+        with_W(int(info.W), [&](auto w) {
+            if (path.gather == Gather::OnePlane) return wd_launch_degrid(ga, wd, d_rec.p, d_grid.p, sacc, swgt, pval, stream);
+            with_KP(kp, [&](auto k) {
+                constexpr int W = decltype(w)::value, KP = decltype(k)::value;
+                if (path.gather == Gather::RowWalk) {
+                    allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_rw<W, KP>), 160 * 1024);
+                    const size_t lds = size_t(KP) * RW_LS * RW_LS * sizeof(double2);
+                    hipLaunchKernelGGL((k_degrid_rw<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds, stream, ga, d_rec.p, d_kw.p, d_grid.p,
+                                       sacc, swgt, pval);
+                } else {
+                    allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_mp<W, KP>), int(lds_bytes_mp_max<W>()));
+                    hipLaunchKernelGGL((k_degrid_mp<W, KP>), dim3(ga.a.nwork), dim3(MP_THREADS), lds_bytes_mp<W>(), stream, ga, d_grid.p,
+                                       sacc, swgt, pval);
+                }
+            });
+        });
     }
 
     dim3 tgrid(int64_t ncols, int64_t nrows) const { return dim3(uint32_t(ceil_div(ncols, TP)), uint32_t(ceil_div(nrows, TP))); }
 
     // Clear the second plane buffer on the side stream, starting when this stream reaches the present point (which also
     // means the previous apply's scatter half, the buffer's last user, has finished).
-    void side_clear()
+    void side_clear(ApplyState &a)
     {
         PFB_HIP(hipEventRecord(ev_start, stream));
         PFB_HIP(hipStreamWaitEvent(clear_stream, ev_start, 0));
-        if (n_clear_rects > 0) {
-            hipLaunchKernelGGL(k_clear_rects, dim3(uint32_t(n_clear_rects), uint32_t(info.nplanes)), dim3(256), 0, clear_stream,
-                               d_clear_rects.p, d_grid2.p, plane_stride, geom.apitch);
-            PFB_HIP(hipGetLastError());
-        } else {
-            double2 *keep = grid_cur;
-            grid_cur = d_grid2.p;
-            clear_planes(int(info.nplanes), clear_stream);
-            grid_cur = keep;
-        }
+        clear_planes(d_grid2.p, int(info.nplanes), clear_stream);
         PFB_HIP(hipEventRecord(ev_clear, clear_stream));
-        side_clear_pending = false;
-        side_clear_done = true;
+        a.side = SideClear::Done;
     }
 
-    // zero the occupied rows of the first kp planes of the active plane buffer -- or, where the first-axis transform reads
-    // column runs only (tfft), just the rectangles the scatter can touch (multi-pass plans: every pass clears its planes)
-    void clear_planes(int kp, hipStream_t st)
+    // zero the occupied rows of the first kp planes of `planes` -- or, where the first-axis transform reads column runs only
+    // (FirstAxis::Transposing: n_clear_rects > 0), just the rectangles the scatter can touch (multi-pass plans: every pass
+    // clears its planes)
+    void clear_planes(double2 *planes, int kp, hipStream_t st)
     {
-        if (n_clear_rects > 0 && tfft) {
-            hipLaunchKernelGGL(k_clear_rects, dim3(uint32_t(n_clear_rects), uint32_t(kp)), dim3(256), 0, st, d_clear_rects.p, grid_cur,
+        if (n_clear_rects > 0) {
+            hipLaunchKernelGGL(k_clear_rects, dim3(uint32_t(n_clear_rects), uint32_t(kp)), dim3(256), 0, st, d_clear_rects.p, planes,
                                plane_stride, geom.apitch);
             PFB_HIP(hipGetLastError());
             return;
         }
         for (int k = 0; k < kp; ++k)
             for (auto &sp : spans)
-                PFB_HIP(hipMemsetAsync(grid_cur + size_t(k) * plane_stride + size_t(sp.row0) * size_t(geom.apitch), 0,
+                PFB_HIP(hipMemsetAsync(planes + size_t(k) * plane_stride + size_t(sp.row0) * size_t(geom.apitch), 0,
                                        size_t(sp.nrows) * size_t(geom.apitch) * sizeof(double2), st));
     }
 
     // sval (tile-sorted, weighted) -> accT, the TRANSPOSED (ny, nx) raw image (before correction)
     // `fin` (fused path only): the last launch writes the finalized image; returns true if it did
-    bool grid_all_planes(const double2 *sval, const FusedFinal *fin = nullptr)
+    bool grid_all_planes(const ApplyState &a, const double2 *sval, const FusedFinal *fin = nullptr)
     {
         const int64_t npix = int64_t(prm.nx) * prm.ny;
         if (info.nactive == 0 || info.nwork == 0) {
             PFB_HIP(hipMemsetAsync(d_accT.p, 0, npix * sizeof(double), stream));
             return false;
         }
+        const bool fused = path.axis2 == SecondAxis::Fused, tfft = path.axis1 == FirstAxis::Transposing;
         bool finalized = false;
         for (int p0 = 0; p0 < info.nplanes; p0 += kp_max) {
             const int kp = int(std::min<int64_t>(kp_max, info.nplanes - p0));
-            if (!planes_cleared) {  // (a Hessian apply may have cleared them on the side stream already)
-                timer.begin(5);
-                clear_planes(kp, stream);
+            if (a.side != SideClear::Done) {  // (a Hessian apply has cleared them on the side stream)
+                timer.begin(ST_OTHER);
+                clear_planes(a.out, kp, stream);
                 timer.end();
             }
-            PFB_W_DISPATCH(launch_grid_mp_w, p0, kp, sval);  // stage 0, timed per kernel launch inside
+            launch_grid(a, p0, kp, sval);  // ST_GRID, timed per kernel launch inside
             PFB_HIP(hipGetLastError());
             if (tfft) {  // every plane of the pass in one launch
-                timer.begin(2);
-                rowfft_a2b(rowfft_v.pl, grid_cur, d_gridB.p, d_rowmap.p, int(occ_rows), geom.bpitch, int(prm.ny), size_t(geom.apitch),
+                timer.begin(ST_FFT_ROWS);
+                rowfft_a2b(rowfft_v.pl, a.out, d_gridB.p, d_rowmap.p, int(occ_rows), geom.bpitch, int(prm.ny), size_t(geom.apitch),
                            kp, plane_stride, bstride, d_colruns.p, stream);
                 timer.end();
             }
             for (int k = 0; k < kp && !tfft; ++k) {
                 const int p = p0 + k;
-                fft_rows_A(false, k);
-                timer.begin(4);
+                fft_rows_A(a.out, false, k);
+                timer.begin(ST_CROP);
                 hipLaunchKernelGGL(k_a2b, tgrid(info.nu, prm.ny), dim3(TP, TRANSPOSE_ROWS), 0, stream, geom, d_occ.p,
-                                   grid_cur + size_t(k) * plane_stride, d_gridB.p + (fused ? size_t(k) * bstride : 0),
+                                   a.out + size_t(k) * plane_stride, d_gridB.p + (fused ? size_t(k) * bstride : 0),
                                    fused ? 0 : 1);
                 PFB_HIP(hipGetLastError());
                 timer.end();
                 if (!fused) {
                     fft_rows_B(false);
-                    timer.begin(4);
+                    timer.begin(ST_CROP);
                     hipLaunchKernelGGL(k_crop_screen_T, dim3(uint32_t(ceil_div(prm.nx, 256)), uint32_t(prm.ny)),
                                        dim3(256), 0, stream, geom, fgeom, d_gridB.p, prm.do_wgridding, wplanes[size_t(p)],
                                        p == 0 ? 1 : 0, d_accT.p);
@@ -954,7 +894,7 @@ struct pfbhip_gridder {
                 }
             }
             if (fused) {
-                timer.begin(6);
+                timer.begin(ST_FFT_CROP);
                 const bool last_group = p0 + kp >= info.nplanes;
                 FusedFinal f = (fin != nullptr && last_group) ? *fin : FusedFinal{};
                 if (f.corr != nullptr) finalized = true;
@@ -966,7 +906,8 @@ struct pfbhip_gridder {
         return finalized;
     }
     // grid + finalize, folding the finalize into the last fused launch where possible
-    void grid_and_finalize(const double2 *sval, const double *beam, double scale, double eta, const double *x, double *out)
+    void grid_and_finalize(const ApplyState &a, const double2 *sval, const double *beam, double scale, double eta, const double *x,
+                           double *out)
     {
         FusedFinal f;
         f.corr = d_corr.p;
@@ -975,7 +916,7 @@ struct pfbhip_gridder {
         f.scale = scale;
         f.eta = eta;
         f.out = out;
-        if (!grid_all_planes(sval, fused ? &f : nullptr)) finalize(beam, scale, eta, x, out);
+        if (!grid_all_planes(a, sval, path.axis2 == SecondAxis::Fused ? &f : nullptr)) finalize(beam, scale, eta, x, out);
     }
 
     FusedGeom fgeom;  // filled once by create_impl (fused path)
@@ -996,7 +937,7 @@ struct pfbhip_gridder {
     void finalize(const double *beam, double scale, double eta, const double *x, double *out)
     {
         const int64_t npix = int64_t(prm.nx) * prm.ny;
-        timer.begin(5);
+        timer.begin(ST_OTHER);
         hipLaunchKernelGGL(k_finalize_img, dim3(uint32_t(ceil_div(npix, 256))), dim3(256), 0, stream, d_accT.p, d_corr.p, beam, scale,
                            eta, x, npix, out);
         PFB_HIP(hipGetLastError());
@@ -1007,7 +948,7 @@ struct pfbhip_gridder {
     void prepare_degrid_input(const double *x, const double *beam)
     {
         const int64_t npix = int64_t(prm.nx) * prm.ny;
-        timer.begin(5);
+        timer.begin(ST_OTHER);
         hipLaunchKernelGGL(k_prepare_img, dim3(uint32_t(ceil_div(npix, 256))), dim3(256), 0, stream, x, d_corr.p, beam, npix,
                            d_accT.p);
         PFB_HIP(hipGetLastError());
@@ -1015,7 +956,7 @@ struct pfbhip_gridder {
     }
 
     // x -> sacc, folding the x * corr * beam step into the fused pad kernel where possible
-    void prepare_and_degrid(const double *x, const double *beam, double2 *sacc)
+    void prepare_and_degrid(ApplyState &a, const double *x, const double *beam, double2 *sacc)
     {
         // The side-stream clear of the scatter's planes starts with the apply, under the degridding side's row transforms (round
         // 4b; before that: in front of the gather).  The gather's workgroups fill every CU's registers (three
@@ -1023,43 +964,44 @@ struct pfbhip_gridder {
         // the scatter; the fused row-FFT kernels leave room.  C2: degrid 1.647 -> 1.594 ms, pad_fft + 0.01, apply 5.91 -> 5.86 ms.
         // (one plane only: with the three planes of the polynomial scheme the clear's 0.9 GB cost pad_fft what they save the gather,
         // 9.73 against 9.77 ms)
-        if (side_clear_pending && info.nplanes == 1) side_clear();
-        if (fused && info.nactive != 0 && info.nwork != 0 && fused_pad_takes_prep(rowfft_u, fgeom)) {
+        if (a.side == SideClear::Pending && info.nplanes == 1) side_clear(a);
+        if (path.axis2 == SecondAxis::Fused && info.nactive != 0 && info.nwork != 0 && fused_pad_takes_prep(rowfft_u, fgeom)) {
             FusedPrep p;
             p.x = x;
             p.corr = d_corr.p;
             p.beam = beam;
-            degrid_all_planes(sacc, &p);
+            degrid_all_planes(a, sacc, &p);
         } else {
             prepare_degrid_input(x, beam);
-            degrid_all_planes(sacc);
+            degrid_all_planes(a, sacc);
         }
     }
 
     // accT (transposed, corrected image) -> sacc (tile-sorted)
     // `prep` (fused path only): the fused pad kernel reads x * corr [* beam] itself instead of a prepared accT
-    void degrid_all_planes(double2 *sacc, const FusedPrep *prep = nullptr)
+    void degrid_all_planes(ApplyState &a, double2 *sacc, const FusedPrep *prep = nullptr)
     {
-        if (!want_pval && !hess_fused) PFB_HIP(hipMemsetAsync(sacc, 0, size_t(std::max<int64_t>(info.nactive, 1)) * sizeof(double2), stream));
+        if (!a.gather_values && !a.hess_fused) PFB_HIP(hipMemsetAsync(sacc, 0, size_t(std::max<int64_t>(info.nactive, 1)) * sizeof(double2), stream));
         if (info.nactive == 0 || info.nwork == 0) return;
+        const bool fused = path.axis2 == SecondAxis::Fused, tfft = path.axis1 == FirstAxis::Transposing;
         for (int p0 = 0; p0 < info.nplanes; p0 += kp_max) {
             const int kp = int(std::min<int64_t>(kp_max, info.nplanes - p0));
             if (fused) {
-                timer.begin(7);
+                timer.begin(ST_PAD_FFT);
                 fused_pad_fft(rowfft_u, fused_geom(), d_occ.p, d_accT.p, prep != nullptr ? *prep : FusedPrep{},
                               fused_planes(p0, kp), prm.do_wgridding, d_gridB.p, bstride, stream);
                 timer.end();
             }
             if (tfft) {
-                timer.begin(2);
-                rowfft_b2a(rowfft_v.pl, d_gridB.p, grid_cur, d_rowmap.p, int(occ_rows), geom.bpitch, int(prm.ny), size_t(geom.apitch),
+                timer.begin(ST_FFT_ROWS);
+                rowfft_b2a(rowfft_v.pl, d_gridB.p, d_grid.p, d_rowmap.p, int(occ_rows), geom.bpitch, int(prm.ny), size_t(geom.apitch),
                            fgeom.tpitch, kp, plane_stride, bstride, d_colruns.p, stream);
                 timer.end();
             }
             for (int k = 0; k < kp && !tfft; ++k) {
                 const int p = p0 + k;
                 if (!fused) {
-                    timer.begin(3);
+                    timer.begin(ST_PAD);
                     hipLaunchKernelGGL(k_pad_screen_T, dim3(uint32_t(ceil_div(info.nu, 256)), uint32_t(prm.ny)),
                                        dim3(256), 0, stream, geom, fgeom, d_accT.p, prm.do_wgridding, wplanes[size_t(p)],
                                        d_gridB.p);
@@ -1067,59 +1009,57 @@ struct pfbhip_gridder {
                     timer.end();
                     fft_rows_B(true);
                 }
-                timer.begin(3);
+                timer.begin(ST_PAD);
                 hipLaunchKernelGGL(k_b2a, tgrid(info.nu, info.nv), dim3(TP, TRANSPOSE_ROWS), 0, stream, geom, d_occ.p,
-                                   d_gridB.p + (fused ? size_t(k) * bstride : 0), grid_cur + size_t(k) * plane_stride);
+                                   d_gridB.p + (fused ? size_t(k) * bstride : 0), d_grid.p + size_t(k) * plane_stride);
                 PFB_HIP(hipGetLastError());
                 timer.end();
-                fft_rows_A(true, k);
+                fft_rows_A(d_grid.p, true, k);
             }
-            if (side_clear_pending) side_clear();
-            if (hess_fused) continue;  // (the fused launches of the scatter half gather)
-            timer.begin(1);
-            PFB_W_DISPATCH(launch_degrid_mp_w, p0, kp, sacc);
+            if (a.side == SideClear::Pending) side_clear(a);
+            if (a.hess_fused) continue;  // (the fused launches of the scatter half gather)
+            timer.begin(ST_DEGRID);
+            launch_degrid(a, p0, kp, sacc);
             PFB_HIP(hipGetLastError());
             timer.end();
         }
     }
 
-    // single-precision host arrays: uploaded as they are into a staging buffer, widened on the device
+    // host <-> device transfers of n values: double as they are; float (single-precision I/O) through a staging buffer,
+    // widened / narrowed on the device (the staging buffer is reused by the next transfer: in-order on this stream)
     DevBuf<float> d_stage32;
-    void upload_f32(const float *host, size_t n, double *dst)
+    void upload(const double *host, size_t n, double *dst)
+    {
+        PFB_HIP(hipMemcpyAsync(dst, host, n * sizeof(double), hipMemcpyHostToDevice, stream));
+    }
+    void upload(const float *host, size_t n, double *dst)
     {
         d_stage32.ensure(n);
         PFB_HIP(hipMemcpyAsync(d_stage32.p, host, n * sizeof(float), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(k_widen_f32, dim3(uint32_t(ceil_div(int64_t(n), 256))), dim3(256), 0, stream, int64_t(n), d_stage32.p, dst);
         PFB_HIP(hipGetLastError());
-        // (the staging buffer is reused by the next upload: in-order on this stream)
     }
-    void download_f32(const double *src, size_t n, float *host)
+    void download(const double *src, size_t n, double *host)
+    {
+        PFB_HIP(hipMemcpyAsync(host, src, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    void download(const double *src, size_t n, float *host)
     {
         d_stage32.ensure(n);
         hipLaunchKernelGGL(k_narrow_f64, dim3(uint32_t(ceil_div(int64_t(n), 256))), dim3(256), 0, stream, int64_t(n), src, d_stage32.p);
         PFB_HIP(hipGetLastError());
         PFB_HIP(hipMemcpyAsync(host, d_stage32.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
-    void upload_vis_wgt_sp(const float *vis_host, const float *wgt_host)
+    template <class T>
+    void upload_vis_wgt(const T *vis_host, const T *wgt_host)
     {
         if (vis_host) {
             d_vis.ensure(size_t(nvis));
-            upload_f32(vis_host, size_t(nvis) * 2, reinterpret_cast<double *>(d_vis.p));
+            upload(vis_host, size_t(nvis) * 2, reinterpret_cast<double *>(d_vis.p));
         }
         if (wgt_host) {
             d_wgt.ensure(size_t(nvis));
-            upload_f32(wgt_host, size_t(nvis), d_wgt.p);
-        }
-    }
-    void upload_vis_wgt(const double *vis_host, const double *wgt_host)
-    {
-        if (vis_host) {
-            d_vis.ensure(size_t(nvis));
-            PFB_HIP(hipMemcpyAsync(d_vis.p, vis_host, size_t(nvis) * sizeof(double2), hipMemcpyHostToDevice, stream));
-        }
-        if (wgt_host) {
-            d_wgt.ensure(size_t(nvis));
-            PFB_HIP(hipMemcpyAsync(d_wgt.p, wgt_host, size_t(nvis) * sizeof(double), hipMemcpyHostToDevice, stream));
+            upload(wgt_host, size_t(nvis), d_wgt.p);
         }
     }
 };
@@ -1281,6 +1221,116 @@ static PlanSwitches read_plan_switches()
     sw.tfft = first("PFBHIP_TFFT") != '0';
     sw.wd_fused = first("PFBHIP_WD_FUSED") != '0';
     return sw;
+}
+
+// ---- the plan's path (PlanPath), step 1: sort key layout ----
+// The register-footprint scatters walk runs of visibilities whose footprint origins share a 4 x 4-cell block: the sort key carries
+// that block (key_sub 64) unless PFBHIP_SCATTER=walk or the key would not fit 32 bits.  At W = 14 / 15 the scatters' 16 x 16-cell
+// register frame is anchored on 2 x 2-cell blocks (k_grid_blk, k_grid_rec, k_grid_wd), and the key carries those as well (256);
+// PFBHIP_WD_BLOCK=4 keeps the 4 x 4 anchoring (17 / 18-cell frame on 3 x 20 lanes).  ES-plane plans whose (tile, plane, block)
+// key would not fit 32 bits (C5: 409 600 tiles x 64 planes) stay on 4 x 4 blocks.
+static int sort_key_sub(const PlanSwitches &sw, int W, int64_t nkeys)
+{
+    if (sw.scatter == ScatterForce::Walk || nkeys * 64 >= (int64_t(1) << 32) - 2) return 1;
+    const bool fine = (W == 14 || W == 15) && !sw.wd_block4 && nkeys * 256 < (int64_t(1) << 32) - 2;
+    return fine ? 256 : 64;
+}
+
+// ---- step 2: the scatter and gather kernels, once the work lists exist ----
+struct WorkShape {
+    int key_sub;           // sort_key_sub
+    size_t nwork;          // work items of all passes
+    size_t per_pass;       // mean work items per pass
+    size_t coarse_per_pass;  // mean work items per pass at CHUNK visibilities each
+    size_t grid_bytes;     // the plane buffer of one pass
+};
+static PlanPath choose_kernels(const PlanSwitches &sw, const pfbhip_gridder_params &prm, const pfbhip_gridder_info &info, int kp_max,
+                               const WorkShape &ws)
+{
+    PlanPath p;
+    p.bc = wd_block_edge(int(info.W), ws.key_sub == 256);
+    bool blk = ws.key_sub > 1;  // without the block order in the 32-bit key the runs are ~1 long: the walk kernel is cheaper
+    // Small plans (C1: ~300 work items) run faster on the single-launch walk kernel: four colour launches of a few dozen
+    // workgroups each leave most of the 256 CUs idle.  (One-plane scheme, round 4 size sweep: one launch with the atomic flush
+    // wins up to 4096^2 / 4e6 visibilities = 5 000 tiles in use, ties at 6144^2 = 11 000, loses at C2 = 20 000: 2.44 vs 2.31 ms.)
+    // The block order of the sort is kept either way (any order is valid).  (Mean over the passes: the first and last pass of an
+    // ES-plane plan hold the few visibilities at the ends of the w range -- their launches are short whichever kernel runs them.)
+    bool one_launch = false;
+    if (info.wmode == 2) {
+        PFB_REQUIRE(blk, "the one-plane w-scheme needs the block-ordered sort");
+        // (PFBHIP_WD_COLOURS=1: the four colour launches whatever the size -- tests; 0: one launch with the atomic flush)
+        one_launch = sw.wd_colours < 0 ? ws.coarse_per_pass < size_t(8192) : sw.wd_colours == 0;
+    } else if (blk && sw.scatter == ScatterForce::Auto && ws.per_pass < size_t(2048)) {
+        blk = false;
+    }
+    // colour launches need whole tile pairs on both axes: with odd tile counts the periodic wrap puts two tiles of one colour
+    // next to each other
+    p.coloured = blk && !one_launch && ceil_div(info.nu, TILE) % 2 == 0 && ceil_div(info.nv, TILE) % 2 == 0 && info.nu % TILE == 0 &&
+                 info.nv % TILE == 0;
+    const bool has_work = info.nactive > 0 && ws.nwork > 0;
+    // single-pass plans without ES-kernel w-planes: the record scatter and the row-walk gather
+    const bool rec_mode = info.nplanes <= kp_max && (!prm.do_wgridding || info.wmode >= 1) && has_work;
+    // ES-kernel plane stacks (round 3): the record scatter with the values of each pass written by k_plane_values_es in front of
+    // it, ONLY with PFBHIP_SCATTER=rec_es.  Measured (gpurun_out/r03w, r03x): 8192^2 image, 19 planes, 9.5e6 visibilities: scatter
+    // 21.2 -> 17.8 ms, + 1.4 ms of plane values (88 bytes per visibility and pass), apply 73.2 -> 70.9 ms; C5: 195 -> 190 ms,
+    // + 13 ms of plane values, apply 1035 -> 1044 ms -- there the scatter waits on the records / values of 1e8 visibilities
+    // (6 GB per pass set) whichever kernel runs.  Round 4b: with the 16 x 16-cell frame (W <= 13, or W = 14 / 15 on the finer sort key) and
+    // its paired kernel evaluation the record form is 16 % ahead of k_grid_blk at 8192^2 / 19 planes (17.2 + 1.5 against 20.4 ms, apply
+    // 69.9 against 72.2); at C5 (4 x 4 blocks: the key does not fit) it is 6.5 % ahead and the plane values eat that (1038.6 against
+    // 1033.3 ms).  Default: the record form where the 16 x 16 frame applies and the plan is not C5's size; k_grid_blk otherwise.
+    const bool rec_es_auto = sw.scatter == ScatterForce::Auto && blk_frame16(int(info.W), p.bc) && info.nactive <= int64_t(30000000);
+    // (polynomial planes in several passes -- 5 to 10 planes, moderate omega -- can take the same route, k_plane_values in front of each
+    // pass's scatter, on request only: 4096^2 / 10 planes, grid 3.70 + 0.37 ms of plane values against 4.20 for k_grid_blk, apply 13.05
+    // against 13.02 ms -- every visibility is in every pass there, so the values pass costs what the kernel gains)
+    const bool multi_poly = info.wmode == 1 && info.nplanes > kp_max;
+    const bool rec_es = prm.do_wgridding && has_work &&
+                        ((info.wmode == 0 && (sw.scatter == ScatterForce::RecEs || rec_es_auto)) ||
+                         (multi_poly && sw.scatter == ScatterForce::RecEs));
+    const bool rec = (rec_mode || rec_es) && blk && sw.scatter != ScatterForce::Block;
+    p.scatter = !blk ? Scatter::Walk : info.wmode == 2 ? Scatter::OnePlane : rec ? Scatter::Rec : Scatter::Block;
+    p.gather = info.wmode == 2 ? Gather::OnePlane : rec_mode ? Gather::RowWalk : Gather::Walk;
+    // one pass over the planes (otherwise the buffer is reused inside the apply) and a second buffer of <= 40 GB
+    p.side_clear = info.nplanes <= kp_max && has_work && ws.grid_bytes <= (size_t(40) << 30);
+    // one-plane coloured plans (wd_hessian_supported): a Hessian apply runs k_hess_wd per colour instead of the gather and the
+    // four scatter launches
+    p.hess_fused = sw.wd_fused && info.wmode == 2 && p.coloured && p.side_clear && info.nplanes == 1 &&
+                   wd_hessian_supported(int(info.W), p.bc);
+    p.gather_values = rec_mode && rec && !p.hess_fused;
+    return p;
+}
+
+// ---- step 3: the plane transforms, once the row-FFT plans exist ----
+// (doubled first-axis shapes transpose only where the waiting half transform is parked in LDS -- 20480 points)
+static bool transposing_possible(bool fused, const RowFFT &rv) { return fused && rv.ok && (!rv.pl.doubled || fused_doubled_stashes(rv)); }
+static PlanPath choose_transforms(PlanPath p, const PlanSwitches &sw, const pfbhip_gridder_params &prm, const RowFFT &ru,
+                                  const RowFFT &rv, int npoly, bool has_work)
+{
+    // Doubled shapes (20480, 24576, 32768 points) run the plain row kernel on both axes and keep the separate pad / crop
+    // kernels.  Their dedicated fused kernels (k_fused_fft_crop2 / k_fused_pad_fft2: even / odd half transforms combined
+    // pair by pair) hold one half's 16 outputs across the other half's transform and still spill ~100 registers at the
+    // 170-VGPR budget of a 640..1024-thread workgroup: measured 36.8 ms against 35.6 ms unfused for the second axis of
+    // a 16384^2 image / 20480^2 grid with 4 planes, so they stay behind PFBHIP_FUSED_DOUBLED=1 (tests keep them alive).
+    // Round 3: at 20480 points the waiting half is parked in LDS (k_fused_fft_crop2 / k_fused_pad_fft2, STASH) and the fused
+    // kernels are the default; PFBHIP_FUSED_DOUBLED=0 / 1 forces the choice for every doubled shape.
+    const bool fuse_doubled = sw.fused_doubled >= 0 ? sw.fused_doubled == 1 : fused_doubled_stashes(ru);
+    // (the fused kernels evaluate n - 1 by the polynomial only: fields reaching 45 degrees off axis, npoly = 0, keep the
+    // separate pad / crop kernels with the closed form)
+    const bool fused = sw.fused_fft && ru.ok && (!ru.pl.doubled || fuse_doubled) && (!prm.do_wgridding || npoly > 0);
+    p.axis2 = fused ? SecondAxis::Fused : (sw.rowfft && ru.ok) ? SecondAxis::Rows : SecondAxis::RocFFT;
+    p.axis1 = (sw.tfft && has_work && transposing_possible(fused, rv)) ? FirstAxis::Transposing
+              : rv.ok                                                   ? FirstAxis::Rows
+                                                                        : FirstAxis::RocFFT;
+    return p;
+}
+
+// the plan's path as pfbhip_gridder_info reports it
+static void report_path(const PlanPath &p, pfbhip_gridder_info &info)
+{
+    info.scatter_mode = p.scatter == Scatter::Walk ? 0 : (p.scatter == Scatter::Block ? 1 : 2);
+    info.scatter_launches = p.coloured ? 4 : 1;
+    info.scatter_block = p.bc;
+    info.fft_mode = (p.axis1 != FirstAxis::RocFFT ? 1 : 0) | (p.axis2 == SecondAxis::Fused ? 2 : 0) |
+                    (p.axis2 == SecondAxis::Rows ? 4 : 0) | (p.axis1 == FirstAxis::Transposing ? 8 : 0);
 }
 
 static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo, double whi, double tmax, double nmin)
@@ -1516,6 +1566,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 {
     auto &prm = g->prm;
     const PlanSwitches sw = read_plan_switches();
+    PlanPath path;  // (g->path once complete)
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {  // verbosity >= 1: wall-clock of the plan-creation phases
         if (prm.verbosity < 1) return;
@@ -1631,18 +1682,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                               info.ntiles * info.nplanes < (int64_t(1) << 32) - 2;
     m.key_planes = plane_sorted ? int(info.nplanes) : 1;
     const int64_t nkeys = info.ntiles * m.key_planes;
-    // register-footprint scatter (k_grid_blk): runs of visibilities whose footprint origins share a 4 x 4-cell block
-    // PFBHIP_SCATTER = walk | block forces the kernel; by default the register-footprint form is used when the plan has
-    // enough work items to fill the GPU in each of its four colour launches (decided below, once the work list exists)
-    g->scatter_blk = sw.scatter != ScatterForce::Walk;
-    m.key_sub = (g->scatter_blk && nkeys * 64 < (int64_t(1) << 32) - 2) ? 64 : 1;
-    // register-footprint scatters at W = 14 / 15: a 16 x 16-cell register frame anchored on 2 x 2-cell blocks (k_grid_blk,
-    // k_grid_rec, k_grid_wd); PFBHIP_WD_BLOCK=4 keeps the 4 x 4 anchoring (17 / 18-cell frame on 3 x 20 lanes).  ES-plane plans whose
-    // (tile, plane, block) key would not fit 32 bits (C5: 409 600 tiles x 64 planes) stay on 4 x 4 blocks.
-    const bool want2 = (info.W == 14 || info.W == 15) && !sw.wd_block4;
-    if (m.key_sub == 64 && want2 && nkeys * 256 < (int64_t(1) << 32) - 2) m.key_sub = 256;
-    g->wd_bc = wd_block_edge(int(info.W), m.key_sub == 256);
-    g->scatter_blk = m.key_sub > 1;  // without the block order in the 32-bit key the runs are ~1 long: the walk kernel is cheaper
+    m.key_sub = sort_key_sub(sw, int(info.W), nkeys);
     std::vector<WorkItem> work;
     uint32_t chunk_used = CHUNK;
     size_t coarse_items = 0;  // work items at CHUNK visibilities each (the size measure of the launch-shape decisions below)
@@ -1716,31 +1756,29 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         g->work_off.push_back(0);
         g->work_cnt.push_back(0);
     }
-    // Small plans (C1: ~300 work items) run faster on the single-launch walk kernel: four colour launches of a few dozen
-    // workgroups each leave most of the 256 CUs idle.  (One-plane scheme, round 4 size sweep: one launch with the atomic flush
-    // wins up to 4096^2 / 4e6 visibilities = 5 000 tiles in use, ties at 6144^2 = 11 000, loses at C2 = 20 000: 2.44 vs 2.31 ms.)  The block order of the sort is kept either way (any order is valid).
+    // (row pitch of the uv-plane buffer: see the B pitch below; rocFFT row plans on A need the dense pitch)
     {
-        // (mean over the passes: the first and last pass of an ES-plane plan hold the few visibilities at the ends of the w
-        // range -- their launches are short whichever kernel runs them)
-        const size_t per_pass = work.size() / std::max<size_t>(g->work_cnt.size(), 1);
-        if (info.wmode == 2) {
-            PFB_REQUIRE(g->scatter_blk, "the one-plane w-scheme needs the block-ordered sort");
-            // (PFBHIP_WD_COLOURS=1: the four colour launches whatever the size -- tests; 0: one launch with the atomic flush)
-            g->wd_small = sw.wd_colours < 0 ? coarse_items / std::max<size_t>(g->work_cnt.size(), 1) < size_t(8192) : sw.wd_colours == 0;
-        } else if (g->scatter_blk && sw.scatter == ScatterForce::Auto && per_pass < size_t(2048)) g->scatter_blk = false;
+        RowFFTPlan probe;
+        const bool own_v = sw.rowfft && rowfft_make_plan(info.nv, &probe);
+        g->geom.apitch = int(info.nv) + (own_v ? 8 : 0);
+    }
+    g->plane_stride = size_t(info.nu) * size_t(g->geom.apitch);
+    {
+        const size_t npass = std::max<size_t>(g->work_cnt.size(), 1);
+        const WorkShape ws{m.key_sub, work.size(), work.size() / npass, coarse_items / npass,
+                           g->plane_stride * size_t(g->kp_max) * sizeof(double2)};
+        path = choose_kernels(sw, prm, info, g->kp_max, ws);
     }
     {
         // colour slices of every group's list (LPT order kept inside a slice); chunks of a tile that has several in the
         // slice are flagged shared (pad = 1) and keep the atomic flush
-        const int64_t ntu_c = ceil_div(info.nu, TILE);
-        g->coloured = g->scatter_blk && !g->wd_small && (ntu_c % 2 == 0) && (m.ntv % 2 == 0) && info.nu % TILE == 0 && info.nv % TILE == 0;
         // The one-plane scatter runs 256-thread workgroups: an item of 4096 visibilities is 1024 per wave, longer than a whole
         // colour launch of a mid-size plan should take (4096^2, 4e6 visibilities: grid 1.61 ms -> 1.02 with items of <= 1024; C2
         // indifferent between 1024 and 4096).  Its lists are cut finer than the gather's: about three items per workgroup
         // slot and launch, 512..2048 visibilities each.
         uint32_t schunk = chunk_used;
         if (info.wmode == 2) {
-            const double per_launch = double(info.nactive) / (g->coloured ? 4.0 : 1.0);
+            const double per_launch = double(info.nactive) / (path.coloured ? 4.0 : 1.0);
             uint32_t c = 512;
             while (c < 2048 && double(c) * 1.5 < per_launch / (3.0 * 768.0)) c *= 2;
             schunk = std::min(c, chunk_used);
@@ -1758,11 +1796,11 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                 g->col_off.push_back(wcol.size());
                 for (size_t i = b0; i < b1; ++i) {
                     const uint32_t tu = work[i].tile / uint32_t(m.ntv), tv = work[i].tile % uint32_t(m.ntv);
-                    const int c = g->coloured ? int((tu & 1u) * 2u + (tv & 1u)) : 0;
+                    const int c = path.coloured ? int((tu & 1u) * 2u + (tv & 1u)) : 0;
                     if (c != col) continue;
                     WorkItem w = work[i];
                     const uint32_t nt = w.end - w.begin, parts = (nt + schunk - 1) / schunk;
-                    w.pad = (!g->coloured || seen[w.tile] > 1 || parts > 1) ? 1u : 0u;
+                    w.pad = (!path.coloured || seen[w.tile] > 1 || parts > 1) ? 1u : 0u;
                     for (uint32_t q = 0; q < std::max(parts, 1u); ++q) {
                         WorkItem wq = w;
                         wq.begin = w.begin + uint32_t(uint64_t(nt) * q / std::max(parts, 1u));
@@ -1785,62 +1823,26 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             PFB_HIP(hipMemcpyAsync(g->d_work_col.p, wcol.data(), wcol.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
         PFB_HIP(hipStreamSynchronize(st));  // wcol is a local
     }
-    const bool rec_mode = info.nplanes <= g->kp_max && (!prm.do_wgridding || info.wmode >= 1) && info.nactive > 0 && !work.empty();
-    // ES-kernel plane stacks (round 3): the record scatter with the values of each pass written by k_plane_values_es in front of
-    // it, ONLY with PFBHIP_SCATTER=rec_es.  Measured (gpurun_out/r03w, r03x): 8192^2 image, 19 planes, 9.5e6 visibilities: scatter
-    // 21.2 -> 17.8 ms, + 1.4 ms of plane values (88 bytes per visibility and pass), apply 73.2 -> 70.9 ms; C5: 195 -> 190 ms,
-    // + 13 ms of plane values, apply 1035 -> 1044 ms -- there the scatter waits on the records / values of 1e8 visibilities
-    // (6 GB per pass set) whichever kernel runs.  Round 4b: with the 16 x 16-cell frame (W <= 13, or W = 14 / 15 on the finer sort key) and
-    // its paired kernel evaluation the record form is 16 % ahead of k_grid_blk at 8192^2 / 19 planes (17.2 + 1.5 against 20.4 ms, apply
-    // 69.9 against 72.2); at C5 (4 x 4 blocks: the key does not fit) it is 6.5 % ahead and the plane values eat that (1038.6 against
-    // 1033.3 ms).  Default: the record form where the 16 x 16 frame applies and the plan is not C5's size; k_grid_blk otherwise.
-    const bool rec_es_auto = sw.scatter == ScatterForce::Auto && blk_frame16(int(info.W), g->wd_bc) && info.nactive <= int64_t(30000000);
-    // (polynomial planes in several passes -- 5 to 10 planes, moderate omega -- can take the same route, k_plane_values in front of each
-    // pass's scatter, on request only: 4096^2 / 10 planes, grid 3.70 + 0.37 ms of plane values against 4.20 for k_grid_blk, apply 13.05
-    // against 13.02 ms -- every visibility is in every pass there, so the values pass costs what the kernel gains)
-    const bool multi_poly = info.wmode == 1 && info.nplanes > g->kp_max;
-    const bool rec_es = prm.do_wgridding && info.nactive > 0 && !work.empty() &&
-                        ((info.wmode == 0 && (sw.scatter == ScatterForce::RecEs || rec_es_auto)) ||
-                         (multi_poly && sw.scatter == ScatterForce::RecEs));
-    g->scatter_rec = (rec_mode || rec_es) && g->scatter_blk && sw.scatter != ScatterForce::Block;
-    g->pval_from_gather = rec_mode && g->scatter_rec;
-    g->gather_rw = rec_mode;
-    if (rec_mode || g->scatter_rec) {
+    // per-visibility records of the record scatter, the row-walk gather and the one-plane kernels
+    if (path.scatter == Scatter::Rec || path.scatter == Scatter::OnePlane || path.gather != Gather::Walk) {
         g->d_rec.alloc(size_t(info.nactive) + REC_PAD);
         g->d_pval.alloc((size_t(info.nactive) + REC_PAD) * size_t(info.wmode == 2 ? info.nderiv : g->kp_max));
         PFB_HIP(hipMemsetAsync(g->d_pval.p, 0, g->d_pval.bytes(), st));
-        switch (info.W) {
-#define PFB_CASE(w)                                                                                                      \
-    case w:                                                                                                              \
-        hipLaunchKernelGGL((k_vis_records<w>), blocks1d(info.nactive + REC_PAD), dim3(256), 0, st, int(info.nu), int(info.nv), \
-                           info.nactive, g->d_pu.p, g->d_pv.p, g->d_rec.p);                                              \
-        break;
-            PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-            PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-            default: throw std::runtime_error("unsupported kernel support");
-        }
-        PFB_HIP(hipGetLastError());
-        if (g->gather_rw && info.wmode != 2) {
-            g->d_kw.alloc((size_t(info.nactive) + REC_PAD) * size_t(g->kp_max));
-            // (the planes / polynomial nodes are set by choose_kernel; the work list is not needed here)
-            GroupArgs ga = g->group_args(0, int(info.nplanes));
-            switch (info.W) {
-#define PFB_CASE(w)                                                                                                   \
-    case w:                                                                                                           \
-        hipLaunchKernelGGL((k_plane_weights<w>), blocks1d(info.nactive + REC_PAD), dim3(256), 0, st, ga, info.nactive, \
-                           g->d_kw.p);                                                                                \
-        break;
-                PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-                PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-                default: throw std::runtime_error("unsupported kernel support");
-            }
+        with_W(int(info.W), [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            hipLaunchKernelGGL((k_vis_records<W>), blocks1d(info.nactive + REC_PAD), dim3(256), 0, st, int(info.nu), int(info.nv),
+                               info.nactive, g->d_pu.p, g->d_pv.p, g->d_rec.p);
             PFB_HIP(hipGetLastError());
-        }
+            if (path.gather == Gather::RowWalk) {
+                g->d_kw.alloc((size_t(info.nactive) + REC_PAD) * size_t(g->kp_max));
+                // (the planes / polynomial nodes are set by choose_kernel; the work list is not needed here)
+                GroupArgs ga = g->group_args(0, int(info.nplanes));
+                hipLaunchKernelGGL((k_plane_weights<W>), blocks1d(info.nactive + REC_PAD), dim3(256), 0, st, ga, info.nactive, g->d_kw.p);
+                PFB_HIP(hipGetLastError());
+            }
+        });
         PFB_HIP(hipStreamSynchronize(st));
     }
-    info.scatter_launches = (g->scatter_blk && g->coloured) ? 4 : 1;
     info.nwork = int64_t(work.size());
     g->d_work.alloc(std::max<size_t>(work.size(), 1));
     if (!work.empty())
@@ -1862,7 +1864,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             wa = WdArgs{};
             wa.K = K;
             wa.W = W;
-            wa.bc = g->wd_bc;
+            wa.bc = path.bc;
             wa.whalf = info.whalf;
             wa.nshift = info.nshift;
             std::vector<double> dtab(size_t(K) * W * D1, 0.0);
@@ -1924,27 +1926,13 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 
     lap("kernel table + correction");
     // ---- scratch + FFT plans ----
-    // (row pitch of the uv-plane buffer: see the B pitch below; rocFFT row plans on A need the dense pitch)
-    {
-        RowFFTPlan probe;
-        const bool own_v = sw.rowfft && rowfft_make_plan(info.nv, &probe);
-        g->geom.apitch = int(info.nv) + (own_v ? 8 : 0);
-    }
-    g->plane_stride = size_t(info.nu) * size_t(g->geom.apitch);
     g->d_grid.alloc(g->plane_stride * size_t(g->kp_max));
-    g->grid_cur = g->d_grid.p;
-    {
-        // one pass over the planes (otherwise the buffer is reused inside the apply) and a second buffer of <= 40 GB
-        g->async_clear = info.nplanes <= g->kp_max && info.nactive > 0 && g->d_grid.bytes() <= (size_t(40) << 30);
-        if (g->async_clear) {
-            g->d_grid2.alloc(g->plane_stride * size_t(g->kp_max));
-            PFB_HIP(hipStreamCreateWithFlags(&g->clear_stream, hipStreamNonBlocking));
-            PFB_HIP(hipEventCreateWithFlags(&g->ev_clear, hipEventDisableTiming));
-            PFB_HIP(hipEventCreateWithFlags(&g->ev_start, hipEventDisableTiming));
-            PFB_HIP(hipMemsetAsync(g->d_grid2.p, 0, g->d_grid2.bytes(), st));
-        }
-        g->hess_fused_ok = sw.wd_fused && info.wmode == 2 && g->coloured && !g->wd_small && g->async_clear && info.nplanes == 1 &&
-                           wd_hessian_supported(int(info.W), g->wd.bc);
+    if (path.side_clear) {
+        g->d_grid2.alloc(g->plane_stride * size_t(g->kp_max));
+        PFB_HIP(hipStreamCreateWithFlags(&g->clear_stream, hipStreamNonBlocking));
+        PFB_HIP(hipEventCreateWithFlags(&g->ev_clear, hipEventDisableTiming));
+        PFB_HIP(hipEventCreateWithFlags(&g->ev_start, hipEventDisableTiming));
+        PFB_HIP(hipMemsetAsync(g->d_grid2.p, 0, g->d_grid2.bytes(), st));
     }
     lap("uv-plane buffers");
     g->d_img.alloc(size_t(npix));
@@ -1955,17 +1943,8 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // {1,3,5} x 2^a (every size grid_size() prefers), with the pad / crop / w-screen of the second axis
     // fused into its load / store; rocFFT row plans otherwise.  PFBHIP_FUSED_FFT=0 / PFBHIP_ROWFFT=0
     // force the rocFFT paths (used by the tests to keep both alive).
-    const bool own_rows = sw.rowfft;
-    const bool want_fused = sw.fused_fft;
-    if (own_rows || want_fused) (void)g->rowfft_u.init(info.nu);
-    // Doubled shapes (20480, 24576, 32768 points) run the plain row kernel on both axes and keep the separate pad / crop
-    // kernels.  Their dedicated fused kernels (k_fused_fft_crop2 / k_fused_pad_fft2: even / odd half transforms combined
-    // pair by pair) hold one half's 16 outputs across the other half's transform and still spill ~100 registers at the
-    // 170-VGPR budget of a 640..1024-thread workgroup: measured 36.8 ms against 35.6 ms unfused for the second axis of
-    // a 16384^2 image / 20480^2 grid with 4 planes, so they stay behind PFBHIP_FUSED_DOUBLED=1 (tests keep them alive).
-    // Round 3: at 20480 points the waiting half is parked in LDS (k_fused_fft_crop2 / k_fused_pad_fft2, STASH) and the fused
-    // kernels are the default; PFBHIP_FUSED_DOUBLED=0 / 1 forces the choice for every doubled shape.
-    const bool fuse_doubled = sw.fused_doubled >= 0 ? sw.fused_doubled == 1 : fused_doubled_stashes(g->rowfft_u);
+    if (sw.rowfft || sw.fused_fft) (void)g->rowfft_u.init(info.nu);
+    if (sw.rowfft) (void)g->rowfft_v.init(info.nv);
     {  // the screen geometry serves the fused kernels and the separate pad / crop kernels alike
         FusedGeom &fg = g->fgeom;
         fg.nx = int(prm.nx);
@@ -1979,15 +1958,14 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         if (prm.do_wgridding) fused_geom_fit(fg);
         if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] w-screen: n-1 polynomial with %d coefficients\n", fg.npoly);
     }
-    // (the fused kernels evaluate n - 1 by the polynomial only: fields reaching 45 degrees off axis, npoly = 0, keep the
-    // separate pad / crop kernels with the closed form)
-    g->fused = want_fused && g->rowfft_u.ok && (!g->rowfft_u.pl.doubled || fuse_doubled) &&
-               (!prm.do_wgridding || g->fgeom.npoly > 0);
-    if (!own_rows && !g->fused) g->rowfft_u.release();
-    if (own_rows) (void)g->rowfft_v.init(info.nv);
+    path = choose_transforms(path, sw, prm, g->rowfft_u, g->rowfft_v, g->fgeom.npoly, !work.empty());
+    g->path = path;
+    report_path(path, info);
+    const bool fused = path.axis2 == SecondAxis::Fused;
+    if (path.axis2 == SecondAxis::RocFFT) g->rowfft_u.release();
     g->plane_groups.clear();
     g->d_tau.release();
-    if (g->fused) {
+    if (fused) {
         // screen form per pass: composite polynomials of the whole phase where it is small, else the separable form (column
         // table x row factor x residual polynomials; PFBHIP_SEPSCREEN=0 disables), else n - 1 and sincos per pixel and plane
         bool any_sep = false;
@@ -2022,32 +2000,28 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                     g->plane_groups.size(), n_sc, n_sep, g->plane_groups.size() - size_t(n_sc + n_sep), nsc_max, g->fgeom.npoly);
         }
     }
-    info.fft_mode = (g->rowfft_v.ok ? 1 : 0) | (g->fused ? 2 : 0) | ((!g->fused && g->rowfft_u.ok) ? 4 : 0);
     info.screen_poly = g->fgeom.npoly;
     info.screen_composite = info.screen_separable = 0;
     for (const FusedPlanes &fp : g->plane_groups) {
         info.screen_composite += (fp.nsc > 0 && !fp.sep) ? 1 : 0;
         info.screen_separable += fp.sep ? 1 : 0;
     }
-    info.scatter_mode = g->scatter_rec ? 2 : (g->scatter_blk ? 1 : 0);
     // Row pitch of B.  A workgroup of the transposing first-axis FFT touches B[y][u] for one u and every y: with a pitch of
     // nu * 16 bytes (a multiple of 2^15 for every size the plan picks) all of a row's 16-byte pieces fall on one L2 /
     // memory channel.  8 more elements (128 bytes) per row walk the channels instead (the rocFFT second axis needs the dense
     // pitch).
-    g->geom.bpitch = int(info.nu) + (g->fused ? 8 : 0);
+    g->geom.bpitch = int(info.nu) + (fused ? 8 : 0);
     g->fgeom.bpitch = g->geom.bpitch;
     g->bstride = size_t(prm.ny) * size_t(g->geom.bpitch);
     // Degridding side of the transposing first-axis FFT: the fused pad kernel stores Bt[u][y] (scattered 16-byte stores that
     // meet in L2, as on the gridding side) and the first-axis transform of row u reads its row of Bt contiguously -- a
     // 16-byte GATHER in that transform's load phase cost 0.3 ms per plane at C2, scattered stores cost 0.1.  The pitch is
-    // kept off the power of two for the same reason as bpitch (40 more elements: whole 128-byte lines).  Set wherever the
-    // transposing first axis can run; cleared again below if it does not.  (Doubled first-axis shapes: only where the
-    // waiting half transform is parked in LDS -- 20480 points.)
-    const bool tfft_ok = g->fused && g->rowfft_v.ok && (!g->rowfft_v.pl.doubled || fused_doubled_stashes(g->rowfft_v));
-    g->fgeom.tpitch = tfft_ok ? int(prm.ny) + 40 : 0;
-    g->bstride = std::max(g->bstride, size_t(info.nu) * size_t(g->fgeom.tpitch));
+    // kept off the power of two for the same reason as bpitch (40 more elements: whole 128-byte lines).  (B is sized for that
+    // layout wherever the transposing first axis could run, whether or not the plan takes it.)
+    g->fgeom.tpitch = path.axis1 == FirstAxis::Transposing ? int(prm.ny) + 40 : 0;  // (0: the tile-transpose kernels read B[y][u])
+    if (transposing_possible(fused, g->rowfft_v)) g->bstride = std::max(g->bstride, size_t(info.nu) * size_t(prm.ny + 40));
     lap("row-FFT tables + w-screens");
-    g->d_gridB.alloc(g->bstride * size_t(g->fused ? g->kp_max : 1));
+    g->d_gridB.alloc(g->bstride * size_t(fused ? g->kp_max : 1));
     g->d_accT.alloc(size_t(npix));
     lap("intermediate plane + image buffers");
 
@@ -2127,7 +2101,8 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
                 g->d_clear_rects.alloc(rects.size());
                 PFB_HIP(hipMemcpyAsync(g->d_clear_rects.p, rects.data(), rects.size() * sizeof(int4), hipMemcpyHostToDevice, st));
                 PFB_HIP(hipStreamSynchronize(st));
-                g->n_clear_rects = int(rects.size());
+                // (the plain first-axis transform runs IN PLACE on the scatter's planes: whole rows to clear)
+                if (path.axis1 == FirstAxis::Transposing) g->n_clear_rects = int(rects.size());
             }
             if (prm.verbosity > 0)
                 fprintf(stderr, "[pfbhip] scatter-plane clear: %lld of %lld cells in %zu rectangles\n", (long long)cells,
@@ -2179,21 +2154,20 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         pfbhip_gridder::RowSpan sp;
         sp.row0 = r.first * TP;
         sp.nrows = std::min<int64_t>(r.second * TP, info.nu) - sp.row0;
-        if (!g->rowfft_v.ok) {
+        if (path.axis1 == FirstAxis::RocFFT) {
             sp.fwd = make_rows(info.nv, sp.nrows, true);
             sp.bwd = make_rows(info.nv, sp.nrows, false);
         }
         g->occ_rows += sp.nrows;
         g->spans.push_back(sp);
     }
-    if (!g->fused && !g->rowfft_u.ok) {  // second axis on rocFFT only if the hand-written FFT does not take nu
+    if (path.axis2 == SecondAxis::RocFFT) {  // second axis on rocFFT only if the hand-written FFT does not take nu
         g->fftB_fwd = make_rows(info.nu, prm.ny, true);
         g->fftB_bwd = make_rows(info.nu, prm.ny, false);
     }
     info.occ_rows = int32_t(g->occ_rows);
     {
-        g->tfft = sw.tfft && tfft_ok && g->occ_rows > 0;
-        if (g->tfft) {
+        if (path.axis1 == FirstAxis::Transposing) {
             std::vector<int> rows;
             rows.reserve(size_t(g->occ_rows));
             for (auto &sp : g->spans)
@@ -2212,9 +2186,6 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             PFB_HIP(hipMemcpyAsync(g->d_rowmap.p, map.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
             PFB_HIP(hipStreamSynchronize(st));
         }
-        if (!g->tfft) g->fgeom.tpitch = 0;  // (the tile-transpose kernels read B[y][u])
-        if (!g->tfft) g->n_clear_rects = 0;  // (the plain first-axis transform runs IN PLACE on the scatter's planes: whole rows to clear)
-        info.fft_mode |= g->tfft ? 8 : 0;
     }
     lap("occupancy, column runs, row map");
     if (any_rocfft) {
@@ -2233,6 +2204,128 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 }
 
 }  // namespace pfbhip
+
+// ---------------------------------------------------------------------------------------
+// bodies of the C-ABI entries, shared by the double and single-precision host entries (T = double, float): only
+// pfbhip_gridder::upload / download differ
+// ---------------------------------------------------------------------------------------
+
+// sval = the uploaded visibilities (d_vis) in tile-sorted order, weighted with d_wgt if `weighted`, phase-shifted
+static void permute_in(pfbhip_gridder *g, bool weighted)
+{
+    if (g->info.nactive)
+        hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->map, g->d_src.p, g->info.nactive,
+                           g->d_vis.p, weighted ? g->d_wgt.p : nullptr, int(g->shifting), g->info.lshift, g->info.mshift,
+                           g->info.nshift, g->d_sval.p);
+    PFB_HIP(hipGetLastError());
+}
+
+// the uploaded visibilities -> dirty image (device)
+static void vis2dirty_device(pfbhip_gridder *g, bool weighted, double *dirty_dev)
+{
+    permute_in(g, weighted);
+    g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, dirty_dev);
+}
+
+template <class T>
+static void vis2dirty_host(pfbhip_gridder *g, const T *vis_host, const T *wgt_host, T *dirty_host)
+{
+    PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
+    g->upload_vis_wgt(vis_host, wgt_host);
+    vis2dirty_device(g, wgt_host != nullptr, g->d_img.p);
+    g->download(g->d_img.p, size_t(g->prm.nx * g->prm.ny), dirty_host);
+    PFB_HIP(hipStreamSynchronize(g->stream));
+}
+
+template <class T>
+static void dirty2vis_host(pfbhip_gridder *g, const T *dirty_host, const T *wgt_host, T *vis_host)
+{
+    PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
+    hipStream_t st = g->stream;
+    g->upload(dirty_host, size_t(g->prm.nx * g->prm.ny), g->d_img.p);
+    g->upload_vis_wgt<T>(nullptr, wgt_host);
+    ApplyState a{g->d_grid.p};
+    g->prepare_and_degrid(a, g->d_img.p, nullptr, g->d_sacc.p);
+    if (g->nvis) {
+        g->d_vis.ensure(size_t(g->nvis));
+        PFB_HIP(hipMemsetAsync(g->d_vis.p, 0, size_t(g->nvis) * sizeof(double2), st));
+        if (g->info.nactive)
+            hipLaunchKernelGGL(k_permute_out, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p, g->info.nactive,
+                               g->d_sacc.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting), g->info.lshift, g->info.mshift,
+                               g->info.nshift, g->d_vis.p);
+        PFB_HIP(hipGetLastError());
+        g->download(reinterpret_cast<const double *>(g->d_vis.p), size_t(g->nvis) * 2, vis_host);
+    }
+    PFB_HIP(hipStreamSynchronize(st));
+}
+
+template <class T>
+static void set_weights_host(pfbhip_gridder *g, const T *wgt_host)
+{
+    PFB_REQUIRE(g, "NULL handle");
+    g->upload_vis_wgt<T>(nullptr, wgt_host);
+    g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
+    if (g->info.nactive)
+        hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->d_src.p, g->info.nactive,
+                           wgt_host ? g->d_wgt.p : nullptr, g->d_swgt.p);
+    PFB_HIP(hipGetLastError());
+    PFB_HIP(hipStreamSynchronize(g->stream));
+    g->weights_bound = true;
+}
+
+// out = beam_out * R^H W R (beam_in * x) * scale + eta * addend   (every image resident in HBM; beams and addend may be NULL)
+static void apply_op(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, const double *beam_out_dev, double scale,
+                     double eta, const double *addend_dev, double *out_dev)
+{
+    PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the Hessian");
+    const PlanPath &path = g->path;
+    ApplyState a{g->d_grid.p};
+    // the scatter's planes (second buffer) are cleared on the side stream while the degrid half runs (the gather is LDS /
+    // VALU-bound: the clear's HBM traffic is free there): see side_clear()
+    a.side = path.side_clear ? SideClear::Pending : SideClear::None;
+    // record scatter: the gather's epilogue writes the weighted, plane-weighted model visibilities (no sacc, no scaling pass)
+    a.gather_values = path.gather_values;
+    // one-plane coloured plans: no gather launch; the scatter half's launches gather from d_grid themselves (k_hess_wd)
+    a.hess_fused = path.hess_fused;
+    g->prepare_and_degrid(a, x_dev, beam_dev, g->d_sacc.p);
+    PFB_REQUIRE(!a.hess_fused || a.side == SideClear::Done, "fused Hessian: the output plane was not cleared");
+    if (!a.gather_values && !a.hess_fused) {
+        g->timer.begin(ST_OTHER);
+        if (g->info.nactive)
+            hipLaunchKernelGGL(k_scale_sorted, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->info.nactive, g->d_sacc.p,
+                               g->d_swgt.p, g->d_sval.p);
+        PFB_HIP(hipGetLastError());
+        g->timer.end();
+    }
+    if (a.side == SideClear::Done) {
+        PFB_HIP(hipStreamWaitEvent(g->stream, g->ev_clear, 0));
+        a.out = g->d_grid2.p;
+    }
+    g->grid_and_finalize(a, g->d_sval.p, beam_out_dev, scale, eta, (eta != 0.0) ? addend_dev : nullptr, out_dev);
+}
+
+static void hessian_dev_impl(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
+                             double *out_dev)
+{
+    apply_op(g, x_dev, beam_dev, beam_dev, wsum > 0.0 ? 1.0 / wsum : 1.0, eta, eta != 0.0 ? x_dev : nullptr, out_dev);
+}
+
+template <class T>
+static void hessian_host(pfbhip_gridder *g, const T *x_host, const T *beam_host, double eta, double wsum, T *out_host)
+{
+    PFB_REQUIRE(g && x_host && out_host, "NULL argument");
+    const size_t npix = size_t(g->prm.nx * g->prm.ny);
+    g->d_img.ensure(npix);
+    g->d_img2.ensure(npix);
+    g->upload(x_host, npix, g->d_img.p);
+    if (beam_host) {
+        g->d_beam.ensure(npix);
+        g->upload(beam_host, npix, g->d_beam.p);
+    }
+    hessian_dev_impl(g, g->d_img.p, beam_host ? g->d_beam.p : nullptr, eta, wsum, g->d_img2.p);
+    g->download(g->d_img2.p, npix, out_host);
+    PFB_HIP(hipStreamSynchronize(g->stream));
+}
 
 // ---------------------------------------------------------------------------------------
 // C-ABI
@@ -2272,7 +2365,6 @@ int pfbhip_gridder_get_info(const pfbhip_gridder *g, pfbhip_gridder_info *info)
         std::swap(info->nu, info->nv);          // report the caller's orientation (the plan holds the transposed problem)
         std::swap(info->lshift, info->mshift);
         info->device_bytes = g->device_bytes();
-        info->scatter_block = g->wd_bc;
         info->reserved0 = 0;
     });
 }
@@ -2313,35 +2405,16 @@ int pfbhip_gridder_get_binmap(pfbhip_gridder *g, int32_t *iu0, int32_t *iv0, int
 
 int pfbhip_gridder_vis2dirty(pfbhip_gridder *g, const double *vis_host, const double *wgt_host, double *dirty_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-        hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        g->upload_vis_wgt(vis_host, wgt_host);
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                               g->info.nactive, g->d_vis.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                               g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
-        PFB_HIP(hipGetLastError());
-        g->grid_and_finalize(g->d_sval.p, nullptr, 1.0, 0.0, nullptr, g->d_img.p);
-        PFB_HIP(hipMemcpyAsync(dirty_host, g->d_img.p, size_t(npix) * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { vis2dirty_host(g, vis_host, wgt_host, dirty_host); });
 }
 
 int pfbhip_gridder_vis2dirty_dev(pfbhip_gridder *g, const double *vis_host, const double *wgt_host, double *dirty_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && (vis_host || g->nvis == 0), "NULL argument");
-        hipStream_t st = g->stream;
         g->upload_vis_wgt(vis_host, wgt_host);
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                               g->info.nactive, g->d_vis.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                               g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
-        PFB_HIP(hipGetLastError());
-        g->grid_and_finalize(g->d_sval.p, nullptr, 1.0, 0.0, nullptr, dirty_dev);
-        PFB_HIP(hipStreamSynchronize(st));
+        vis2dirty_device(g, wgt_host != nullptr, dirty_dev);
+        PFB_HIP(hipStreamSynchronize(g->stream));
     });
 }
 
@@ -2355,18 +2428,8 @@ int pfbhip_gridder_grid_plane(pfbhip_gridder *g, const double *vis_host, const d
         g->upload_vis_wgt(vis_host, wgt_host);
         PFB_HIP(hipMemsetAsync(g->d_grid.p, 0, g->plane_stride * sizeof(double2), st));
         if (g->info.nactive && g->info.nwork) {
-            hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                               g->info.nactive, g->d_vis.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                               g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
-            PFB_HIP(hipGetLastError());
-            auto &info = g->info;
-            switch (info.W) {
-#define PFB_CASE(w) case w: g->launch_grid_mp_w<w>(int(plane), 1, g->d_sval.p); break;
-                PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-                PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-                default: throw std::runtime_error("unsupported kernel support");
-            }
+            permute_in(g, wgt_host != nullptr);
+            g->launch_grid(ApplyState{g->d_grid.p}, int(plane), 1, g->d_sval.p);
             PFB_HIP(hipGetLastError());
         }
         // the plan's plane is (nv, nu) in the caller's terms: transpose on the host (debug entry)
@@ -2384,100 +2447,12 @@ int pfbhip_gridder_grid_plane(pfbhip_gridder *g, const double *vis_host, const d
 
 int pfbhip_gridder_dirty2vis(pfbhip_gridder *g, const double *dirty_host, const double *wgt_host, double *vis_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-        hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        PFB_HIP(hipMemcpyAsync(g->d_img.p, dirty_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-        g->upload_vis_wgt(nullptr, wgt_host);
-        g->prepare_and_degrid(g->d_img.p, nullptr, g->d_sacc.p);
-        if (g->nvis) {
-            g->d_vis.ensure(size_t(g->nvis));
-            PFB_HIP(hipMemsetAsync(g->d_vis.p, 0, size_t(g->nvis) * sizeof(double2), st));
-            if (g->info.nactive)
-                hipLaunchKernelGGL(k_permute_out, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                                   g->info.nactive, g->d_sacc.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                                   g->info.lshift, g->info.mshift, g->info.nshift, g->d_vis.p);
-            PFB_HIP(hipGetLastError());
-            PFB_HIP(hipMemcpyAsync(vis_host, g->d_vis.p, size_t(g->nvis) * sizeof(double2), hipMemcpyDeviceToHost, st));
-        }
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { dirty2vis_host(g, dirty_host, wgt_host, vis_host); });
 }
 
 int pfbhip_gridder_set_weights(pfbhip_gridder *g, const double *wgt_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g, "NULL handle");
-        hipStream_t st = g->stream;
-        g->upload_vis_wgt(nullptr, wgt_host);
-        g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, st, g->d_src.p, g->info.nactive,
-                               wgt_host ? g->d_wgt.p : nullptr, g->d_swgt.p);
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(st));
-        g->weights_bound = true;
-    });
-}
-
-// out = beam_out * R^H W R (beam_in * x) * scale + eta * addend   (every image resident in HBM; beams and addend may be NULL)
-static void apply_op(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, const double *beam_out_dev, double scale,
-                     double eta, const double *addend_dev, double *out_dev)
-{
-    PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the Hessian");
-    hipStream_t st = g->stream;
-    const int64_t npix = g->prm.nx * g->prm.ny;
-    const bool side = g->async_clear && g->info.nwork > 0;
-    // the scatter's planes (second buffer) are cleared on the side stream while the GATHER runs (LDS / VALU-bound: the
-    // clear's HBM traffic is free there; next to the row-FFT stages it only takes their bandwidth): see side_clear()
-    g->side_clear_pending = side;
-    g->side_clear_done = false;
-    // record scatter: the gather's epilogue writes the weighted, plane-weighted model visibilities (no sacc, no scaling pass)
-    // one-plane coloured plans: no gather launch; the scatter half's launches gather from d_grid themselves (k_hess_wd)
-    g->hess_fused = g->hess_fused_ok && side;
-    g->want_pval = !g->hess_fused && g->pval_from_gather && g->info.nwork > 0;
-    struct ClearFlags {
-        pfbhip_gridder *g;
-        ~ClearFlags() { g->want_pval = g->pval_ready = g->hess_fused = false; }
-    } clear_flags{g};
-    g->prepare_and_degrid(x_dev, beam_dev, g->d_sacc.p);
-    g->side_clear_pending = false;
-    if (g->hess_fused) {
-        PFB_REQUIRE(g->side_clear_done, "fused Hessian: the output plane was not cleared");
-        g->pval_ready = true;
-    } else if (g->want_pval) {
-        g->want_pval = false;
-        g->pval_ready = true;
-    } else {
-        g->timer.begin(5);
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_scale_sorted, blocks1d(g->info.nactive), dim3(256), 0, st, g->info.nactive, g->d_sacc.p,
-                               g->d_swgt.p, g->d_sval.p);
-        PFB_HIP(hipGetLastError());
-        g->timer.end();
-    }
-    if (g->side_clear_done) {
-        PFB_HIP(hipStreamWaitEvent(st, g->ev_clear, 0));
-        g->grid_cur = g->d_grid2.p;
-        g->planes_cleared = true;
-    }
-    struct Restore {  // also on an exception out of the scatter half
-        pfbhip_gridder *g;
-        ~Restore()
-        {
-            g->grid_cur = g->d_grid.p;
-            g->planes_cleared = false;
-        }
-    } restore{g};
-    g->grid_and_finalize(g->d_sval.p, beam_out_dev, scale, eta, (eta != 0.0) ? addend_dev : nullptr, out_dev);
-    (void)npix;
-}
-
-static void hessian_dev_impl(pfbhip_gridder *g, const double *x_dev, const double *beam_dev, double eta, double wsum,
-                             double *out_dev)
-{
-    apply_op(g, x_dev, beam_dev, beam_dev, wsum > 0.0 ? 1.0 / wsum : 1.0, eta, eta != 0.0 ? x_dev : nullptr, out_dev);
+    return guarded([&] { set_weights_host(g, wgt_host); });
 }
 
 // The exact residual of one partition (gridder.py:962-1016 of the reference: dirty2vis of beam * model, vis2dirty with the
@@ -2508,100 +2483,30 @@ int pfbhip_gridder_hessian_dev(pfbhip_gridder *g, const double *x_dev, const dou
 int pfbhip_gridder_hessian(pfbhip_gridder *g, const double *x_host, const double *beam_host, double eta, double wsum,
                            double *out_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && x_host && out_host, "NULL argument");
-        hipStream_t st = g->stream;
-        const size_t npix = size_t(g->prm.nx * g->prm.ny);
-        g->d_img.ensure(npix);
-        g->d_img2.ensure(npix);
-        PFB_HIP(hipMemcpyAsync(g->d_img.p, x_host, npix * sizeof(double), hipMemcpyHostToDevice, st));
-        if (beam_host) {
-            g->d_beam.ensure(npix);
-            PFB_HIP(hipMemcpyAsync(g->d_beam.p, beam_host, npix * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        hessian_dev_impl(g, g->d_img.p, beam_host ? g->d_beam.p : nullptr, eta, wsum, g->d_img2.p);
-        PFB_HIP(hipMemcpyAsync(out_host, g->d_img2.p, npix * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { hessian_host(g, x_host, beam_host, eta, wsum, out_host); });
 }
 
 // ---- single-precision host arrays (precision = "single" of the reference's vis2im / im2vis, operators/gridder.py:58-100, with
 // double-precision accumulation: complex64 / float32 cross PCIe, every device buffer and sum stays double) ----
 int pfbhip_gridder_vis2dirty_sp(pfbhip_gridder *g, const float *vis_host, const float *wgt_host, float *dirty_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-        hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        g->upload_vis_wgt_sp(vis_host, wgt_host);
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                               g->info.nactive, g->d_vis.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                               g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
-        PFB_HIP(hipGetLastError());
-        g->grid_and_finalize(g->d_sval.p, nullptr, 1.0, 0.0, nullptr, g->d_img.p);
-        g->download_f32(g->d_img.p, size_t(npix), dirty_host);
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { vis2dirty_host(g, vis_host, wgt_host, dirty_host); });
 }
 
 int pfbhip_gridder_dirty2vis_sp(pfbhip_gridder *g, const float *dirty_host, const float *wgt_host, float *vis_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-        hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        g->upload_f32(dirty_host, size_t(npix), g->d_img.p);
-        g->upload_vis_wgt_sp(nullptr, wgt_host);
-        g->prepare_and_degrid(g->d_img.p, nullptr, g->d_sacc.p);
-        if (g->nvis) {
-            g->d_vis.ensure(size_t(g->nvis));
-            PFB_HIP(hipMemsetAsync(g->d_vis.p, 0, size_t(g->nvis) * sizeof(double2), st));
-            if (g->info.nactive)
-                hipLaunchKernelGGL(k_permute_out, blocks1d(g->info.nactive), dim3(256), 0, st, g->map, g->d_src.p,
-                                   g->info.nactive, g->d_sacc.p, wgt_host ? g->d_wgt.p : nullptr, int(g->shifting),
-                                   g->info.lshift, g->info.mshift, g->info.nshift, g->d_vis.p);
-            PFB_HIP(hipGetLastError());
-            g->download_f32(reinterpret_cast<const double *>(g->d_vis.p), size_t(g->nvis) * 2, vis_host);
-        }
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { dirty2vis_host(g, dirty_host, wgt_host, vis_host); });
 }
 
 int pfbhip_gridder_set_weights_sp(pfbhip_gridder *g, const float *wgt_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g, "NULL handle");
-        hipStream_t st = g->stream;
-        g->upload_vis_wgt_sp(nullptr, wgt_host);
-        g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
-        if (g->info.nactive)
-            hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, st, g->d_src.p, g->info.nactive,
-                               wgt_host ? g->d_wgt.p : nullptr, g->d_swgt.p);
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(st));
-        g->weights_bound = true;
-    });
+    return guarded([&] { set_weights_host(g, wgt_host); });
 }
 
 int pfbhip_gridder_hessian_sp(pfbhip_gridder *g, const float *x_host, const float *beam_host, double eta, double wsum,
                               float *out_host)
 {
-    return guarded([&] {
-        PFB_REQUIRE(g && x_host && out_host, "NULL argument");
-        hipStream_t st = g->stream;
-        const size_t npix = size_t(g->prm.nx * g->prm.ny);
-        g->d_img.ensure(npix);
-        g->d_img2.ensure(npix);
-        g->upload_f32(x_host, npix, g->d_img.p);
-        if (beam_host) {
-            g->d_beam.ensure(npix);
-            g->upload_f32(beam_host, npix, g->d_beam.p);
-        }
-        hessian_dev_impl(g, g->d_img.p, beam_host ? g->d_beam.p : nullptr, eta, wsum, g->d_img2.p);
-        g->download_f32(g->d_img2.p, npix, out_host);
-        PFB_HIP(hipStreamSynchronize(st));
-    });
+    return guarded([&] { hessian_host(g, x_host, beam_host, eta, wsum, out_host); });
 }
 
 int pfbhip_gridder_cg(pfbhip_gridder *g, const double *beam_host, double eta, double wsum, const double *rhs_host,
@@ -2674,7 +2579,8 @@ int pfbhip_gridder_degrid_dev(pfbhip_gridder *g, const double *dirty_dev, double
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && vis_sorted_dev, "NULL argument");
-        g->prepare_and_degrid(dirty_dev, nullptr, reinterpret_cast<double2 *>(vis_sorted_dev));
+        ApplyState a{g->d_grid.p};
+        g->prepare_and_degrid(a, dirty_dev, nullptr, reinterpret_cast<double2 *>(vis_sorted_dev));
         PFB_HIP(hipStreamSynchronize(g->stream));
     });
 }
@@ -2683,7 +2589,7 @@ int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, dou
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && vis_sorted_dev, "NULL argument");
-        g->grid_and_finalize(reinterpret_cast<const double2 *>(vis_sorted_dev), nullptr, 1.0, 0.0, nullptr, dirty_dev);
+        g->grid_and_finalize(ApplyState{g->d_grid.p}, reinterpret_cast<const double2 *>(vis_sorted_dev), nullptr, 1.0, 0.0, nullptr, dirty_dev);
         PFB_HIP(hipStreamSynchronize(g->stream));
     });
 }

@@ -6,6 +6,7 @@
 #include <stdexcept>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace pfbhip {
 
@@ -14,20 +15,7 @@ namespace pfbhip {
 // fewer work items than three per CU (C1: ~300) cannot fill the chip with 256-thread workgroups: those take one 768-thread
 // workgroup per item.
 static int scatter_threads_for(uint32_t nwork) { return nwork < 768u ? wd_threads() : 256; }
-int wd_scatter_threads() { return wd_threads(); }  // (the largest: what the LDS limit is sized for)
 static int wd_gather_threads_rt(int NJ, uint32_t nwork) { return std::min(nwork < 768u ? 768 : 256, wd_gather_threads(NJ)); }
-size_t wd_scatter_lds_bytes(int W)
-{
-    size_t n = 0;
-    switch (W) {
-#define PFB_CASE(w) case w: n = wd_lds_doubles(w, wd_scatter_threads() / 64); break;
-        PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-        PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-        default: throw std::runtime_error("unsupported kernel support");
-    }
-    return n * sizeof(double);
-}
 size_t wd_gather_lds_bytes() { return size_t(RW_LS) * RW_LS * sizeof(double2); }
 
 void wd_launch_coeffs(const WdArgs &wa, int64_t nactive, const double *pw, double2 *cw, hipStream_t st)
@@ -44,112 +32,59 @@ void wd_launch_plane_values(int K, int64_t nactive, const double2 *cw, const dou
     PFB_HIP(hipGetLastError());
 }
 
-template <int W, int NJ, int BC>
-static void grid_wkb(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *pval, double2 *grid, hipStream_t st)
-{
-    allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_wd<W, NJ, BC>), 160 * 1024);
-    const int threads = scatter_threads_for(ga.a.nwork);
-    const size_t lds = wd_lds_doubles(W, threads / 64) * sizeof(double);
-    hipLaunchKernelGGL((k_grid_wd<W, NJ, BC>), dim3(ga.a.nwork), dim3(threads), lds, st, ga, wa, rec, pval, grid);
-}
-template <int W, int NJ>
-static void grid_wk(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *pval, double2 *grid, hipStream_t st)
-{
-    if constexpr (W == 14 || W == 15) {
-        if (wa.bc == 2) return grid_wkb<W, NJ, 2>(ga, wa, rec, pval, grid, st);
-    }
-    if (wa.bc != 4) throw std::runtime_error("one-plane scatter: block edge 2 is built for W = 14, 15 only");
-    grid_wkb<W, NJ, 4>(ga, wa, rec, pval, grid, st);
-}
-template <int W>
-static void grid_w(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *pval, double2 *grid, hipStream_t st)
-{
-    switch (wa.K) {
-        case 2: grid_wk<W, 2>(ga, wa, rec, pval, grid, st); break;
-        case 3: grid_wk<W, 3>(ga, wa, rec, pval, grid, st); break;
-        case 4: grid_wk<W, 4>(ga, wa, rec, pval, grid, st); break;
-        default: throw std::runtime_error("one-plane w-scheme: 2..4 kernel functions");
-    }
-}
 void wd_launch_grid(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *pval, double2 *grid, hipStream_t st)
 {
     if (ga.a.nwork == 0) return;
-    switch (wa.W) {
-#define PFB_CASE(w) case w: grid_w<w>(ga, wa, rec, pval, grid, st); break;
-        PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-        PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-        default: throw std::runtime_error("unsupported kernel support");
-    }
+    with_W(wa.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        with_K(wa.K, [&](auto nj) {
+            with_BC<W>(wa.bc, [&](auto bc) {
+                constexpr int NJ = decltype(nj)::value, BC = decltype(bc)::value;
+                allow_dynamic_lds(reinterpret_cast<const void *>(&k_grid_wd<W, NJ, BC>), 160 * 1024);
+                const int threads = scatter_threads_for(ga.a.nwork);
+                const size_t lds = wd_lds_doubles(W, threads / 64) * sizeof(double);
+                hipLaunchKernelGGL((k_grid_wd<W, NJ, BC>), dim3(ga.a.nwork), dim3(threads), lds, st, ga, wa, rec, pval, grid);
+            });
+        });
+    });
     PFB_HIP(hipGetLastError());
 }
 
-template <int W, int NJ>
-static void degrid_wk(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *grid, double2 *sacc,
-                      const double *swgt, double2 *pval_out, hipStream_t st)
-{
-    allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_wd<W, NJ>), 160 * 1024);
-    hipLaunchKernelGGL((k_degrid_wd<W, NJ>), dim3(ga.a.nwork), dim3(wd_gather_threads_rt(NJ, ga.a.nwork)), wd_gather_lds_bytes(), st, ga, wa, rec, grid, sacc,
-                       swgt, pval_out);
-}
-template <int W>
-static void degrid_w(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *grid, double2 *sacc,
-                     const double *swgt, double2 *pval_out, hipStream_t st)
-{
-    switch (wa.K) {
-        case 2: degrid_wk<W, 2>(ga, wa, rec, grid, sacc, swgt, pval_out, st); break;
-        case 3: degrid_wk<W, 3>(ga, wa, rec, grid, sacc, swgt, pval_out, st); break;
-        case 4: degrid_wk<W, 4>(ga, wa, rec, grid, sacc, swgt, pval_out, st); break;
-        default: throw std::runtime_error("one-plane w-scheme: 2..4 kernel functions");
-    }
-}
 void wd_launch_degrid(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double2 *grid, double2 *sacc,
                       const double *swgt, double2 *pval_out, hipStream_t st)
 {
     if (ga.a.nwork == 0) return;
-    switch (wa.W) {
-#define PFB_CASE(w) case w: degrid_w<w>(ga, wa, rec, grid, sacc, swgt, pval_out, st); break;
-        PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-        PFB_CASE(12) PFB_CASE(13) PFB_CASE(14) PFB_CASE(15) PFB_CASE(16)
-#undef PFB_CASE
-        default: throw std::runtime_error("unsupported kernel support");
-    }
+    with_W(wa.W, [&](auto w) {
+        with_K(wa.K, [&](auto nj) {
+            constexpr int W = decltype(w)::value, NJ = decltype(nj)::value;
+            allow_dynamic_lds(reinterpret_cast<const void *>(&k_degrid_wd<W, NJ>), 160 * 1024);
+            hipLaunchKernelGGL((k_degrid_wd<W, NJ>), dim3(ga.a.nwork), dim3(wd_gather_threads_rt(NJ, ga.a.nwork)), wd_gather_lds_bytes(),
+                               st, ga, wa, rec, grid, sacc, swgt, pval_out);
+        });
+    });
     PFB_HIP(hipGetLastError());
 }
 
-template <int W, int NJ, int BC>
-static void hess_wkb(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
-                     hipStream_t st)
-{
-    allow_dynamic_lds(reinterpret_cast<const void *>(&k_hess_wd<W, NJ, BC>), 160 * 1024);
-    hipLaunchKernelGGL((k_hess_wd<W, NJ, BC>), dim3(ga.a.nwork), dim3(256), wd_hess_lds_bytes(W), st, ga, wa, rec, swgt, gin, gout);
-}
-template <int W, int BC>
-static void hess_wb(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
-                    hipStream_t st)
-{
-    switch (wa.K) {
-        case 2: hess_wkb<W, 2, BC>(ga, wa, rec, swgt, gin, gout, st); break;
-        case 3: hess_wkb<W, 3, BC>(ga, wa, rec, swgt, gin, gout, st); break;
-        case 4: hess_wkb<W, 4, BC>(ga, wa, rec, swgt, gin, gout, st); break;
-        default: throw std::runtime_error("one-plane w-scheme: 2..4 kernel functions");
-    }
-}
 bool wd_hessian_supported(int W, int bc) { return W >= 4 && W <= 16 && (bc == 2 || bc == 4) && wd_hess_fits(W, bc) && (bc == 4 || W >= 14); }
 void wd_launch_hessian(const GroupArgs &ga, const WdArgs &wa, const VisRec *rec, const double *swgt, const double2 *gin, double2 *gout,
                        hipStream_t st)
 {
     if (ga.a.nwork == 0) return;
     if (!wd_hessian_supported(wa.W, wa.bc)) throw std::runtime_error("fused Hessian: W + block edge - 1 must be <= 16");
-    switch (wa.W) {
-#define PFB_CASE(w) case w: hess_wb<w, 4>(ga, wa, rec, swgt, gin, gout, st); break;
-        PFB_CASE(4) PFB_CASE(5) PFB_CASE(6) PFB_CASE(7) PFB_CASE(8) PFB_CASE(9) PFB_CASE(10) PFB_CASE(11)
-        PFB_CASE(12) PFB_CASE(13)
-#undef PFB_CASE
-        case 14: hess_wb<14, 2>(ga, wa, rec, swgt, gin, gout, st); break;
-        case 15: hess_wb<15, 2>(ga, wa, rec, swgt, gin, gout, st); break;
-        default: throw std::runtime_error("unsupported kernel support");
-    }
+    with_W(wa.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if constexpr (W <= 15) {  // (built as supported: BC = 4 up to W = 13, BC = 2 at W = 14, 15)
+            constexpr int BC = W >= 14 ? 2 : 4;
+            with_K(wa.K, [&](auto nj) {
+                constexpr int NJ = decltype(nj)::value;
+                allow_dynamic_lds(reinterpret_cast<const void *>(&k_hess_wd<W, NJ, BC>), 160 * 1024);
+                hipLaunchKernelGGL((k_hess_wd<W, NJ, BC>), dim3(ga.a.nwork), dim3(256), wd_hess_lds_bytes(W), st, ga, wa, rec, swgt, gin,
+                                   gout);
+            });
+        } else {
+            throw std::runtime_error("unsupported kernel support");
+        }
+    });
     PFB_HIP(hipGetLastError());
 }
 

@@ -21,9 +21,6 @@ struct WdArgs {
 
 // the block edge the scatter of a plan of support W runs with, given whether its sort key carries 2 x 2-cell blocks
 __host__ __device__ constexpr int wd_block_edge(int W, bool fine_key) { return (W == 14 || W == 15) && fine_key ? 2 : BLK_CELLS; }
-// threads per workgroup of the scatter (the caller sizes the dynamic LDS with wd_scatter_lds_bytes)
-int wd_scatter_threads();
-size_t wd_scatter_lds_bytes(int W);
 size_t wd_gather_lds_bytes();
 // C_k of every sorted visibility (plan time)
 void wd_launch_coeffs(const WdArgs &wa, int64_t nactive, const double *pw, double2 *cw, hipStream_t st);

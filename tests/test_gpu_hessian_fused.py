@@ -26,7 +26,8 @@ def plan(c, npix, cell, eps, force=None):
 
 
 def applies(g, c, x):
-    """hessian with and without beam / eta / wsum, residual_dev; and the number of gather launches the first one made"""
+    """hessian with and without beam / eta / wsum, residual_dev, then a plain dirty2vis, vis2dirty and hessian on the same plan
+    (nothing of a Hessian apply may carry over into the next call); and the number of gather launches the first one made"""
     from pfb_imaging_amd._lib import DeviceArray
 
     beam = 0.5 + np.random.default_rng(3).random(x.shape)
@@ -44,7 +45,10 @@ def applies(g, c, x):
     r = o_d.download()
     for d in (m_d, a_d, b_d, o_d):
         d.free()
-    return (h0, h1, h2, r), gathers
+    v = g.dirty2vis(x)
+    d = g.vis2dirty(v, c["wgt"])
+    h3 = g.hessian(x)
+    return (h0, h1, h2, r, v, d, h3), gathers
 
 
 def fused_vs_pair(c, npix, cell, eps, monkeypatch, force=None, tol=2e-11):
