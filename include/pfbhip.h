@@ -409,6 +409,34 @@ int pfbhip_primal_dual(pfbhip_psi *psi, pfbhip_psfconv *const *pcs /* [nband] */
                        double *x_host, double *v_host, const double *weight_host, double lam, double sigma, double tau,
                        int positivity, double tol, int maxit, pfbhip_comm *comm, pfbhip_pd_info *info);
 
+/* ---- Hogbom and Clark CLEAN (the kclean minor cycle) ------------------- */
+/*
+ * deconv/hogbom.py:9-63 and deconv/clark.py:11-143 of pfb-imaging with every cube resident in HBM (clean.hip; the semantics,
+ * quirks included, are listed in DESIGN.md "Device-resident CLEAN").  A plan holds psf (nband, nx_psf, ny_psf) and, for Clark,
+ * psfhat (nband, nx_psf, ny_psf / 2 + 1) complex (NULL: Hogbom only).  Cubes are C-ordered float64 (nband, nx, ny); mask (nx, ny).
+ * model_host receives the model, residual_host (may be NULL) the final residual.  nband <= 64.
+ */
+typedef struct pfbhip_clean pfbhip_clean;
+typedef struct pfbhip_clean_info {
+    int32_t iters;         /* Hogbom: iterations; Clark: major iterations */
+    int32_t status;        /* 1 when iters >= maxit, else 0 */
+    int64_t minor_iters;   /* Hogbom: iterations; Clark: sub-minor iterations over all major cycles */
+    int64_t idle_launches; /* step launches enqueued after the loop had stopped (batched host control) */
+    int64_t nsub_lds;      /* Clark sub-minor loops run by the one-workgroup LDS kernel */
+    int64_t nsub_grid;     /* ... and by the two-kernel grid path */
+    double rmax;           /* last peak residual */
+    double loop_ms;        /* wall time of the loop (uploads / downloads excluded) */
+    double conv_ms, search_ms, compact_ms, sub_lds_ms, sub_grid_ms; /* Clark: device time per phase (events), summed */
+} pfbhip_clean_info;
+int pfbhip_clean_create(int64_t nband, int64_t nx, int64_t ny, int64_t nx_psf, int64_t ny_psf, const double *psf_host,
+                        const double *psfhat_host, pfbhip_clean **out);
+int pfbhip_clean_destroy(pfbhip_clean *c);
+int pfbhip_clean_hogbom(pfbhip_clean *c, const double *dirty_host, double threshold, double gamma, double pf, int64_t maxit,
+                        double *model_host, double *residual_host, pfbhip_clean_info *info);
+int pfbhip_clean_clark(pfbhip_clean *c, const double *dirty_host, const double *wsums, const double *mask_host, double threshold,
+                       double gamma, double pf, int64_t maxit, double subpf, int64_t submaxit, double *model_host,
+                       double *residual_host, pfbhip_clean_info *info);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

@@ -65,6 +65,12 @@ class CGInfo(ct.Structure):
     _fields_ = [("iters", i32), ("status", i32), ("eps", f64), ("phi", f64)]
 
 
+class CleanInfo(ct.Structure):
+    _fields_ = [("iters", i32), ("status", i32), ("minor_iters", i64), ("idle_launches", i64), ("nsub_lds", i64),
+                ("nsub_grid", i64), ("rmax", f64), ("loop_ms", f64), ("conv_ms", f64), ("search_ms", f64),
+                ("compact_ms", f64), ("sub_lds_ms", f64), ("sub_grid_ms", f64)]
+
+
 # every symbol include/pfbhip.h declares (tests check the library exports all of them)
 SYMBOLS = (
     "pfbhip_last_error", "pfbhip_device_count", "pfbhip_set_device", "pfbhip_get_device", "pfbhip_device_name",
@@ -90,6 +96,7 @@ SYMBOLS = (
     "pfbhip_comm_unique_id", "pfbhip_comm_create", "pfbhip_comm_destroy", "pfbhip_comm_reduce_sum",
     "pfbhip_comm_allreduce_sum", "pfbhip_comm_allgather", "pfbhip_comm_allreduce_sum_host", "pfbhip_comm_reduce_sum_host",
     "pfbhip_comm_allgather_host", "pfbhip_comm_barrier",
+    "pfbhip_clean_create", "pfbhip_clean_destroy", "pfbhip_clean_hogbom", "pfbhip_clean_clark",
 )
 
 _lib = None
