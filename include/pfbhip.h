@@ -437,6 +437,42 @@ int pfbhip_clean_clark(pfbhip_clean *c, const double *dirty_host, const double *
                        double gamma, double pf, int64_t maxit, double subpf, int64_t submaxit, double *model_host,
                        double *residual_host, pfbhip_clean_info *info);
 
+/* ---- forward-backward (ISTA / FISTA) backward step ----------------------- */
+/* ForwardBackward.solve (src/pfb_imaging/opt/forward_backward.py:95-133; replaces its host loop over
+ * _apply_prox :83-93) with every cube resident on the device (fb.hip).  Per iteration: the forward step
+ * xg = y + (step / g) H (xtilde - y) with H as in pfbhip_primal_dual (band b: nparts[b] consecutive slots of
+ * its plan pcs[b], scale[b], eta[b]); the tight-frame prox x = xg + Psi(prox(Psi^H xg) - Psi^H xg) / nu with
+ * the l21 (reg_kind 0, prox/l21.py) or l1 (reg_kind 1, prox/l1.py) prox at threshold step * lam * weight;
+ * positivity 0 | 1 | 2; eps = ||x - xp|| / ||x|| (1 if x == 0); FISTA momentum when acceleration != 0.
+ * psi == NULL is IdentityPsi.  x0 / xtilde (nband, nx, ny); weight (nbasis, nxmax, nymax) in the PsiNocopyt
+ * layout ((nx, ny) for the identity).  All bands are on this device.
+ *
+ * The handle keeps the iterate, momentum and iteration count between runs: pfbhip_fb_run iterates from where
+ * the previous run stopped until eps < tol (status 0, a convergence event) or the loop index reaches
+ * maxit - 1 (status 1), then writes x to x_host.  The caller may replace the weight with pfbhip_fb_set_weight
+ * and run again (the on_converge protocol of forward_backward.py:111-113).  Psi's and the plans' streams are
+ * switched to the first plan's for the duration of each run; the handle must not outlive them. */
+#define PFBHIP_FB_NSTAGES 5
+typedef struct pfbhip_fb pfbhip_fb;
+typedef struct pfbhip_fb_info {
+    int32_t iters;  /* loop index of the last iteration run */
+    int32_t status; /* 0 converged, 1 maxit reached */
+    double eps;
+    double loop_ms; /* wall time of the iteration loops of all runs of the handle (uploads / downloads excluded) */
+    int64_t events; /* runs that ended with eps < tol */
+    /* device time (HIP events) and bracketed launches per stage, summed over the iterations of runs with maxit <= 64:
+     * 0 forward Hessian (one partition apply per launch), 1 Psi^H analysis, 2 shrink, 3 Psi synthesis, 4 step + norms */
+    double stage_ms[PFBHIP_FB_NSTAGES];
+    int64_t stage_calls[PFBHIP_FB_NSTAGES];
+} pfbhip_fb_info;
+int pfbhip_fb_create(pfbhip_psi *psi /* NULL: identity */, pfbhip_psfconv *const *pcs /* [nband] */, int64_t nband,
+                     const int64_t *nparts, const int64_t *psf_slots, const int64_t *beam_slots, const double *scale,
+                     const double *eta, const double *xtilde_host, double g, const double *x0_host, const double *weight_host,
+                     int reg_kind, double nu, double step, int positivity, int acceleration, pfbhip_fb **out);
+int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_host, pfbhip_fb_info *info);
+int pfbhip_fb_set_weight(pfbhip_fb *h, const double *weight_host);
+int pfbhip_fb_destroy(pfbhip_fb *h);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

@@ -57,6 +57,15 @@ class PDInfo(ct.Structure):
                 ("stage_calls", i64 * PD_NSTAGES)]
 
 
+FB_NSTAGES = 5
+FB_STAGE_NAMES = ("forward_hessian", "psi_analysis", "shrink", "psi_synthesis", "step")
+
+
+class FBInfo(ct.Structure):
+    _fields_ = [("iters", i32), ("status", i32), ("eps", f64), ("loop_ms", f64), ("events", i64), ("stage_ms", f64 * FB_NSTAGES),
+                ("stage_calls", i64 * FB_NSTAGES)]
+
+
 class PMInfo(ct.Structure):
     _fields_ = [("iters", i32), ("status", i32), ("eps", f64), ("beta", f64)]
 
@@ -97,6 +106,7 @@ SYMBOLS = (
     "pfbhip_comm_allreduce_sum", "pfbhip_comm_allgather", "pfbhip_comm_allreduce_sum_host", "pfbhip_comm_reduce_sum_host",
     "pfbhip_comm_allgather_host", "pfbhip_comm_barrier",
     "pfbhip_clean_create", "pfbhip_clean_destroy", "pfbhip_clean_hogbom", "pfbhip_clean_clark",
+    "pfbhip_fb_create", "pfbhip_fb_run", "pfbhip_fb_set_weight", "pfbhip_fb_destroy",
 )
 
 _lib = None

@@ -14,11 +14,12 @@ primal-dual step sizes (core/sara.py:200-209, deconv/pfb.py:118-126), iterated o
 """
 
 import ctypes as ct
+import time
 
 import numpy as np
 
 from . import _lib
-from ._lib import PDInfo, PMInfo, check, cint, f64, i64, lib, ptr
+from ._lib import FBInfo, PDInfo, PMInfo, check, cint, f64, i64, lib, ptr
 from .operators.psi import Psi, PsiNocopyt
 from .prox import dual_update_numba_fast, prox_21m_numba
 
@@ -41,8 +42,10 @@ class L21:
 
     def coeff_shape(self):
         """(nband, nbasis, n1, n2) in the layout of ``psi`` (the reference allocates (.., nymax, nxmax))."""
+        from .operators.psi import PsiNocopytRay
+
         p = self.psi
-        if isinstance(p, PsiNocopyt):
+        if isinstance(p, (PsiNocopyt, PsiNocopytRay)):
             return (p.nband, p.nbasis, p.nxmax, p.nymax)
         return (p.nband, p.nbasis, p.nymax, p.nxmax)
 
@@ -115,6 +118,39 @@ class PsfGrad:
         return -self.hess.dot(self.xtilde - x) / self.gamma
 
 
+def _psf_hess_bands(hess, nband):
+    """(bands, comm, local): per LOCAL band (plan, psf slots, beam slots, scale, eta) of a device-resident PSF
+    Hessian -- HessPSF (all bands here, comm None) or HessTreeRay (this rank's bands of its pool) -- or None.
+    Shared by the primal-dual and forward-backward device loops and the device power method."""
+    from .operators.hessian import HessPSF, HessTreeRay
+
+    if isinstance(hess, HessPSF) and hess.nband == nband:
+        bands = [(hess._plan, [b], [-1 if hess.beam[b] is None else b], 1.0, float(hess.eta[b])) for b in range(nband)]
+        return bands, None, list(range(nband))
+    if isinstance(hess, HessTreeRay) and hess.nband == nband:
+        pool = hess._pool
+        comm = pool.comm if (pool.comm is not None and pool.comm.world_size > 1) else None
+        # Whether THIS rank could run the device loop: RCCL transport, at least one band here (pfbhip_primal_dual /
+        # pfbhip_psfconv_power_method take nband >= 1), one correlation per band.
+        ok = comm is None or (comm.transport == "rccl" and bool(pool.local))
+        out = []
+        for b in (pool.local if ok else ()):
+            tree = getattr(pool.workers[b], "_hess", None)
+            if tree is None or tree.ncorr != 1:
+                ok = False
+                break
+            s = tree._slots(0)
+            out.append((tree._plan, s, s, 1.0 / float(tree.wsum[0]), float(tree.eta)))
+        # The choice is COLLECTIVE: the device loop's RCCL sequence (one all-reduce of a single-band coefficient cube,
+        # then one of 3 doubles, per iteration) differs from the generic loop's (cube-level psi / hess all-reduces), so a
+        # rank deciding on its own -- e.g. the ranks >= nband of a 4-band run on 8 GPUs, which hold no band -- would
+        # deadlock the others.  Every rank evaluates this, in the same place, whenever the pool is distributed.
+        if comm is not None:
+            ok = comm.min_over_ranks(1.0 if ok else 0.0) == 1.0
+        return (out, comm, list(pool.local)) if ok else None
+    return None
+
+
 class PrimalDual:
     """primal_dual.py:303-448: same constructor, ``setup`` / ``set_grad`` / ``reset`` / ``solve`` contract."""
 
@@ -149,37 +185,7 @@ class PrimalDual:
             self._v[...] = 0.0
 
     # ---- device-resident loop --------------------------------------------------------------
-    @staticmethod
-    def _hess_bands(hess, nband):
-        """(bands, comm, local): per LOCAL band (plan, psf slots, beam slots, scale, eta) of a device-resident PSF
-        Hessian -- HessPSF (all bands here, comm None) or HessTreeRay (this rank's bands of its pool) -- or None."""
-        from .operators.hessian import HessPSF, HessTreeRay
-
-        if isinstance(hess, HessPSF) and hess.nband == nband:
-            bands = [(hess._plan, [b], [-1 if hess.beam[b] is None else b], 1.0, float(hess.eta[b])) for b in range(nband)]
-            return bands, None, list(range(nband))
-        if isinstance(hess, HessTreeRay) and hess.nband == nband:
-            pool = hess._pool
-            comm = pool.comm if (pool.comm is not None and pool.comm.world_size > 1) else None
-            # Whether THIS rank could run the device loop: RCCL transport, at least one band here (pfbhip_primal_dual /
-            # pfbhip_psfconv_power_method take nband >= 1), one correlation per band.
-            ok = comm is None or (comm.transport == "rccl" and bool(pool.local))
-            out = []
-            for b in (pool.local if ok else ()):
-                tree = getattr(pool.workers[b], "_hess", None)
-                if tree is None or tree.ncorr != 1:
-                    ok = False
-                    break
-                s = tree._slots(0)
-                out.append((tree._plan, s, s, 1.0 / float(tree.wsum[0]), float(tree.eta)))
-            # The choice is COLLECTIVE: the device loop's RCCL sequence (one all-reduce of a single-band coefficient cube,
-            # then one of 3 doubles, per iteration) differs from the generic loop's (cube-level psi / hess all-reduces), so a
-            # rank deciding on its own -- e.g. the ranks >= nband of a 4-band run on 8 GPUs, which hold no band -- would
-            # deadlock the others.  Every rank evaluates this, in the same place, whenever the pool is distributed.
-            if comm is not None:
-                ok = comm.min_over_ranks(1.0 if ok else 0.0) == 1.0
-            return (out, comm, list(pool.local)) if ok else None
-        return None
+    _hess_bands = staticmethod(_psf_hess_bands)
 
     def _device_path(self):
         from .prox import positivity, positivity_band
@@ -274,6 +280,236 @@ class PrimalDual:
             np.copyto(vp, v)
         self.last = dict(iters=k, status=0 if eps < self.tol else 1, eps=eps)
         return x
+
+
+def _distributed(pool):
+    return pool is not None and pool.comm is not None and pool.comm.world_size > 1
+
+
+class ForwardBackward:
+    """forward_backward.py:21-133: same constructor, ``setup`` / ``set_grad`` / ``reset`` / ``solve`` / ``_apply_prox``.
+
+    Each iteration takes ``x = y - step grad(y)``, applies the tight-frame prox
+    ``x += Psi(prox(Psi^T x, step lam) - Psi^T x) / nu`` and ``primal_prox``, measures ``eps = ||x - xp|| / ||x||`` (1 when
+    x is all zero) and, with ``acceleration``, moves ``y`` by the FISTA momentum.  ``on_converge(x, k, eps)`` fires when
+    ``eps < tol``; the loop stops unless it returns False.
+
+    When the gradient is a ``PsfGrad`` over a single-process device Hessian (HessPSF, HessTreeRay), the regulariser an
+    ``L21`` / ``L1`` over ``Psi`` / ``PsiNocopyt`` / a single-process ``PsiNocopytRay`` / ``IdentityPsi`` and
+    ``primal_prox`` None or a positivity prox, the whole loop runs on the device (``pfbhip_fb_*``, csrc/fb.hip); a
+    convergence event hands x to ``on_converge`` on the host and resumes with the state in HBM, re-uploading the
+    regulariser's weights.  Anything else runs the reference's loop over this package's GPU operators."""
+
+    def __init__(self, tol=1e-5, maxit=1000, report_freq=10, verbosity=1, gamma=1.0, acceleration=True, on_converge=None,
+                 primal_prox=None):
+        self.tol, self.maxit, self.report_freq, self.verbosity = tol, maxit, report_freq, verbosity
+        self.gamma, self.acceleration = gamma, acceleration
+        self.on_converge, self.primal_prox = on_converge, primal_prox
+        self._grad = self._reg = None
+        self.last = None
+
+    def setup(self, prox, hessnorm):
+        """Bind the regulariser, compute the step size, size buffers."""
+        if not all(hasattr(prox, a) for a in ("psi", "nu", "prox")):
+            raise TypeError("prox does not satisfy the Regulariser protocol")
+        for name in ("dot", "hdot", "nband", "nbasis", "nxmax", "nymax"):
+            if not hasattr(prox.psi, name):
+                raise TypeError(f"prox.psi does not satisfy the PsiOperator protocol (missing {name})")
+        self._reg = prox
+        self.hessnorm = hessnorm
+        self.step = 2.0 * self.gamma / hessnorm
+        psi = prox.psi
+        shape = prox.coeff_shape() if hasattr(prox, "coeff_shape") else (psi.nband, psi.nbasis, psi.nymax, psi.nxmax)
+        self._alpha = np.zeros(shape)
+        self._alpha_buf = np.zeros_like(self._alpha)
+        self._xout = np.zeros((psi.nband, psi.nx, psi.ny))
+
+    def set_grad(self, grad):
+        self._grad = grad
+
+    def reset(self):
+        """No warm-start state beyond x itself."""
+
+    def _apply_prox(self, x, lam):
+        """Tight-frame prox of ``lam * g(Psi^T x)`` in place on x (forward_backward.py:83-93), then primal_prox."""
+        reg = self._reg
+        reg.psi.dot(x, self._alpha)
+        reg.prox(self._alpha, self._alpha_buf, self.step * lam, sigma=1.0)
+        self._alpha_buf -= self._alpha
+        reg.psi.hdot(self._alpha_buf, self._xout)
+        x += self._xout / reg.nu
+        if self.primal_prox is not None:
+            self.primal_prox(x)
+        return x
+
+    # ---- device-resident loop --------------------------------------------------------------
+    @staticmethod
+    def _psi_handle(psi):
+        """(pfbhip_psi handle or None for the identity, transposed) of a dictionary the device loop takes, else None."""
+        from .operators.psi import IdentityPsi, PsiNocopytRay
+
+        if isinstance(psi, IdentityPsi):
+            return None, False
+        if isinstance(psi, (Psi, PsiNocopyt)):
+            return psi._band._h, isinstance(psi, Psi)
+        if isinstance(psi, PsiNocopytRay):
+            pool = psi._pool
+            if _distributed(pool) or sorted(pool.local) != list(range(psi.nband)):
+                return None
+            bands = [getattr(pool.workers[b], "_psib", None) for b in pool.local]
+            if any(p is None for p in bands):
+                return None
+            geo = {(p.nx, p.ny, p.nbasis, p.nlevel, p.nxmax, p.nymax) for p in bands}
+            if len(geo) != 1:
+                return None
+            # every band's PsiBand has the same geometry: one handle serves all bands (as _PsiCube does)
+            return bands[0]._h, False
+        return None
+
+    def _device_path(self):
+        """The positivity mode (0 / 1 / 2) of the device loop, or None when the solve takes the generic loop.  A
+        distributed pool (world_size > 1) always takes the generic loop: decided from world_size alone, no collective."""
+        from .operators.hessian import HessTreeRay
+        from .prox import positivity, positivity_band
+
+        g, reg = self._grad, self._reg
+        if not (isinstance(g, PsfGrad) and isinstance(reg, (L21, L1))):
+            return None
+        mode = {None: 0, positivity: 1, positivity_band: 2}.get(self.primal_prox, None)
+        if mode is None or self._psi_handle(reg.psi) is None:
+            return None
+        if isinstance(g.hess, HessTreeRay) and _distributed(g.hess._pool):
+            return None
+        if _psf_hess_bands(g.hess, reg.psi.nband) is None:
+            return None
+        return mode
+
+    def _device_weight(self, transposed):
+        """The regulariser's current weight in the device's layout: (nbasis, nxmax, nymax) for a wavelet dictionary (the
+        weight of ``Psi`` is transposed from its (nbasis, nymax, nxmax)), (1, nx, ny) for the identity."""
+        from .operators.psi import IdentityPsi
+
+        reg, psi = self._reg, self._reg.psi
+        w = np.asarray(reg.l1weight if isinstance(reg, L21) else reg.weight, dtype=np.float64)
+        if isinstance(psi, IdentityPsi):
+            return np.ascontiguousarray(np.broadcast_to(w, (1, psi.nx, psi.ny)))
+        if transposed:
+            return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nymax, psi.nxmax)).transpose(0, 2, 1))
+        return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nxmax, psi.nymax)))
+
+    def _solve_device(self, x, lam, mode):
+        reg, psi, g = self._reg, self._reg.psi, self._grad
+        handle, transposed = self._psi_handle(psi)
+        bands, _, _ = _psf_hess_bands(g.hess, psi.nband)
+        nband = len(bands)
+        x0 = np.ascontiguousarray(x, dtype=np.float64)
+        xt = np.ascontiguousarray(g.xtilde, dtype=np.float64)
+        if x0.shape != (nband, psi.nx, psi.ny) or xt.shape != x0.shape:
+            raise ValueError(f"x {x0.shape} / xtilde {xt.shape}: expected {(nband, psi.nx, psi.ny)}")
+        handles = (ct.c_void_p * nband)(*[b[0]._h for b in bands])
+        nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
+        psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
+        beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
+        scale = np.array([b[3] for b in bands], dtype=np.float64)
+        eta = np.array([b[4] for b in bands], dtype=np.float64)
+        kind = 0 if isinstance(reg, L21) else 1
+        h = ct.c_void_p()
+        check(lib().pfbhip_fb_create(handle, handles, i64(nband), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale),
+                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(self._device_weight(transposed)), cint(kind),
+                                     f64(reg.nu), f64(self.step), cint(mode), cint(1 if self.acceleration else 0),
+                                     ct.byref(h)))
+        info = FBInfo()
+        try:
+            while True:
+                out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
+                check(lib().pfbhip_fb_run(h, f64(lam), f64(self.tol), cint(self.maxit), ptr(out), ct.byref(info)))
+                if info.status != 0 or self.on_converge is None or self.on_converge(out, int(info.iters), float(info.eps)):
+                    break
+                if info.iters >= self.maxit - 1:
+                    break
+                # on_converge may have replaced the weights (ReweightOnConverge -> update_weights): resume with them
+                check(lib().pfbhip_fb_set_weight(h, ptr(self._device_weight(transposed))))
+        finally:
+            lib().pfbhip_fb_destroy(h)
+        self.last = dict(iters=int(info.iters), status=0 if info.eps < self.tol else 1, eps=float(info.eps),
+                         loop_ms=float(info.loop_ms), events=int(info.events),
+                         stages={n: (float(info.stage_ms[i]), int(info.stage_calls[i]))
+                                 for i, n in enumerate(_lib.FB_STAGE_NAMES)})
+        return out
+
+    def solve(self, x, lam):
+        """Run the forward-backward loop; returns the final iterate (a new array)."""
+        if self._reg is None:
+            raise RuntimeError("regulariser not bound; call setup() before solve()")
+        if self._grad is None:
+            raise RuntimeError("grad not set; call set_grad() before solve()")
+        _lib.require_gpu()
+        mode = self._device_path()
+        if mode is not None:
+            return self._solve_device(x, lam, mode)
+        x = np.array(x, dtype=np.float64)
+        xp, y = x.copy(), x.copy()
+        t, eps, k, events = 1.0, 1.0, 0, 0
+        t0 = time.perf_counter()
+        for k in range(self.maxit):
+            x = y - self.step * self._grad(y)
+            x = self._apply_prox(x, lam)
+            eps = float(np.sqrt(((x - xp) ** 2).sum() / max(float((x**2).sum()), 1e-12))) if _lib.any_nonzero(x) else 1.0
+            if eps < self.tol:
+                events += 1
+                if self.on_converge is None or self.on_converge(x, k, eps):
+                    break
+            if self.acceleration:
+                tp = t
+                t = (1.0 + np.sqrt(1.0 + 4.0 * tp**2)) / 2.0
+                y = x + (tp - 1.0) / t * (x - xp)
+            else:
+                np.copyto(y, x)
+            np.copyto(xp, x)
+        self.last = dict(iters=k, status=0 if eps < self.tol else 1, eps=eps, loop_ms=(time.perf_counter() - t0) * 1e3,
+                         events=events, stages={})
+        return x
+
+
+def fista(x0, hessnorm, fprime, prox, tol=1e-3, maxit=100, report_freq=50, verbosity=1):
+    """The legacy FISTA solver of ``min_x f(x) + R(x)`` (opt/fista.py:13-95), kept by the reference as the oracle for
+    ``ForwardBackward``.  ``fprime(x)`` returns ``(f(x), grad f(x))``, ``prox(x)`` the prox of R at the implicit step
+    ``1 / hessnorm``.  When a step raises f, ``hessnorm`` doubles and the step is retried, up to 10 times; after the 10th
+    retry the solver stops ("stalled").  Otherwise it stops on ``||x - xp|| / ||x|| < tol`` or after ``maxit`` iterations.
+    Pure composition of the caller's callables (GPU when they are this package's)."""
+    t, eps, k = 1.0, 1.0, 0
+    x, y = np.array(x0, copy=True), np.array(x0, copy=True)
+    fidp, gradp = fprime(x)
+    for k in range(maxit):
+        xp = x.copy()
+        x = prox(y - gradp / hessnorm)
+        fidn, gradn = fprime(x)
+        tries = 0
+        while fidn > fidp and tries < 10:
+            hessnorm *= 2.0
+            if verbosity > 1:
+                print(f"Step size too large, adjusting {hessnorm:f}")
+            x = prox(y - gradp / hessnorm)
+            fidn, gradn = fprime(x)
+            tries += 1
+        if tries == 10:
+            if verbosity > 1:
+                print("Stalled")
+            k = maxit - 1
+            break
+        tp = t
+        t = (1.0 + np.sqrt(1.0 + 4.0 * tp**2)) / 2.0
+        y = x + (tp - 1.0) / t * (x - xp)
+        eps = np.linalg.norm(x - xp) / np.linalg.norm(x)
+        if eps < tol:
+            break
+        fidp, gradp = fidn, gradn
+        if verbosity > 1 and not k % report_freq:
+            print(f"At iteration {k} eps = {eps:f}")
+    if verbosity:
+        print(f"Maximum iterations reached. Relative difference between updates = {eps:f}" if k == maxit - 1
+              else f"Success, converged after {k} iterations")
+    return x
 
 
 def primal_dual_numba(x, v, lam, psih, psi, hessnorm, prox, l1weight, reweighter, grad, nu=1.0, sigma=None, mask=None,
@@ -371,7 +607,7 @@ def _pm_device(aop, imsize, b):
             return b
         return call
     if isinstance(owner, (HessPSF, HessTreeRay)) and fn is type(owner).dot and len(imsize) == 3:
-        hb = PrimalDual._hess_bands(owner, imsize[0])
+        hb = _psf_hess_bands(owner, imsize[0])
         if hb is None:
             return None
         bands, comm, local = hb
