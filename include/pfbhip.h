@@ -257,6 +257,9 @@ int pfbhip_psfconv_apply_dev(pfbhip_psfconv *p, const double *x_dev, int64_t psf
  * receives the estimate before the beam division, out_host after it. */
 int pfbhip_psfconv_direct(pfbhip_psfconv *p, const double *x_host, int64_t psf_slot, int64_t taper_slot, double shift,
                           int64_t beam_slot, double min_beam, double *raw_host, double *out_host);
+/* Diagnostic: *out = 1 when the plan runs the three-pass row-FFT pipeline (both padded sizes are plain row-FFT lengths), 0 when it
+ * runs the rocFFT 2-D r2c / c2r fallback.  Fixed at create time. */
+int pfbhip_psfconv_uses_rowfft(const pfbhip_psfconv *p, int *out);
 
 /* Single-precision host arrays: the reference's precision="single" (vis2im / im2vis, operators/gridder.py:58-100:
  * complex64 visibilities, float32 weights and images) with double-precision accumulation (ducc0's

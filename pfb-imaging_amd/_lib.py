@@ -99,7 +99,7 @@ SYMBOLS = (
     "pfbhip_l21_scale_dev", "pfbhip_prox_21m", "pfbhip_positivity", "pfbhip_positivity_dev", "pfbhip_primal_dual",
     "pfbhip_psfconv_power_method", "pfbhip_gridder_power_method",
     "pfbhip_psfconv_create", "pfbhip_psfconv_destroy", "pfbhip_psfconv_set_psfhat", "pfbhip_psfconv_set_beam",
-    "pfbhip_psfconv_apply", "pfbhip_psfconv_apply_dev", "pfbhip_psfconv_direct", "pfbhip_psfconv_cg",
+    "pfbhip_psfconv_apply", "pfbhip_psfconv_apply_dev", "pfbhip_psfconv_direct", "pfbhip_psfconv_cg", "pfbhip_psfconv_uses_rowfft",
     "pfbhip_uvcell_index", "pfbhip_compute_counts", "pfbhip_counts_divide", "pfbhip_box_sum_counts",
     "pfbhip_filter_extreme_counts", "pfbhip_imaging_weights",
     "pfbhip_comm_unique_id", "pfbhip_comm_create", "pfbhip_comm_destroy", "pfbhip_comm_reduce_sum",
@@ -129,6 +129,7 @@ def lib():
         L.pfbhip_thread_pool_size.restype = cint
         L.pfbhip_hash64.restype = ct.c_uint64
         L.pfbhip_hash64.argtypes = [ct.c_void_p, ct.c_size_t]
+        L.pfbhip_psfconv_uses_rowfft.argtypes = [ct.c_void_p, ct.POINTER(cint)]
         _lib = L
     return _lib
 

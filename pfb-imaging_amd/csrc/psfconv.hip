@@ -387,6 +387,14 @@ int pfbhip_psfconv_cg(pfbhip_psfconv *p, int64_t nparts, const int64_t *psf_slot
     });
 }
 
+int pfbhip_psfconv_uses_rowfft(const pfbhip_psfconv *p, int *out)
+{
+    return guarded([&] {
+        PFB_REQUIRE(p && out, "NULL argument");
+        *out = p->own.ok ? 1 : 0;
+    });
+}
+
 // ---- stand-alone r2c / c2r (host arrays) ------------------------------------------------
 
 // out[k0][k1] *= (-1)^(k0 + k1): the spectrum of ifftshift(x) from the spectrum of x when both lengths are even

@@ -11,8 +11,12 @@
 //      imaginary parts, crop, beam, scale, eta
 // Nothing outside the nx x nyo2 corner is ever stored: ~6 GB of traffic at 8192^2 / 16384^2 where the
 // padded r2c / c2r pipeline moves ~24 GB.  Padded sizes: ny_psf any plain row-FFT size ({1,3,5,7,9,15} x 2^a, 1024..16384);
-// nx_psf a power of two (the two transforms of pass 2 chain in registers) or {3,5} x 2^a <= 10240 (they hand the row
-// over through LDS).
+// nx_psf a power of two (the two transforms of pass 2 chain in registers) or {3,5,7,9,15} x 2^a <= 10240 (they hand the
+// row over through LDS).
+// Precondition on psfhat: its ky = 0 and ky = nyp / 2 columns are conjugate-symmetric in kx (psfhat[(nxp - kx) % nxp] ==
+// conj(psfhat[kx]); a real psfhat: even in kx), as rfft2 of a real PSF and its modulus are.  Pass 3 extends the half
+// spectrum as it stands, so an imaginary part left on those two columns leaks into the partner row of the pair, where
+// numpy's irfft2 drops it.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -35,6 +35,14 @@ class PsfConv:
         except Exception:
             pass
 
+    @property
+    def uses_rowfft(self):
+        """True when this plan runs the three-pass row-FFT pipeline (csrc/psffft.hip), False when it runs the rocFFT
+        2-D r2c / c2r fallback; fixed when the plan is created."""
+        v = cint(0)
+        check(lib().pfbhip_psfconv_uses_rowfft(self._h, ct.byref(v)))
+        return bool(v.value)
+
     def set_psfhat(self, slot, psfhat):
         psfhat = np.asarray(psfhat)
         if psfhat.shape != (self.nx_psf, self.nyo2):

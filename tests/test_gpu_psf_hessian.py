@@ -394,6 +394,95 @@ def test_psfconv_rowfft_pipeline(is_complex, nx, nxp, nyp, monkeypatch):
         assert rel(results[(None, i)], results[("0", i)]) < 1e-12
 
 
+def test_operator_family_on_the_rowfft_geometry():
+    """The operator family at padded sizes the row-FFT pipeline takes (600 x 520 -> 1280 x 1024; the small cases above run the
+    rocFFT fallback): psf_convolve_slice / cube / fscube, hessian_psf_slice / cube, hess_direct_slice, HessPSF.dot / idot (the
+    direct estimate: taper and beam division), HessianTree over several parts, HessTreeRay + cg, pcg_psf and the device power
+    method, against the numpy restatement."""
+    from pfb_imaging_amd import psfconv
+    from pfb_imaging_amd.operators.hessian import (HessianTree, HessPSF, HessTreeRay, hess_direct_slice, hessian_psf_cube,
+                                                   hessian_psf_slice, taperf)
+    from pfb_imaging_amd.operators.psf import psf_convolve_cube, psf_convolve_fscube, psf_convolve_slice
+    from pfb_imaging_amd.opt import pcg_psf, power_method
+
+    nband, nx, ny, nxp, nyp = 2, 600, 520, 1280, 1024
+    key = (nx, ny, nxp, nyp)
+    psf, psfhat, abspsf, x, beam = _psf_case(nband=nband, nx=nx, ny=ny, nxp=nxp, nyp=nyp, seed=21)
+    # psf_convolve_*
+    ref = fftconv.psf_convolve(x, psfhat, nxp, nyp)
+    xout = np.zeros((nx, ny))
+    psf_convolve_slice(None, None, xout, psfhat[0], nyp, x[0])
+    assert psfconv._plans[key].uses_rowfft
+    assert rel(xout, ref[0]) < 1e-11
+    cube = np.zeros_like(x)
+    psf_convolve_cube(None, None, cube, psfhat, nyp, x)
+    assert rel(cube, ref) < 1e-11
+    fs = np.zeros((nband, 1, nx, ny))
+    psf_convolve_fscube(None, None, fs, psfhat[:, None], nyp, x[:, None])
+    assert rel(fs[:, 0], ref) < 1e-11
+    # hessian_psf_slice / cube, hess_direct_slice
+    for bm, eta in ((None, None), (beam[0], 0.3)):
+        got = hessian_psf_slice(x[0], xout=np.zeros_like(x[0]), abspsf=abspsf[0], beam=bm, lastsize=nyp, eta=eta)
+        assert rel(got, fftconv.hessian_psf_slice(x[0], abspsf[0], nyp, beam=bm, eta=eta)) < 1e-11
+    got = hessian_psf_cube(None, None, np.zeros_like(x), beam, abspsf, nyp, x, eta=0.2)
+    assert rel(got, fftconv.hess_psf_dot(x, abspsf, nyp, beam=beam, eta=0.2)) < 1e-11
+    assert psfconv._plans[key].uses_rowfft
+    taper = taperf((nx, ny), 32)
+    for mode in ("forward", "backward"):
+        got = hess_direct_slice(x[0], xout=np.zeros_like(x[0]), abspsf=abspsf[0], taperxy=taper, lastsize=nyp, eta=2.5,
+                                mode=mode)
+        assert rel(got, fftconv.hess_direct_slice(x[0], abspsf[0], nyp, taper, 2.5, mode)) < 1e-10
+    # HessPSF.dot / idot
+    wabs = 1.0 + 0.2 * abspsf / abspsf.max()
+    eta = np.array([0.1, 0.2])
+    h = HessPSF(nx, ny, wabs, beam=beam, eta=eta, cgtol=1e-10, cgmaxit=400)
+    assert h._plan.uses_rowfft
+    hx = fftconv.hess_psf_dot(x, wabs, nyp, beam=beam, eta=eta)
+    assert rel(h.dot(x), hx) < 1e-11
+    assert rel(h.idot(hx.copy(), mode="psf"), x) < 1e-6
+    d = h.idot(hx.copy(), mode="direct")
+    want = np.stack([fftconv.hess_direct_slice(hx[b], wabs[b], nyp, h.taperxy, eta[b] * np.sqrt(nx * ny), "backward") for b in range(nband)])
+    msk = (want > 0) & (beam > h.min_beam)
+    want[msk] /= beam[msk] ** 2
+    assert msk.any() and (~msk).any() and rel(d, want) < 1e-10
+    # HessianTree over three parts, two correlations
+    parts = _tree_parts(nx, ny, nxp, nyp, 3, 2, 22)
+    x2 = np.random.default_rng(23).standard_normal((2, nx, ny))
+    t = HessianTree(parts, nx, ny, nxp, nyp, eta=0.2, wsum=7.0)
+    assert t._plan.uses_rowfft
+    assert rel(t.dot(x2), fftconv.hessian_tree_dot(x2, parts, nxp, nyp, eta=0.2, wsum=7.0)) < 1e-11
+    # HessTreeRay + cg (on-device CG over the slot lists of each band)
+    ppb = [_tree_parts(nx, ny, nxp, nyp, 2, 1, 30 + b) for b in range(nband)]
+    for p in ppb:
+        for q in p:
+            q["psfhat"] = 1.0 + 0.3 * q["psfhat"] / q["psfhat"].max()
+    wsum_tot = sum(sum(q["wsum"][0] for q in p) for p in ppb)
+    hr = HessTreeRay(ppb, nx, ny, nxp, nyp, etas=eta, wsums=wsum_tot, cg_tol=1e-10, cg_maxit=300)
+
+    def tree_op(z):
+        return np.stack([fftconv.hessian_tree_dot(z[b], ppb[b], nxp, nyp, eta=eta[b], wsum=wsum_tot)[0] for b in range(nband)])
+
+    hrx = hr.dot(x)
+    assert rel(hrx, tree_op(x)) < 1e-11
+    sol = hr.cg(hrx, tol=1e-10, maxit=300, minit=1)
+    assert rel(sol, x) < 1e-6
+    # pcg_psf
+    rhs = fftconv.hess_psf_dot(x, wabs, nyp, beam=beam, eta=eta)
+    sol = pcg_psf(wabs, rhs, np.zeros_like(rhs), beam, nyp, 1, eta, dict(tol=1e-11, maxit=400, minit=1, verbosity=0))
+    assert psfconv._plans[key].uses_rowfft
+    assert rel(sol, x) < 1e-7
+    # the device power method on HessPSF.dot and HessTreeRay.dot, a fixed number of iterations
+    rng = np.random.default_rng(24)
+    b0 = rng.standard_normal(x.shape)
+    beta, b = power_method(h.dot, x.shape, b0=b0, tol=0.0, maxit=15, verbosity=0)
+    rbeta, rb, _ = fftconv.power_method(lambda z: fftconv.hess_psf_dot(z, wabs, nyp, beam=beam, eta=eta), x.shape, b0.copy(),
+                                        tol=0.0, maxit=15)
+    assert abs(beta - rbeta) < 1e-11 * abs(rbeta) and rel(b, rb) < 1e-9
+    betat, bt = power_method(hr.dot, x.shape, b0=b0, tol=0.0, maxit=15, verbosity=0)
+    rbt, rbv, _ = fftconv.power_method(tree_op, x.shape, b0.copy(), tol=0.0, maxit=15)
+    assert abs(betat - rbt) < 1e-11 * abs(rbt) and rel(bt, rbv) < 1e-9
+
+
 def test_power_method_on_device():
     """power_method (opt/power_method.py:40-148) as called for hess_norm (core/sara.py:200-209): the device-resident
     iteration on HessPSF.dot / HessTreeRay.dot against the numpy restatement around the oracle's Hessian, the host
