@@ -447,6 +447,35 @@ __device__ __forceinline__ void hess_frame_steps(const double (&ks)[NJ], const d
     }
 }
 
+// The fused Hessian kernel's row walk with the tile reads in flight: rows 0 .. PD - 1 of the footprint are in pf[] when the walk
+// starts (hess_issue_rows, issued a whole round ahead from the NEXT record's key), and step I, once it has used slot I mod PD,
+// refills it with row I + PD.  Same FMAs in the same order as wd_steps; the sched_barrier keeps each refill inside its own
+// step (without it the compiler folds the reads back onto two registers, each read waited for at once), so its counted
+// lgkmcnt waits leave the younger reads in flight.
+template <int PD>
+__device__ __forceinline__ void hess_issue_rows(const char *base, double2 (&pf)[PD])
+{
+#pragma unroll
+    for (int r = 0; r < PD; ++r) pf[r] = *reinterpret_cast<const double2 *>(base + size_t(r) * RW_LS * 16);
+}
+
+template <int W, int NJ, int PD, int I>
+__device__ __forceinline__ void hess_walk_steps(const char *base, const double (&ku)[NJ], double (&tr)[NJ], double (&ti)[NJ],
+                                                double2 (&pf)[PD])
+{
+    if constexpr (I < W) {
+        const double2 cell = pf[I % PD];
+#pragma unroll
+        for (int r = 0; r < NJ; ++r) {
+            fmac_row_bcast<I>(tr[r], ku[r], cell.x);
+            fmac_row_bcast<I>(ti[r], ku[r], cell.y);
+        }
+        if constexpr (I + PD < W) pf[I % PD] = *reinterpret_cast<const double2 *>(base + size_t(I + PD) * RW_LS * 16);
+        __builtin_amdgcn_sched_barrier(0);
+        hess_walk_steps<W, NJ, PD, I + 1>(base, ku, tr, ti, pf);
+    }
+}
+
 // register budget of the gather: 768 threads per CU (168 VGPRs: the three / four coefficient sets of K >= 3 do not fit the 128 of
 // 1024 threads), launched as three workgroups of 256 (one wave per SIMD each: a workgroup's tile load -- 19 % of an item's
 // cycles -- overlaps the other two's rounds; C2: 1.90 -> 1.64 ms)
@@ -628,6 +657,9 @@ __global__ void __launch_bounds__(wd_gather_threads(NJ)) k_degrid_wd(GroupArgs g
 //            sum_r a_r(f - du) P_r(b): the same broadcast FMA with the u-values moved by du lanes (one ds_bpermute).
 // The frame (W + BC - 1 <= 16 rows of 16 columns, 32 doubles per lane) is flushed into the LDS output tile with ds_add when
 // the row's block changes.  Input plane: the 48 x 48 tile of k_degrid_wd in LDS; output: k_grid_wd's tile and flush.
+// Two waves per SIMD do not hide an LDS round trip or a dependent trip to memory, so the kernel does not make exposed ones:
+// the walk's tile rows are requested a round ahead and refilled inside the walk (hess_issue_rows / hess_walk_steps,
+// wd_hess_read_depth rows in flight), and every request of the prologue is issued before its first wait.
 // Launched with 256 threads; two workgroups (71 KB of LDS each at W = 15) and two waves per SIMD.  The 512 of __launch_bounds__ is
 // the REGISTER CAP, not the launch size: it holds the compiler to <= 256 VGPRs per lane (two waves per SIMD); with 256 it may
 // allocate up to 512 (one wave per SIMD, and the second workgroup would not fit beside the first).
@@ -635,6 +667,14 @@ __host__ __device__ constexpr bool wd_hess_fits(int W, int BC) { return W + BC -
 __host__ __device__ constexpr size_t wd_hess_lds_bytes(int W)
 {
     return size_t(2) * blk_tile_rows(W) * wd_stride(W) * sizeof(double) + size_t(RW_LS) * RW_LS * 16;
+}
+
+// Tile rows the row walk keeps in flight (4 VGPRs each, and live across the frame's FMAs): 8 where the registers are there.  The
+// K = 4 kernels of wide supports sit a few registers under the cap of 256 (a 257th would spill: the occupancy is fixed by
+// __launch_bounds__): they keep 4 (W = 10 .. 12) or the 2 rows the walk always held (W >= 13), still issued a round ahead.
+__host__ __device__ constexpr int wd_hess_read_depth(int W, int NJ)
+{
+    return NJ >= 4 && W >= 13 ? 2 : NJ >= 4 && W >= 10 ? 4 : W < 8 ? W : 8;
 }
 
 template <int W, int NJ, int BC>
@@ -650,6 +690,7 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
     constexpr int FP = W + BC - 1;
     static_assert(BC == 2 || BC == 4, "block edge: 2 or 4 cells");
     static_assert(wd_hess_fits(W, BC), "frame wider than a 16-lane row");
+    constexpr int PD = wd_hess_read_depth(W, NJ);
     extern __shared__ double lds[];
     double2 *tin = reinterpret_cast<double2 *>(lds + 2 * LL);
 
@@ -658,7 +699,7 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
     const WorkItem wi = a.work[item];
     const int bu = int(wi.tile / uint32_t(a.ntv)) * TILE;
     const int bv = int(wi.tile % uint32_t(a.ntv)) * TILE;
-    const int NT = int(blockDim.x);
+    constexpr int NT = 256;  // the launch size (wd_launch_hessian)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = lane & 15, g = lane >> 4, rowl = lane & ~15;
     // visibilities of this row: stream s = 4 wave + g of NS, a contiguous slice of the item
@@ -671,44 +712,62 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
     auto load_key = [&](uint32_t jj) { return rec[min(jj, jlast)].key; };
     double2 z = load_z(j);
     int key = load_key(j);
-    double wv = j < jend ? swgt[min(j, jlast)] : 0.0;
+    // One trip to memory for the whole prologue: the first record, the input tile (as k_degrid_wd's; every load from a
+    // clamped, wrapped address, zeroed by select once it is here) and the lane's coefficients (tap min(b, W - 1), zeroed
+    // likewise) are all requested before anything waits, and the output tile is cleared under their flight.
+    const double wv0 = swgt[min(j, jlast)];
     double2 cwv[NJ];
 #pragma unroll
     for (int k = 0; k < NJ; ++k) cwv[k] = wa.cw[size_t(min(j, jlast)) * NJ + k];
-
-    for (int i = threadIdx.x; i < 2 * LL; i += NT) lds[i] = 0.0;
-    for (int i0 = 0; i0 < LLI; i0 += 4 * NT) {  // input tile, as k_degrid_wd
-        double2 v[4];
-        int idx[4];
+    constexpr int NLD = (LLI + NT - 1) / NT;  // 9 cells of the 48 x 48 input tile per thread
+    double2 tv[NLD];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + int(threadIdx.x) + q * NT;
-            idx[q] = i;
-            const int ic = min(i, LLI - 1);
-            const int la = ic / RW_LS, lb = ic - la * RW_LS;
-            int gu = bu + la, gv = bv + lb;
-            gu = gu >= a.nu ? gu % a.nu : gu;
-            gv = gv >= a.nv ? gv % a.nv : gv;
-            const bool in = i < LLI && la < L && lb < L;
-            const double2 t = gin[size_t(gu) * size_t(a.apitch) + size_t(gv)];
-            v[q] = in ? t : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (idx[q] < LLI) tin[idx[q]] = v[q];
+    for (int q = 0; q < NLD; ++q) {
+        const int ic = min(int(threadIdx.x) + q * NT, LLI - 1);
+        const int la = ic / RW_LS, lb = ic - la * RW_LS;
+        int gu = bu + la, gv = bv + lb;
+        gu = gu >= a.nu ? gu % a.nu : gu;
+        gv = gv >= a.nv ? gv % a.nv : gv;
+        tv[q] = gin[size_t(gu) * size_t(a.apitch) + size_t(gv)];
     }
     double c0[D + 1], c1[D - 1], c2[NJ > 2 ? D - 3 : 1], c3[NJ > 3 ? D - 5 : 1];
+    const int bt = min(b, W - 1);
 #pragma unroll
-    for (int q = 0; q <= D; ++q) c0[q] = b < W ? wa.dtab[(size_t(0) * W + b) * (D + 1) + q] : 0.0;
+    for (int q = 0; q <= D; ++q) c0[q] = wa.dtab[(size_t(0) * W + bt) * (D + 1) + q];
 #pragma unroll
-    for (int q = 0; q <= D - 2; ++q) c1[q] = b < W ? wa.dtab[(size_t(1) * W + b) * (D + 1) + q] : 0.0;
+    for (int q = 0; q <= D - 2; ++q) c1[q] = wa.dtab[(size_t(1) * W + bt) * (D + 1) + q];
     if constexpr (NJ > 2) {
 #pragma unroll
-        for (int q = 0; q <= D - 4; ++q) c2[q] = b < W ? wa.dtab[(size_t(2) * W + b) * (D + 1) + q] : 0.0;
+        for (int q = 0; q <= D - 4; ++q) c2[q] = wa.dtab[(size_t(2) * W + bt) * (D + 1) + q];
     }
     if constexpr (NJ > 3) {
 #pragma unroll
-        for (int q = 0; q <= D - 6; ++q) c3[q] = b < W ? wa.dtab[(size_t(3) * W + b) * (D + 1) + q] : 0.0;
+        for (int q = 0; q <= D - 6; ++q) c3[q] = wa.dtab[(size_t(3) * W + bt) * (D + 1) + q];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    for (int i = threadIdx.x; i < 2 * LL; i += NT) lds[i] = 0.0;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+        const int i = int(threadIdx.x) + q * NT;
+        const int la = i / RW_LS, lb = i - la * RW_LS;
+        const bool in = la < L && lb < L;
+        if (NLD * NT == LLI || i < LLI) tin[i] = in ? tv[q] : make_double2(0.0, 0.0);
+    }
+    double wv = j < jend ? wv0 : 0.0;
+    if (b >= W) {
+#pragma unroll
+        for (int q = 0; q <= D; ++q) c0[q] = 0.0;
+#pragma unroll
+        for (int q = 0; q <= D - 2; ++q) c1[q] = 0.0;
+        if constexpr (NJ > 2) {
+#pragma unroll
+            for (int q = 0; q <= D - 4; ++q) c2[q] = 0.0;
+        }
+        if constexpr (NJ > 3) {
+#pragma unroll
+            for (int q = 0; q <= D - 6; ++q) c3[q] = 0.0;
+        }
     }
     auto evens = [](const auto &c, auto deg, double zz) {
         constexpr int DG = decltype(deg)::value;
@@ -748,12 +807,21 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
     __syncthreads();
 
     const char *tbase = reinterpret_cast<const char *>(tin);
+    // first frame-aligned cell of a record's footprint, this lane's column (every record of the item lies inside the tile)
+    auto walk_base = [&](int k) {
+        const int klu = k >> 8, klv = k & 255;
+        return tbase + (klu * RW_LS + (klv - (klv & (BC - 1))) + b) * 16;
+    };
+    double2 pf[PD];  // tile rows in flight: the first PD rows of the round to come
+    const char *base = walk_base(key);
+    if (niter > 0) hess_issue_rows<PD>(base, pf);
     for (uint32_t it = 0; it < niter; ++it) {
         const bool valid = j < jend;
         const uint32_t jn = j + 1;
         const double2 nz = load_z(jn);
         const int nkey = load_key(jn);
-        const double nwv = jn < jend ? swgt[min(jn, jlast)] : 0.0;
+        const double nwv0 = swgt[min(jn, jlast)];
+        const double nwv = jn < jend ? nwv0 : 0.0;
         double2 ncw[NJ];
 #pragma unroll
         for (int k = 0; k < NJ; ++k) ncw[k] = wa.cw[size_t(min(jn, jlast)) * NJ + k];
@@ -770,13 +838,13 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
             for (int r = 0; r < NJ; ++r) B[r] = __shfl(kvb[r], rowl + ((b - dv) & 15));
 #pragma unroll
             for (int r = 0; r < NJ; ++r) ks[r] = __shfl(ku[r], rowl + ((b - du) & 15));
-            const char *base = tbase + (lu * RW_LS + c0c + b) * 16;
             double tr[NJ], ti[NJ];
 #pragma unroll
             for (int r = 0; r < NJ; ++r) tr[r] = ti[r] = 0.0;
 #pragma unroll
             for (int r = 0; r < NJ; ++r) asm volatile("s_nop 1" : "+v"(ku[r]));  // VALU write -> DPP read needs 2 wait states
-            wd_steps<W, NJ, 0>(base, ku, tr, ti);
+            __builtin_amdgcn_sched_barrier(0);  // the shuffles above are queued before the walk's refills, not among them
+            hess_walk_steps<W, NJ, PD, 0>(base, ku, tr, ti, pf);
             double sr[NJ], si[NJ];
             double vr = 0.0, vi = 0.0;
 #pragma unroll
@@ -810,6 +878,12 @@ __global__ void __launch_bounds__(512) k_hess_wd(GroupArgs ga, WdArgs wa, const 
                 if (cur >= 0) flush();
                 cur = blk;
             }
+            // the next round's first rows, behind the flush's ds_add in the queue and under the frame's FMAs (no LDS reads of
+            // their own), the next round's kernel values and shuffles.  Past the row's slice the clamped record is still one
+            // of this item: its rows lie inside the tile.
+            base = walk_base(nkey);
+            hess_issue_rows<PD>(base, pf);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < NJ; ++r) asm volatile("s_nop 1" : "+v"(ks[r]));
             hess_frame_steps<FP, NJ, 0>(ks, pr, pim, fre, fim);
