@@ -412,6 +412,56 @@ int pfbhip_primal_dual(pfbhip_psi *psi, pfbhip_psfconv *const *pcs /* [nband] */
                        double *x_host, double *v_host, const double *weight_host, double lam, double sigma, double tau,
                        int positivity, double tol, int maxit, pfbhip_comm *comm, pfbhip_pd_info *info);
 
+/* The same solve as a resumable handle, for PrimalDual.solve with an on_converge callback (primal_dual.py:430-435; the
+ * callback the reference's PFBSolver installs is ReweightOnConverge, deconv/pfb.py:14-54, 132-136).  pfbhip_pd_create takes
+ * the description of pfbhip_primal_dual (no communicator: all nband bands are on this device), uploads x, v, xtilde and the
+ * weight once (weight_host == NULL: the caller sets it before the first run) and keeps x, xp, v, vp, the extrapolated dual, the weight and the loop index in HBM.  pfbhip_pd_run iterates
+ * from where the previous run stopped until eps < tol (status 0, a convergence event) or the loop index reaches maxit - 1
+ * (status 1) and writes x only to x_host; a run after an event continues as the reference's loop does when on_converge
+ * returns False: xp <- x, vp <- v, the index goes on, maxit bounds the total.  Between runs the caller may replace the
+ * weight from host (pfbhip_pd_set_weight) or device memory (pfbhip_pd_set_weight_dev: a copy, the handle keeps its own
+ * buffer) and read the iterate in place (pfbhip_pd_iterate_dev: valid until the next run or the destroy).
+ * pfbhip_pd_get_dual downloads the dual of the last iteration (PrimalDual._v, the warm start of the next solve).  The same
+ * kernels run in the same order as in pfbhip_primal_dual with comm == NULL: the iterates are identical.  Psi's and the
+ * plans' streams are switched to the first plan's for the duration of each run; the handle must not outlive them. */
+typedef struct pfbhip_pd pfbhip_pd;
+typedef struct pfbhip_pd_traffic {
+    int64_t events;     /* runs that ended with eps < tol */
+    int64_t h2d_bytes;  /* host-to-device bytes after the create: the weights of pfbhip_pd_set_weight */
+    int64_t d2h_bytes;  /* device-to-host bytes: the iterate of every run and the dual of pfbhip_pd_get_dual */
+    int64_t norm_bytes; /* the per-iteration block of norm partials (3 x 1024 doubles), not part of d2h_bytes */
+} pfbhip_pd_traffic;
+int pfbhip_pd_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs /* [nband] */, int64_t nband, const int64_t *nparts,
+                     const int64_t *psf_slots, const int64_t *beam_slots, const double *scale, const double *eta,
+                     const double *xtilde_host, double gamma, const double *x_host, const double *v_host, const double *weight_host,
+                     double sigma, double tau, int positivity, pfbhip_pd **out);
+int pfbhip_pd_run(pfbhip_pd *h, double lam, double tol, int maxit, double *x_host, pfbhip_pd_info *info);
+int pfbhip_pd_set_weight(pfbhip_pd *h, const double *weight_host);
+int pfbhip_pd_set_weight_dev(pfbhip_pd *h, const double *weight_dev);
+int pfbhip_pd_iterate_dev(pfbhip_pd *h, const double **x_dev);
+int pfbhip_pd_get_dual(pfbhip_pd *h, double *v_host);
+int pfbhip_pd_get_traffic(const pfbhip_pd *h, pfbhip_pd_traffic *out);
+int pfbhip_pd_destroy(pfbhip_pd *h);
+
+/* l1 reweighting of the l21 regulariser on the device: replaces the host arithmetic of L21.update_weights /
+ * init_reweighting (src/pfb_imaging/prox/l21.py:52-88) and l1reweight_func (utils/misc.py:742-755).
+ * pfbhip_l21_reweight_dev: x_dev (nband, nx, ny) is analysed band by band into scratch_dev (nband, nbasis, nxmax, nymax),
+ * then ONE pass adds the bands of each coefficient in band order (np.sum(axis=0): bit-identical) and writes
+ * weight_dev (nbasis, nxmax, nymax) = (1 + rmsfactor) / (1 + |s|^alpha / rms[basis]^alpha); alpha == 2 and alpha == 4 are
+ * products.  Cells of the padded frame that hold no coefficient are zero and get 1 + rmsfactor.  rms is a HOST array.
+ * pfbhip_l21_rms_dev: per basis, the number of NONZERO band sums of Psi^H update and their population standard deviation
+ * (l21.py:56-65; two passes, f64 per-workgroup partials added on the host in a fixed order); a basis with no nonzero
+ * entry reports count 0 and rms 0 (the caller keeps 1, l21.py:58).  scratch_dev is overwritten.
+ * pfbhip_l21_reweight / pfbhip_l21_rms: the host-array forms ((nbasis, nxmax, nymax) layout; bandsum_host, may be NULL,
+ * receives the band sum).  All run on the dictionary's stream and return when the result is complete. */
+int pfbhip_l21_reweight_dev(pfbhip_psi *psi, const double *x_dev, int64_t nband, const double *rms /* [nbasis], host */,
+                            double rmsfactor, double alpha, double *scratch_dev, double *weight_dev);
+int pfbhip_l21_rms_dev(pfbhip_psi *psi, const double *update_dev, int64_t nband, double *scratch_dev,
+                       double *rms_out /* [nbasis], host */, int64_t *count_out /* [nbasis], host */);
+int pfbhip_l21_reweight(pfbhip_psi *psi, const double *x_host, int64_t nband, const double *rms, double rmsfactor, double alpha,
+                        double *weight_host, double *bandsum_host);
+int pfbhip_l21_rms(pfbhip_psi *psi, const double *update_host, int64_t nband, double *rms_out, int64_t *count_out);
+
 /* ---- Hogbom and Clark CLEAN (the kclean minor cycle) ------------------- */
 /*
  * deconv/hogbom.py:9-63 and deconv/clark.py:11-143 of pfb-imaging with every cube resident in HBM (clean.hip; the semantics,
@@ -448,7 +498,8 @@ int pfbhip_clean_clark(pfbhip_clean *c, const double *dirty_host, const double *
  * the l21 (reg_kind 0, prox/l21.py) or l1 (reg_kind 1, prox/l1.py) prox at threshold step * lam * weight;
  * positivity 0 | 1 | 2; eps = ||x - xp|| / ||x|| (1 if x == 0); FISTA momentum when acceleration != 0.
  * psi == NULL is IdentityPsi.  x0 / xtilde (nband, nx, ny); weight (nbasis, nxmax, nymax) in the PsiNocopyt
- * layout ((nx, ny) for the identity).  All bands are on this device.
+ * layout ((nx, ny) for the identity).  weight_host == NULL: the caller sets the weight before the first
+ * run.  All bands are on this device.
  *
  * The handle keeps the iterate, momentum and iteration count between runs: pfbhip_fb_run iterates from where
  * the previous run stopped until eps < tol (status 0, a convergence event) or the loop index reaches
@@ -474,6 +525,10 @@ int pfbhip_fb_create(pfbhip_psi *psi /* NULL: identity */, pfbhip_psfconv *const
                      int reg_kind, double nu, double step, int positivity, int acceleration, pfbhip_fb **out);
 int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_host, pfbhip_fb_info *info);
 int pfbhip_fb_set_weight(pfbhip_fb *h, const double *weight_host);
+/* Between runs: the weight from device memory (a copy; forward_backward.py:111-113 with the weights of
+ * pfbhip_l21_reweight_dev) and the iterate in place (valid until the next run or the destroy). */
+int pfbhip_fb_set_weight_dev(pfbhip_fb *h, const double *weight_dev);
+int pfbhip_fb_iterate_dev(pfbhip_fb *h, const double **x_dev);
 int pfbhip_fb_destroy(pfbhip_fb *h);
 
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */

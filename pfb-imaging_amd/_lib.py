@@ -57,6 +57,10 @@ class PDInfo(ct.Structure):
                 ("stage_calls", i64 * PD_NSTAGES)]
 
 
+class PDTraffic(ct.Structure):
+    _fields_ = [("events", i64), ("h2d_bytes", i64), ("d2h_bytes", i64), ("norm_bytes", i64)]
+
+
 FB_NSTAGES = 5
 FB_STAGE_NAMES = ("forward_hessian", "psi_analysis", "shrink", "psi_synthesis", "step")
 
@@ -107,6 +111,10 @@ SYMBOLS = (
     "pfbhip_comm_allgather_host", "pfbhip_comm_barrier",
     "pfbhip_clean_create", "pfbhip_clean_destroy", "pfbhip_clean_hogbom", "pfbhip_clean_clark",
     "pfbhip_fb_create", "pfbhip_fb_run", "pfbhip_fb_set_weight", "pfbhip_fb_destroy",
+    "pfbhip_fb_set_weight_dev", "pfbhip_fb_iterate_dev",
+    "pfbhip_pd_create", "pfbhip_pd_run", "pfbhip_pd_set_weight", "pfbhip_pd_set_weight_dev", "pfbhip_pd_iterate_dev",
+    "pfbhip_pd_get_dual", "pfbhip_pd_get_traffic", "pfbhip_pd_destroy",
+    "pfbhip_l21_reweight_dev", "pfbhip_l21_rms_dev", "pfbhip_l21_reweight", "pfbhip_l21_rms",
 )
 
 _lib = None

@@ -271,6 +271,7 @@ struct pfbhip_fb {
     std::vector<double> hpart;
     int k = 0;                // index of the next iteration
     bool pending = false;     // iteration k - 1 ran: x / xp are rotated and k advanced before the next one
+    bool has_weight = false;
     double t = 1.0, eps = 1.0;
     int64_t events = 0;
     double loop_ms = 0.0;
@@ -348,8 +349,7 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
                      int acceleration, pfbhip_fb **out)
 {
     return guarded([&] {
-        PFB_REQUIRE(out && pcs && nparts && psf_slots && beam_slots && scale && eta && xtilde_host && x0_host && weight_host &&
-                        nband >= 1,
+        PFB_REQUIRE(out && pcs && nparts && psf_slots && beam_slots && scale && eta && xtilde_host && x0_host && nband >= 1,
                     "bad arguments");
         PFB_REQUIRE(reg_kind == 0 || reg_kind == 1, "reg_kind %d (0 l21, 1 l1)", reg_kind);
         PFB_REQUIRE(positivity >= 0 && positivity <= 2, "positivity mode %d", positivity);
@@ -410,7 +410,8 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
         PFB_HIP(hipMemcpyAsync(h->xt.p, xtilde_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(h->xp, x0_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(h->y.p, h->xp, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
-        PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, st));
+        h->has_weight = weight_host != nullptr;  // (NULL: the caller sets the weight before the first run)
+        if (weight_host) PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_fb_diff, blocks256(h->nimg), dim3(256), 0, st, h->xt.p, h->y.p, h->d.p, int64_t(h->nimg));
         PFB_HIP(hipGetLastError());
         PFB_HIP(hipStreamSynchronize(st));
@@ -424,6 +425,25 @@ int pfbhip_fb_set_weight(pfbhip_fb *h, const double *weight_host)
         PFB_REQUIRE(h && weight_host, "NULL argument");
         PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, h->st));
         PFB_HIP(hipStreamSynchronize(h->st));
+        h->has_weight = true;
+    });
+}
+
+int pfbhip_fb_set_weight_dev(pfbhip_fb *h, const double *weight_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(h && weight_dev, "NULL argument");
+        PFB_HIP(hipMemcpyAsync(h->w.p, weight_dev, h->cube * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+        PFB_HIP(hipStreamSynchronize(h->st));
+        h->has_weight = true;
+    });
+}
+
+int pfbhip_fb_iterate_dev(pfbhip_fb *h, const double **x_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(h && x_dev, "NULL argument");
+        *x_dev = h->pending ? h->x : h->xp;  // (before the first iteration the iterate is the start value)
     });
 }
 
@@ -432,6 +452,7 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
     return guarded([&] {
         PFB_REQUIRE(h && x_host && maxit >= 1, "bad arguments");
         PFB_REQUIRE(h->k + (h->pending ? 1 : 0) < maxit, "iteration %d is past maxit %d", h->k + (h->pending ? 1 : 0), maxit);
+        PFB_REQUIRE(h->has_weight, "no weight: created with weight_host == NULL and none set since");
         StreamScope scope(h);
         const hipStream_t st = h->st;
         const int64_t nband = h->nband;

@@ -1,5 +1,5 @@
 // pipeline_api.hpp -- internal (C++) entry points that let one driver chain the device-resident operators
-// of different handles on ONE stream (used by the on-device primal-dual loop, pd.hip).
+// of different handles on ONE stream (used by the on-device primal-dual and forward-backward loops and the l1 reweighting: pd.hip, fb.hip, reweight.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@ namespace pfbhip {
 
 // Psi (psi.hip): all launches of the handle go to `st` until swapped back; returns the previous stream
 hipStream_t psi_swap_stream(pfbhip_psi *p, hipStream_t st);
+hipStream_t psi_stream(const pfbhip_psi *p);
 void psi_geometry(const pfbhip_psi *p, int64_t *nx, int64_t *ny, int *nbasis, int64_t *nxmax, int64_t *nymax);
 void psi_dot_async(pfbhip_psi *p, const double *x_dev, double *alpha_dev);
 void psi_hdot_async(pfbhip_psi *p, const double *alpha_dev, double *x_dev);

@@ -443,6 +443,7 @@ hipStream_t psi_swap_stream(pfbhip_psi *p, hipStream_t st)
     p->stream = st;
     return prev;
 }
+hipStream_t psi_stream(const pfbhip_psi *p) { return p->stream; }
 void psi_geometry(const pfbhip_psi *p, int64_t *nx, int64_t *ny, int *nbasis, int64_t *nxmax, int64_t *nymax)
 {
     *nx = p->nx;

@@ -19,7 +19,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import FBInfo, PDInfo, PMInfo, check, cint, f64, i64, lib, ptr
+from ._lib import FBInfo, PDInfo, PDTraffic, PMInfo, check, cint, f64, i64, lib, ptr
 from .operators.psi import Psi, PsiNocopyt
 from .prox import dual_update_numba_fast, prox_21m_numba
 
@@ -36,7 +36,11 @@ class L21:
         self.bases = tuple(bases)
         self.rmsfactor = rmsfactor
         self.alpha = alpha
-        self.l1weight = np.ones(self.coeff_shape()[1:])
+        self._l1weight = np.ones(self.coeff_shape()[1:])
+        self._wdev = None      # the weight in HBM, (nbasis, nxmax, nymax), when a device update produced it
+        self._scratch = None   # coefficient cube (nband, nbasis, nxmax, nymax) of the device updates
+        self._lent = None      # (host array, device pointer) of a solver's iterate during its on_converge call
+        self._h2d_bytes = 0    # image bytes uploaded by the device updates (an argument that is not a lent iterate)
         self._outvar = None
         self._rms_comps = None
 
@@ -49,13 +53,53 @@ class L21:
             return (p.nband, p.nbasis, p.nxmax, p.nymax)
         return (p.nband, p.nbasis, p.nymax, p.nxmax)
 
+    @property
+    def l1weight(self):
+        """The l1 weights, (nbasis, n1, n2) in the layout of ``psi``.  After a device update they live in HBM: the first
+        read downloads them once and caches the array; assigning stores the host array and drops the device copy."""
+        if self._l1weight is None:
+            w = self._wdev.download()
+            self._l1weight = np.ascontiguousarray(w.transpose(0, 2, 1)) if isinstance(self.psi, Psi) else w
+        return self._l1weight
+
+    @l1weight.setter
+    def l1weight(self, w):
+        self._l1weight = w
+        self._wdev = None
+
     def prox(self, v, vout, lam, sigma=1.0):
         prox_21m_numba(v, vout, lam, sigma=sigma, weight=self.l1weight)
 
-    # ---- l1 reweighting (prox/l21.py:52-88, utils/misc.py:742-755): host bookkeeping on the GPU analysis ----
+    # ---- l1 reweighting (prox/l21.py:52-88, utils/misc.py:742-755) ----
+    # On the device (pfbhip_l21_rms_dev / pfbhip_l21_reweight_dev, csrc/reweight.hip) when ``psi`` is a dictionary the
+    # device loops accept; any other dictionary gets the host bookkeeping on its own analysis.
     @property
     def reweight_active(self):
         return self._rms_comps is not None
+
+    def _psi_dev(self):
+        """The pfbhip_psi handle of a dictionary the device loops take (``ForwardBackward._psi_handle``), else None."""
+        h = ForwardBackward._psi_handle(self.psi)
+        return None if h is None else h[0]
+
+    def _image_dev(self, x):
+        """(device pointer, keep-alive) of the image cube ``x``: the lending solver's iterate in HBM when ``x`` is the very
+        array its callback was handed, else an upload."""
+        if self._lent is not None and x is self._lent[0]:
+            return self._lent[1], None
+        psi = self.psi
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (psi.nband, psi.nx, psi.ny):
+            raise ValueError(f"x shape {x.shape} != {(psi.nband, psi.nx, psi.ny)}")
+        d = _lib.DeviceArray.from_host(x)
+        self._h2d_bytes += x.nbytes
+        return d.ptr, d
+
+    def _scratch_dev(self):
+        if self._scratch is None:
+            psi = self.psi
+            self._scratch = _lib.DeviceArray((psi.nband, psi.nbasis, psi.nxmax, psi.nymax))
+        return self._scratch
 
     def _band_sum(self, x):
         if self._outvar is None:
@@ -65,18 +109,35 @@ class L21:
 
     def init_reweighting(self, update):
         """Estimate per-basis component rms from the update and arm reweighting (l21.py:56-78)."""
-        tmp = self._band_sum(update)
         rms = np.ones(self.psi.nbasis, dtype=float)
-        for i in range(self.psi.nbasis):
-            nonzero = tmp[i][tmp[i] != 0]
-            if nonzero.size:
-                rms[i] = np.std(nonzero)
+        h = self._psi_dev()
+        if h is not None:
+            xdev, keep = self._image_dev(update)
+            got, count = np.zeros(self.psi.nbasis), np.zeros(self.psi.nbasis, dtype=np.int64)
+            check(lib().pfbhip_l21_rms_dev(h, xdev, i64(self.psi.nband), self._scratch_dev().ptr, ptr(got), ptr(count)))
+            rms[count > 0] = got[count > 0]
+            del keep
+        else:
+            tmp = self._band_sum(update)
+            for i in range(self.psi.nbasis):
+                nonzero = tmp[i][tmp[i] != 0]
+                if nonzero.size:
+                    rms[i] = np.std(nonzero)
         self._rms_comps = rms
 
     def update_weights(self, x):
         """l1weight = (1 + rmsfactor) / (1 + |sum_band Psi^T x|^alpha / rms^alpha) (misc.py:742-755)."""
         if self._rms_comps is None:
             raise RuntimeError("reweighting not initialised; call init_reweighting() first")
+        h = self._psi_dev()
+        if h is not None:
+            xdev, keep = self._image_dev(x)
+            wdev = self._wdev if self._wdev is not None else _lib.DeviceArray((self.psi.nbasis, self.psi.nxmax, self.psi.nymax))
+            check(lib().pfbhip_l21_reweight_dev(h, xdev, i64(self.psi.nband), ptr(self._rms_comps), f64(self.rmsfactor),
+                                                f64(self.alpha), self._scratch_dev().ptr, wdev.ptr))
+            self._l1weight, self._wdev = None, wdev
+            del keep
+            return
         mcomps = np.abs(self._band_sum(x))
         self.l1weight = (1 + self.rmsfactor) / (1 + mcomps**self.alpha / self._rms_comps[:, None, None] ** self.alpha)
 
@@ -188,16 +249,90 @@ class PrimalDual:
     _hess_bands = staticmethod(_psf_hess_bands)
 
     def _device_path(self):
+        """The positivity mode (0 / 1 / 2) of the device loop, or None when the solve takes the generic loop.  With an
+        ``on_converge`` callback the device loop is the resumable single-process one (``pfbhip_pd_*``): a distributed
+        pool (world_size > 1) with a callback keeps the generic loop, decided from world_size alone, no collective."""
+        from .operators.hessian import HessTreeRay
         from .prox import positivity, positivity_band
 
         g, reg = self._grad, self._reg
-        if not (isinstance(g, PsfGrad) and isinstance(reg, L21)) or self.on_converge is not None:
+        if not (isinstance(g, PsfGrad) and isinstance(reg, L21)):
             return None
         if not isinstance(reg.psi, (Psi, PsiNocopyt)):
+            return None
+        if self.on_converge is not None and isinstance(g.hess, HessTreeRay) and _distributed(g.hess._pool):
             return None
         if self._hess_bands(g.hess, reg.psi.nband) is None:
             return None
         return {None: 0, positivity: 1, positivity_band: 2}.get(self.primal_prox, None)
+
+    def _solve_events(self, x, lam, mode):
+        """The device loop with convergence events (single process): create / run / on_converge / set-weight / run / ...
+        / get-dual / destroy over ``pfbhip_pd_*``, as ``ForwardBackward._solve_device`` does.  During the callback the
+        regulariser may read the iterate in HBM (``reg.update_weights(x)`` with the very array the callback was handed),
+        and its device weight -- when it has one -- goes to the loop without crossing PCIe."""
+        reg, psi, g = self._reg, self._reg.psi, self._grad
+        bands, _, _ = self._hess_bands(g.hess, psi.nband)
+        nband = len(bands)
+        transposed = isinstance(psi, Psi)
+        vfull = self._v.transpose(0, 1, 3, 2) if transposed else self._v
+        v = np.ascontiguousarray(vfull, dtype=np.float64)
+        x0 = np.ascontiguousarray(x, dtype=np.float64)
+        xt = np.ascontiguousarray(g.xtilde, dtype=np.float64)
+        if x0.shape != (nband, psi.nx, psi.ny) or xt.shape != x0.shape:
+            raise ValueError(f"x {x0.shape} / xtilde {xt.shape}: expected {(nband, psi.nx, psi.ny)}")
+
+        def host_weight():
+            w = reg.l1weight.transpose(0, 2, 1) if transposed else reg.l1weight
+            return np.ascontiguousarray(np.broadcast_to(w, v.shape[1:]), dtype=np.float64)
+
+        handles = (ct.c_void_p * nband)(*[b[0]._h for b in bands])
+        nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
+        psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
+        beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
+        scale = np.array([b[3] for b in bands], dtype=np.float64)
+        eta = np.array([b[4] for b in bands], dtype=np.float64)
+        h = ct.c_void_p()
+        # (a weight left in HBM by an earlier update goes to the loop from there, below: none crosses PCIe for the create)
+        w0 = host_weight() if reg._wdev is None else None
+        uploaded0 = reg._h2d_bytes
+        check(lib().pfbhip_pd_create(psi._band._h, handles, i64(nband), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale),
+                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(v), ptr(w0), f64(self.sigma), f64(self.tau),
+                                     cint(mode), ct.byref(h)))
+        info, traffic = PDInfo(), PDTraffic()
+        try:
+            if reg._wdev is not None:
+                check(lib().pfbhip_pd_set_weight_dev(h, reg._wdev.ptr))
+            while True:
+                out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
+                check(lib().pfbhip_pd_run(h, f64(lam), f64(self.tol), cint(self.maxit), ptr(out), ct.byref(info)))
+                if info.status != 0:
+                    break
+                xdev = ct.c_void_p()
+                check(lib().pfbhip_pd_iterate_dev(h, ct.byref(xdev)))
+                reg._lent = (out, xdev)
+                try:
+                    stop = self.on_converge(out, int(info.iters), float(info.eps))
+                finally:
+                    reg._lent = None
+                if stop or info.iters >= self.maxit - 1:
+                    break
+                # on_converge may have replaced the weights (ReweightOnConverge -> update_weights): resume with them
+                if reg._wdev is not None:
+                    check(lib().pfbhip_pd_set_weight_dev(h, reg._wdev.ptr))
+                else:
+                    check(lib().pfbhip_pd_set_weight(h, ptr(host_weight())))
+            check(lib().pfbhip_pd_get_dual(h, ptr(v)))
+            check(lib().pfbhip_pd_get_traffic(h, ct.byref(traffic)))
+        finally:
+            lib().pfbhip_pd_destroy(h)
+        self._v[...] = v.transpose(0, 1, 3, 2) if transposed else v
+        self.last = dict(iters=int(info.iters), status=0 if info.eps < self.tol else 1, eps=float(info.eps),
+                         loop_ms=float(info.loop_ms), events=int(traffic.events), h2d_bytes=int(traffic.h2d_bytes) + reg._h2d_bytes - uploaded0,
+                         d2h_bytes=int(traffic.d2h_bytes), norm_bytes=int(traffic.norm_bytes),
+                         stages={n: (float(info.stage_ms[i]), int(info.stage_calls[i])) for i, n in enumerate(_lib.PD_STAGE_NAMES)})
+        x[...] = out
+        return x
 
     def _solve_device(self, x, lam, mode):
         reg, psi = self._reg, self._reg.psi
@@ -255,12 +390,12 @@ class PrimalDual:
         _lib.require_gpu()
         mode = self._device_path()
         if mode is not None:
-            return self._solve_device(x, lam, mode)
+            return self._solve_device(x, lam, mode) if self.on_converge is None else self._solve_events(x, lam, mode)
         xp = x.copy()
         v = self._v
         vp = v.copy()
         xout = np.zeros_like(x)
-        eps, k = 1.0, 0
+        eps, k, events = 1.0, 0, 0
         for k in range(self.maxit):
             self._dual_step(xp, v, vp, lam)
             vp[...] = 2.0 * v - vp
@@ -274,11 +409,12 @@ class PrimalDual:
             else:
                 eps = 1.0
             if eps < self.tol:
+                events += 1
                 if self.on_converge is None or self.on_converge(x, k, eps):
                     break
             np.copyto(xp, x)
             np.copyto(vp, v)
-        self.last = dict(iters=k, status=0 if eps < self.tol else 1, eps=eps)
+        self.last = dict(iters=k, status=0 if eps < self.tol else 1, eps=eps, events=events)
         return x
 
 
@@ -297,8 +433,8 @@ class ForwardBackward:
     When the gradient is a ``PsfGrad`` over a single-process device Hessian (HessPSF, HessTreeRay), the regulariser an
     ``L21`` / ``L1`` over ``Psi`` / ``PsiNocopyt`` / a single-process ``PsiNocopytRay`` / ``IdentityPsi`` and
     ``primal_prox`` None or a positivity prox, the whole loop runs on the device (``pfbhip_fb_*``, csrc/fb.hip); a
-    convergence event hands x to ``on_converge`` on the host and resumes with the state in HBM, re-uploading the
-    regulariser's weights.  Anything else runs the reference's loop over this package's GPU operators."""
+    convergence event hands x to ``on_converge`` on the host and resumes with the state in HBM, taking the regulariser's
+    weights from HBM when ``L21.update_weights`` left them there and re-uploading them otherwise.  Anything else runs the reference's loop over this package's GPU operators."""
 
     def __init__(self, tol=1e-5, maxit=1000, report_freq=10, verbosity=1, gamma=1.0, acceleration=True, on_converge=None,
                  primal_prox=None):
@@ -412,23 +548,40 @@ class ForwardBackward:
         beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
         scale = np.array([b[3] for b in bands], dtype=np.float64)
         eta = np.array([b[4] for b in bands], dtype=np.float64)
-        kind = 0 if isinstance(reg, L21) else 1
+        l21 = isinstance(reg, L21)
+        kind = 0 if l21 else 1
         h = ct.c_void_p()
+        # (an L21 weight left in HBM by an earlier update goes to the loop from there, below)
+        w0 = None if l21 and reg._wdev is not None else self._device_weight(transposed)
         check(lib().pfbhip_fb_create(handle, handles, i64(nband), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale),
-                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(self._device_weight(transposed)), cint(kind),
+                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(w0), cint(kind),
                                      f64(reg.nu), f64(self.step), cint(mode), cint(1 if self.acceleration else 0),
                                      ct.byref(h)))
         info = FBInfo()
         try:
+            if w0 is None:
+                check(lib().pfbhip_fb_set_weight_dev(h, reg._wdev.ptr))
             while True:
                 out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
                 check(lib().pfbhip_fb_run(h, f64(lam), f64(self.tol), cint(self.maxit), ptr(out), ct.byref(info)))
-                if info.status != 0 or self.on_converge is None or self.on_converge(out, int(info.iters), float(info.eps)):
+                if info.status != 0 or self.on_converge is None:
                     break
-                if info.iters >= self.maxit - 1:
+                if l21 and handle is not None:  # lend the iterate in HBM to reg.update_weights(out)
+                    xdev = ct.c_void_p()
+                    check(lib().pfbhip_fb_iterate_dev(h, ct.byref(xdev)))
+                    reg._lent = (out, xdev)
+                try:
+                    stop = self.on_converge(out, int(info.iters), float(info.eps))
+                finally:
+                    if l21:
+                        reg._lent = None
+                if stop or info.iters >= self.maxit - 1:
                     break
                 # on_converge may have replaced the weights (ReweightOnConverge -> update_weights): resume with them
-                check(lib().pfbhip_fb_set_weight(h, ptr(self._device_weight(transposed))))
+                if l21 and reg._wdev is not None:
+                    check(lib().pfbhip_fb_set_weight_dev(h, reg._wdev.ptr))
+                else:
+                    check(lib().pfbhip_fb_set_weight(h, ptr(self._device_weight(transposed))))
         finally:
             lib().pfbhip_fb_destroy(h)
         self.last = dict(iters=int(info.iters), status=0 if info.eps < self.tol else 1, eps=float(info.eps),

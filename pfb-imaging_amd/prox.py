@@ -136,3 +136,28 @@ def positivity_prox(mode):
     if mode == 2:
         return positivity_band
     raise ValueError(f"Unknown positivity mode {mode}")
+
+
+def l21_reweight(band, x, rms, rmsfactor, alpha, return_bandsum=False):
+    """l1 weights of the l21 regulariser for host arrays (``pfbhip_l21_reweight``; l1reweight_func, utils/misc.py:742-755):
+    ``(1 + rmsfactor) / (1 + |sum_band Psi^T x|^alpha / rms^alpha)`` with ``band`` a ``PsiBand``, ``x`` (nband, nx, ny) and
+    ``rms`` (nbasis); returns (nbasis, nxmax, nymax), and the band sum itself with ``return_bandsum``.  Callers inside a
+    device loop use ``L21.update_weights``, which leaves the weights in HBM."""
+    x, rms = as_c(x, np.float64), as_c(rms, np.float64)
+    if x.ndim != 3 or x.shape[1:] != (band.nx, band.ny) or rms.shape != (band.nbasis,):
+        raise ValueError(f"x {x.shape} / rms {rms.shape}: expected (nband, {band.nx}, {band.ny}) and ({band.nbasis},)")
+    w = np.empty((band.nbasis, band.nxmax, band.nymax))
+    s = np.empty_like(w) if return_bandsum else None
+    check(lib().pfbhip_l21_reweight(band._h, ptr(x), i64(x.shape[0]), ptr(rms), f64(rmsfactor), f64(alpha), ptr(w), ptr(s)))
+    return (w, s) if return_bandsum else w
+
+
+def l21_rms(band, update):
+    """(rms, count) per basis of the NONZERO band sums of ``Psi^T update`` (``pfbhip_l21_rms``; L21.init_reweighting,
+    prox/l21.py:56-65): the population standard deviation, 0 where ``count`` is 0."""
+    update = as_c(update, np.float64)
+    if update.ndim != 3 or update.shape[1:] != (band.nx, band.ny):
+        raise ValueError(f"update {update.shape}: expected (nband, {band.nx}, {band.ny})")
+    rms, count = np.zeros(band.nbasis), np.zeros(band.nbasis, dtype=np.int64)
+    check(lib().pfbhip_l21_rms(band._h, ptr(update), i64(update.shape[0]), ptr(rms), ptr(count)))
+    return rms, count
