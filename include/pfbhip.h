@@ -421,8 +421,8 @@ int pfbhip_primal_dual(pfbhip_psi *psi, pfbhip_psfconv *const *pcs /* [nband] */
  * returns False: xp <- x, vp <- v, the index goes on, maxit bounds the total.  Between runs the caller may replace the
  * weight from host (pfbhip_pd_set_weight) or device memory (pfbhip_pd_set_weight_dev: a copy, the handle keeps its own
  * buffer) and read the iterate in place (pfbhip_pd_iterate_dev: valid until the next run or the destroy).
- * pfbhip_pd_get_dual downloads the dual of the last iteration (PrimalDual._v, the warm start of the next solve).  The same
- * kernels run in the same order as in pfbhip_primal_dual with comm == NULL: the iterates are identical.  Psi's and the
+ * pfbhip_pd_get_dual downloads the dual of the last iteration (PrimalDual._v, the warm start of the next solve).  It is the
+ * same loop as pfbhip_primal_dual with comm == NULL: the iterates are identical.  Psi's and the
  * plans' streams are switched to the first plan's for the duration of each run; the handle must not outlive them. */
 typedef struct pfbhip_pd pfbhip_pd;
 typedef struct pfbhip_pd_traffic {

@@ -45,6 +45,20 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NS], double *part
     }
 }
 
+// Downloads the partials of NS quantities (synchronises the stream) and adds each in block order into out[NS].
+// host: at least NS * CG_BLOCKS doubles.
+template <int NS>
+inline void fetch_partials(const double *partials_dev, std::vector<double> &host, hipStream_t stream, double *out)
+{
+    PFB_HIP(hipMemcpyAsync(host.data(), partials_dev, size_t(NS) * CG_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, stream));
+    PFB_HIP(hipStreamSynchronize(stream));
+    for (int s = 0; s < NS; ++s) {
+        double t = 0.0;
+        for (int b = 0; b < CG_BLOCKS; ++b) t += host[size_t(s) * CG_BLOCKS + b];
+        out[s] = t;
+    }
+}
+
 // partials: [0] = a.b, [1] = c.d
 static __global__ void __launch_bounds__(CG_THREADS) k_cg_dot2(int64_t n, const double *a, const double *b,
                                                                 const double *c, const double *d, double *partials)
@@ -161,17 +175,6 @@ struct DevCG {
     }
     DevCG(const DevCG &) = delete;
     DevCG &operator=(const DevCG &) = delete;
-    void fetch(int ns, double *out)
-    {
-        PFB_HIP(hipMemcpyAsync(host.data(), partials.p, size_t(ns) * CG_BLOCKS * sizeof(double), hipMemcpyDeviceToHost,
-                               stream));
-        PFB_HIP(hipStreamSynchronize(stream));
-        for (int s = 0; s < ns; ++s) {
-            double t = 0.0;
-            for (int b = 0; b < CG_BLOCKS; ++b) t += host[size_t(s) * CG_BLOCKS + b];
-            out[s] = t;
-        }
-    }
     // aop(in_dev, out_dev) must enqueue on `stream`.  x_dev holds x0 on entry, the solution on exit.
     template <class Op>
     void solve(Op &&aop, const double *b_dev, double *x_dev, double tol, int maxit, int minit, pfbhip_cg_info *info)
@@ -180,7 +183,7 @@ struct DevCG {
         aop(x_dev, ap.p);
         hipLaunchKernelGGL(k_cg_init, dim3(CG_BLOCKS), dim3(CG_THREADS), 0, stream, n, ap.p, b_dev, r.p, p.p, partials.p);
         PFB_HIP(hipGetLastError());
-        fetch(2, s);
+        fetch_partials<2>(partials.p, host, stream, s);
         double rnorm = s[0];
         int k = 0, stall = 0, status = 0;
         double eps = 1.0, phi0 = (std::isnan(rnorm) || rnorm == 0.0) ? 1.0 : rnorm;
@@ -256,13 +259,7 @@ struct DevPower {
     {
         hipLaunchKernelGGL(k_pm_dots, dim3(CG_BLOCKS), dim3(CG_THREADS), 0, stream, n, bp, bv, partials.p);
         PFB_HIP(hipGetLastError());
-        PFB_HIP(hipMemcpyAsync(host.data(), partials.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        PFB_HIP(hipStreamSynchronize(stream));
-        for (int k = 0; k < 3; ++k) {
-            double t = 0.0;
-            for (int i = 0; i < CG_BLOCKS; ++i) t += host[size_t(k) * CG_BLOCKS + i];
-            s[k] = t;
-        }
+        fetch_partials<3>(partials.p, host, stream, s);
         allreduce(s);
     }
     // bp_dev: b0 on entry (any non-zero norm), the normalised last iterate on exit.  aop(in, out) enqueues on `stream`.

@@ -20,18 +20,10 @@
 
 #include "common.hpp"
 #include "devcg.hpp"
+#include "devloop.hpp"
 #include "pipeline_api.hpp"
 
 namespace pfbhip {
-
-constexpr int FB_MAXB = 16;  // bands held in registers by the one-pass kernels (PD_MAXB of pd.hip)
-
-__global__ void __launch_bounds__(256) k_fb_diff(const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ d,
-                                                 int64_t n)
-{
-    const int64_t i = blockIdx.x * int64_t(256) + threadIdx.x;
-    if (i < n) d[i] = a[i] - b[i];
-}
 
 // ratio of the l21 prox: prox(alpha)_b = alpha_b * ratio(sum_b alpha_b) (prox_21m.py:5-26; 0 where the band sum is 0)
 __device__ __forceinline__ double l21_ratio(double s, double thr)
@@ -225,11 +217,11 @@ static void launch_step(hipStream_t st, int64_t npix, double *y, const double *x
                        tau, w, l1, partials);
 }
 
-// compile-time band count 1..FB_MAXB from a runtime one
+// compile-time band count 1..LOOP_MAXB from a runtime one
 template <template <int> class F, int NB = 1, class... A>
 static void dispatch_nb(int nband, A &&...args)
 {
-    if constexpr (NB <= FB_MAXB) {
+    if constexpr (NB <= LOOP_MAXB) {
         if (nband == NB) return F<NB>::run(std::forward<A>(args)...);
         dispatch_nb<F, NB + 1>(nband, std::forward<A>(args)...);
     }
@@ -257,9 +249,7 @@ using namespace pfbhip;
 // The resumable state of one forward-backward solve.
 struct pfbhip_fb {
     pfbhip_psi *psi = nullptr;  // nullptr: IdentityPsi
-    std::vector<pfbhip_psfconv *> pcs;
-    std::vector<int64_t> off, psf_slots, beam_slots;
-    std::vector<double> scale, eta;
+    PsfHessBands bands;
     int64_t nband = 0, nx = 0, ny = 0, nxmax = 0, nymax = 0;
     int nbasis = 1;
     size_t npix = 0, nimg = 0, cube = 0, ncoef = 0;
@@ -269,77 +259,10 @@ struct pfbhip_fb {
     DevBuf<double> xt, y, xa, xb, d, xout, alpha, w, scratch, partials;
     double *x = nullptr, *xp = nullptr;
     std::vector<double> hpart;
-    int k = 0;                // index of the next iteration
-    bool pending = false;     // iteration k - 1 ran: x / xp are rotated and k advanced before the next one
-    bool has_weight = false;
-    double t = 1.0, eps = 1.0;
+    Resume run;
+    double t = 1.0;  // the FISTA sequence
     int64_t events = 0;
-    double loop_ms = 0.0;
-    double stage_ms[PFBHIP_FB_NSTAGES] = {};
-    int64_t stage_calls[PFBHIP_FB_NSTAGES] = {};
 };
-
-namespace {
-
-// Swaps Psi's and the plans' streams to the solve's stream for one run and restores them on exit.
-struct StreamScope {
-    pfbhip_psi *psi = nullptr;
-    hipStream_t psi_prev = nullptr;
-    std::vector<std::pair<pfbhip_psfconv *, hipStream_t>> plans;
-    explicit StreamScope(pfbhip_fb *h)
-    {
-        if (h->psi) {
-            psi_prev = psi_swap_stream(h->psi, h->st);
-            psi = h->psi;
-        }
-        for (int64_t b = 1; b < h->nband; ++b) {
-            bool seen = h->pcs[size_t(b)] == h->pcs[0];
-            for (auto &pr : plans) seen = seen || pr.first == h->pcs[size_t(b)];
-            if (!seen) plans.emplace_back(h->pcs[size_t(b)], psfconv_swap_stream(h->pcs[size_t(b)], h->st));
-        }
-    }
-    ~StreamScope()
-    {
-        if (psi) (void)psi_swap_stream(psi, psi_prev);
-        for (auto it = plans.rbegin(); it != plans.rend(); ++it) {
-            try {
-                (void)psfconv_swap_stream(it->first, it->second);
-            } catch (...) {
-            }
-        }
-    }
-};
-
-// HIP events around the stages of short runs (maxit <= 64), read back after the loop
-struct StageClock {
-    hipStream_t st;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> stage;
-    void begin(int s)
-    {
-        if (!on) return;
-        hipEvent_t a, b;
-        PFB_HIP(hipEventCreate(&a));
-        PFB_HIP(hipEventCreate(&b));
-        PFB_HIP(hipEventRecord(a, st));
-        ev.push_back(a);
-        ev.push_back(b);
-        stage.push_back(s);
-    }
-    void end()
-    {
-        if (on) PFB_HIP(hipEventRecord(ev.back(), st));
-    }
-    ~StageClock()
-    {
-        for (auto e : ev) (void)hipEventDestroy(e);
-    }
-};
-
-dim3 blocks256(size_t n) { return dim3(uint32_t(ceil_div(int64_t(n), 256))); }
-
-}  // namespace
 
 extern "C" {
 
@@ -349,8 +272,7 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
                      int acceleration, pfbhip_fb **out)
 {
     return guarded([&] {
-        PFB_REQUIRE(out && pcs && nparts && psf_slots && beam_slots && scale && eta && xtilde_host && x0_host && nband >= 1,
-                    "bad arguments");
+        PFB_REQUIRE(out && xtilde_host && x0_host, "bad arguments");
         PFB_REQUIRE(reg_kind == 0 || reg_kind == 1, "reg_kind %d (0 l21, 1 l1)", reg_kind);
         PFB_REQUIRE(positivity >= 0 && positivity <= 2, "positivity mode %d", positivity);
         PFB_REQUIRE(g != 0.0 && nu != 0.0, "g and nu must be non-zero");
@@ -363,36 +285,20 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
         h->reg_kind = reg_kind;
         h->positivity = positivity;
         h->acceleration = acceleration ? 1 : 0;
-        int64_t px, py;
-        psfconv_geometry(pcs[0], &px, &py);
-        if (psi) {
-            psi_geometry(psi, &h->nx, &h->ny, &h->nbasis, &h->nxmax, &h->nymax);
-        } else {
-            h->nx = h->nxmax = px;
-            h->ny = h->nymax = py;
+        if (psi) psi_geometry(psi, &h->nx, &h->ny, &h->nbasis, &h->nxmax, &h->nymax);
+        h->bands = PsfHessBands(pcs, nband, nparts, psf_slots, beam_slots, scale, eta, psi ? h->nx : -1, psi ? h->ny : -1);
+        if (!psi) {  // the identity: the coefficients are the image
+            h->nx = h->nxmax = h->bands.nx;
+            h->ny = h->nymax = h->bands.ny;
             h->nbasis = 1;
         }
-        h->off.assign(size_t(nband) + 1, 0);
-        for (int64_t b = 0; b < nband; ++b) {
-            PFB_REQUIRE(pcs[b] != nullptr, "band %lld has no PSF plan", (long long)b);
-            psfconv_geometry(pcs[b], &px, &py);
-            PFB_REQUIRE(px == h->nx && py == h->ny, "the images are (%lld, %lld) but the PSF plan of band %lld is (%lld, %lld)",
-                        (long long)h->nx, (long long)h->ny, (long long)b, (long long)px, (long long)py);
-            PFB_REQUIRE(nparts[b] >= 1, "band %lld has no partitions", (long long)b);
-            h->off[size_t(b) + 1] = h->off[size_t(b)] + nparts[b];
-            h->pcs.push_back(pcs[b]);
-            h->scale.push_back(scale[b]);
-            h->eta.push_back(eta[b]);
-        }
-        h->psf_slots.assign(psf_slots, psf_slots + h->off.back());
-        h->beam_slots.assign(beam_slots, beam_slots + h->off.back());
         h->npix = size_t(h->nx) * size_t(h->ny);
         h->nimg = size_t(nband) * h->npix;
         h->cube = psi ? size_t(h->nbasis) * size_t(h->nxmax) * size_t(h->nymax) : h->npix;
         h->ncoef = size_t(nband) * h->cube;
         // IdentityPsi: the one-pass step folds the prox in when the bands fit in registers; otherwise alpha is a copy of xg
-        const bool fused_id = !psi && nband <= FB_MAXB && h->npix % 2 == 0;
-        h->st = psfconv_stream(pcs[0]);
+        const bool fused_id = !psi && nband <= LOOP_MAXB && h->npix % 2 == 0;
+        h->st = h->bands.stream();
         h->xt.alloc(h->nimg);
         h->y.alloc(h->nimg);
         h->xa.alloc(h->nimg);
@@ -410,9 +316,9 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
         PFB_HIP(hipMemcpyAsync(h->xt.p, xtilde_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(h->xp, x0_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(h->y.p, h->xp, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
-        h->has_weight = weight_host != nullptr;  // (NULL: the caller sets the weight before the first run)
+        h->run.has_weight = weight_host != nullptr;  // (NULL: the caller sets the weight before the first run)
         if (weight_host) PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_fb_diff, blocks256(h->nimg), dim3(256), 0, st, h->xt.p, h->y.p, h->d.p, int64_t(h->nimg));
+        hipLaunchKernelGGL(k_diff, blocks256(h->nimg), dim3(256), 0, st, h->xt.p, h->y.p, h->d.p, int64_t(h->nimg));
         PFB_HIP(hipGetLastError());
         PFB_HIP(hipStreamSynchronize(st));
         *out = h.release();
@@ -423,9 +329,7 @@ int pfbhip_fb_set_weight(pfbhip_fb *h, const double *weight_host)
 {
     return guarded([&] {
         PFB_REQUIRE(h && weight_host, "NULL argument");
-        PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, h->st));
-        PFB_HIP(hipStreamSynchronize(h->st));
-        h->has_weight = true;
+        h->run.set_weight(h->w.p, weight_host, h->cube, hipMemcpyHostToDevice, h->st);
     });
 }
 
@@ -433,9 +337,7 @@ int pfbhip_fb_set_weight_dev(pfbhip_fb *h, const double *weight_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(h && weight_dev, "NULL argument");
-        PFB_HIP(hipMemcpyAsync(h->w.p, weight_dev, h->cube * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-        PFB_HIP(hipStreamSynchronize(h->st));
-        h->has_weight = true;
+        h->run.set_weight(h->w.p, weight_dev, h->cube, hipMemcpyDeviceToDevice, h->st);
     });
 }
 
@@ -443,7 +345,7 @@ int pfbhip_fb_iterate_dev(pfbhip_fb *h, const double **x_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(h && x_dev, "NULL argument");
-        *x_dev = h->pending ? h->x : h->xp;  // (before the first iteration the iterate is the start value)
+        *x_dev = h->run.iterate(h->x, h->xp);
     });
 }
 
@@ -451,27 +353,21 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
 {
     return guarded([&] {
         PFB_REQUIRE(h && x_host && maxit >= 1, "bad arguments");
-        PFB_REQUIRE(h->k + (h->pending ? 1 : 0) < maxit, "iteration %d is past maxit %d", h->k + (h->pending ? 1 : 0), maxit);
-        PFB_REQUIRE(h->has_weight, "no weight: created with weight_host == NULL and none set since");
-        StreamScope scope(h);
+        h->run.require_runnable(maxit);
+        StreamScope scope(h->psi, h->bands, h->st);
         const hipStream_t st = h->st;
         const int64_t nband = h->nband;
         const size_t npix = h->npix, cube = h->cube;
         const double tau = h->step * lam, inv_nu = 1.0 / h->nu;
         const int l1 = h->reg_kind;
-        const bool fast = nband <= FB_MAXB && npix % 2 == 0;
+        const bool fast = nband <= LOOP_MAXB && npix % 2 == 0;
         const bool fused_id = !h->psi && fast;
-        StageClock clk{st, info != nullptr && maxit <= 64, {}, {}};
+        StageClock clk(st, info != nullptr && maxit <= 64);
         int status = 1;
         PFB_HIP(hipStreamSynchronize(st));
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
-            if (h->pending) {  // complete the previous iteration: xp <- x (y and d were written by its step kernel)
-                std::swap(h->x, h->xp);
-                ++h->k;
-                h->pending = false;
-            }
-            const int k = h->k;
+            (void)h->run.complete(h->x, h->xp);  // xp <- x (y and d were written by the previous step kernel)
             double beta = 0.0;
             if (h->acceleration) {  // FISTA momentum: data-independent, advanced once per iteration
                 const double tp = h->t;
@@ -479,16 +375,8 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
                 beta = (tp - 1.0) / h->t;
             }
             // 1. forward step: y <- y + (step / g) H d, d = xtilde - y
-            for (int64_t b = 0; b < nband; ++b) {
-                const double c = h->step / h->g;
-                for (int64_t q = h->off[size_t(b)]; q < h->off[size_t(b) + 1]; ++q) {
-                    clk.begin(0);
-                    psfconv_apply_async(h->pcs[size_t(b)], h->d.p + size_t(b) * npix, h->psf_slots[size_t(q)],
-                                        h->beam_slots[size_t(q)], 0, 0.0, c * h->scale[size_t(b)],
-                                        q == h->off[size_t(b)] ? c * h->eta[size_t(b)] : 0.0, 1, h->y.p + size_t(b) * npix);
-                    clk.end();
-                }
-            }
+            for (int64_t b = 0; b < nband; ++b)
+                h->bands.apply(b, h->d.p + size_t(b) * npix, h->y.p + size_t(b) * npix, h->step / h->g, 1.0, true, &clk, 0);
             const double *xo = h->xout.p;
             if (!fused_id) {
                 // 2. analysis (a copy of xg for the identity)
@@ -501,7 +389,7 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
                 clk.end();
                 // 3. alpha <- prox(alpha) - alpha
                 clk.begin(2);
-                if (nband <= FB_MAXB && cube % 2 == 0) {
+                if (nband <= LOOP_MAXB && cube % 2 == 0) {
                     dispatch_nb<ShrinkNB>(int(nband), st, h->alpha.p, int64_t(cube), tau, (const double *)h->w.p, l1);
                 } else {
                     if (!l1) hipLaunchKernelGGL(k_fb_bandsum, blocks256(cube), dim3(256), 0, st, h->alpha.p, int(nband), int64_t(cube),
@@ -537,43 +425,28 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
             }
             clk.end();
             PFB_HIP(hipGetLastError());
-            PFB_HIP(hipMemcpyAsync(h->hpart.data(), h->partials.p, h->hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            PFB_HIP(hipStreamSynchronize(st));
-            double num = 0.0, den = 0.0, nnz = 0.0;
-            for (int i = 0; i < CG_BLOCKS; ++i) {
-                num += h->hpart[size_t(i)];
-                den += h->hpart[size_t(CG_BLOCKS) + size_t(i)];
-                nnz += h->hpart[2 * size_t(CG_BLOCKS) + size_t(i)];
-            }
-            h->eps = nnz > 0.0 ? std::sqrt(num / std::max(den, 1e-12)) : 1.0;  // _nb_norm_diff / _nb_any_nonzero
-            h->pending = true;
-            if (h->eps < tol) {
+            double s[3];  // |x - xp|^2, |x|^2, #nonzero(x)
+            fetch_partials<3>(h->partials.p, h->hpart, st, s);
+            h->run.eps = rel_change_eps(s[0], s[1], s[2]);
+            h->run.pending = true;
+            if (h->run.eps < tol) {
                 status = 0;
                 ++h->events;
                 break;
             }
-            if (k + 1 >= maxit) break;
+            if (h->run.k + 1 >= maxit) break;
         }
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        h->loop_ms += ms;
+        h->run.loop_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         PFB_HIP(hipMemcpyAsync(x_host, h->x, h->nimg * sizeof(double), hipMemcpyDeviceToHost, st));
         PFB_HIP(hipStreamSynchronize(st));
-        for (size_t i = 0; i < clk.stage.size(); ++i) {
-            float e = 0.f;
-            PFB_HIP(hipEventElapsedTime(&e, clk.ev[2 * i], clk.ev[2 * i + 1]));
-            h->stage_ms[clk.stage[i]] += double(e);
-            h->stage_calls[clk.stage[i]] += 1;
-        }
+        clk.read(h->run.stage_ms, h->run.stage_calls);
         if (info) {
-            info->iters = h->k;
+            info->iters = h->run.k;
             info->status = status;
-            info->eps = h->eps;
-            info->loop_ms = h->loop_ms;
+            info->eps = h->run.eps;
+            info->loop_ms = h->run.loop_ms;
             info->events = h->events;
-            for (int q = 0; q < PFBHIP_FB_NSTAGES; ++q) {
-                info->stage_ms[q] = h->stage_ms[q];
-                info->stage_calls[q] = h->stage_calls[q];
-            }
+            h->run.stages_to(info->stage_ms, info->stage_calls);
         }
     });
 }

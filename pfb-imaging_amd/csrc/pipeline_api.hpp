@@ -1,5 +1,7 @@
 // pipeline_api.hpp -- internal (C++) entry points that let one driver chain the device-resident operators
-// of different handles on ONE stream (used by the on-device primal-dual and forward-backward loops and the l1 reweighting: pd.hip, fb.hip, reweight.hip).
+// of different handles on ONE stream (used by the on-device primal-dual and forward-backward loops and the l1
+// reweighting: pd.hip, fb.hip, reweight.hip).  The scaffold the two loops share on top of these -- the PSF-Hessian band
+// description, the stream scope, the stage clock, the resume protocol -- is devloop.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

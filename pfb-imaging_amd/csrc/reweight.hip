@@ -20,7 +20,7 @@
 
 namespace pfbhip {
 
-constexpr int RW_MAXB = 16;    // bands held in registers by the one-pass kernel (FB_MAXB of fb.hip)
+constexpr int RW_MAXB = 16;    // bands held in registers by the one-pass kernel (LOOP_MAXB of devloop.hpp)
 constexpr int RW_BLOCKS = 512;  // workgroups per basis of the rms passes (8 per CU at four bases; one f64 partial each per quantity)
 
 // |s|^alpha: 0 -> alpha = 2, 1 -> alpha = 4 (the reference's two defaults: products), 2 -> pow

@@ -212,6 +212,77 @@ def _psf_hess_bands(hess, nband):
     return None
 
 
+def _band_args(bands):
+    """The ctypes arguments of a band description of ``_psf_hess_bands`` in the order of the C ABI: plan handles, nband,
+    nparts, psf slots, beam slots, scale, eta (each pointer holds a reference to its array)."""
+    handles = (ct.c_void_p * len(bands))(*[b[0]._h for b in bands])
+    nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
+    psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
+    beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
+    scale = np.array([b[3] for b in bands], dtype=np.float64)
+    eta = np.array([b[4] for b in bands], dtype=np.float64)
+    return handles, i64(len(bands)), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale), ptr(eta)
+
+
+def _device_weight(reg, psi, transposed):
+    """The regulariser's current weight in the device's layout: (nbasis, nxmax, nymax) for a wavelet dictionary (the
+    weight of ``Psi`` is transposed from its (nbasis, nymax, nxmax)), (1, nx, ny) for the identity."""
+    from .operators.psi import IdentityPsi
+
+    w = np.asarray(reg.l1weight if isinstance(reg, L21) else reg.weight, dtype=np.float64)
+    if isinstance(psi, IdentityPsi):
+        return np.ascontiguousarray(np.broadcast_to(w, (1, psi.nx, psi.ny)))
+    if transposed:
+        return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nymax, psi.nxmax)).transpose(0, 2, 1))
+    return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nxmax, psi.nymax)))
+
+
+def _stages(info, names):
+    return {n: (float(info.stage_ms[i]), int(info.stage_calls[i])) for i, n in enumerate(names)}
+
+
+def _rel_change(x, xp):
+    """eps = ||x - xp|| / max(||x||^2, 1e-12)^1/2, 1 when x is all zero (``_nb_norm_diff`` of the reference)."""
+    if not _lib.any_nonzero(x):
+        return 1.0
+    return float(np.sqrt(((x - xp) ** 2).sum() / max(float((x**2).sum()), 1e-12)))
+
+
+def _run_with_events(h, run, set_weight, set_weight_dev, iterate_dev, info, lam, tol, maxit, x0, on_converge, reg, weight):
+    """Drives a resumable device loop (``pfbhip_pd_*`` / ``pfbhip_fb_*``) on the created handle ``h``: run -> ``on_converge(x,
+    k, eps)`` with a fresh host array -> stop, or set the weight again and run on; returns the last iterate.  A weight that
+    ``reg`` holds in HBM (``reg._wdev``) goes to the loop without crossing PCIe, at the start too; ``weight()`` is the host
+    one otherwise.  During the callback an ``L21`` over a real dictionary is lent the iterate in HBM: its
+    ``update_weights(x)`` with the very array the callback was handed reads it in place."""
+    lend = isinstance(reg, L21) and reg._psi_dev() is not None
+
+    def resume_weight(host):
+        wdev = getattr(reg, "_wdev", None)
+        if wdev is not None:
+            check(set_weight_dev(h, wdev.ptr))
+        elif host:
+            check(set_weight(h, ptr(weight())))
+
+    resume_weight(False)  # (the create uploaded the host weight)
+    while True:
+        out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
+        check(run(h, f64(lam), f64(tol), cint(maxit), ptr(out), ct.byref(info)))
+        if info.status != 0 or on_converge is None:
+            return out
+        if lend:
+            xdev = ct.c_void_p()
+            check(iterate_dev(h, ct.byref(xdev)))
+            reg._lent = (out, xdev)
+        try:
+            stop = on_converge(out, int(info.iters), float(info.eps))
+        finally:
+            if lend:
+                reg._lent = None
+        if stop or info.iters >= maxit - 1:
+            return out
+        resume_weight(True)  # on_converge may have replaced the weights (ReweightOnConverge -> update_weights)
+
+
 class PrimalDual:
     """primal_dual.py:303-448: same constructor, ``setup`` / ``set_grad`` / ``reset`` / ``solve`` contract."""
 
@@ -267,10 +338,8 @@ class PrimalDual:
         return {None: 0, positivity: 1, positivity_band: 2}.get(self.primal_prox, None)
 
     def _solve_events(self, x, lam, mode):
-        """The device loop with convergence events (single process): create / run / on_converge / set-weight / run / ...
-        / get-dual / destroy over ``pfbhip_pd_*``, as ``ForwardBackward._solve_device`` does.  During the callback the
-        regulariser may read the iterate in HBM (``reg.update_weights(x)`` with the very array the callback was handed),
-        and its device weight -- when it has one -- goes to the loop without crossing PCIe."""
+        """The device loop with convergence events (single process): create / ``_run_with_events`` / get-dual / destroy
+        over ``pfbhip_pd_*``, as ``ForwardBackward._solve_device`` does over ``pfbhip_fb_*``."""
         reg, psi, g = self._reg, self._reg.psi, self._grad
         bands, _, _ = self._hess_bands(g.hess, psi.nband)
         nband = len(bands)
@@ -281,79 +350,41 @@ class PrimalDual:
         xt = np.ascontiguousarray(g.xtilde, dtype=np.float64)
         if x0.shape != (nband, psi.nx, psi.ny) or xt.shape != x0.shape:
             raise ValueError(f"x {x0.shape} / xtilde {xt.shape}: expected {(nband, psi.nx, psi.ny)}")
-
-        def host_weight():
-            w = reg.l1weight.transpose(0, 2, 1) if transposed else reg.l1weight
-            return np.ascontiguousarray(np.broadcast_to(w, v.shape[1:]), dtype=np.float64)
-
-        handles = (ct.c_void_p * nband)(*[b[0]._h for b in bands])
-        nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
-        psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
-        beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
-        scale = np.array([b[3] for b in bands], dtype=np.float64)
-        eta = np.array([b[4] for b in bands], dtype=np.float64)
         h = ct.c_void_p()
-        # (a weight left in HBM by an earlier update goes to the loop from there, below: none crosses PCIe for the create)
-        w0 = host_weight() if reg._wdev is None else None
+        # (a weight left in HBM by an earlier update goes to the loop from there: none crosses PCIe for the create)
+        w0 = _device_weight(reg, psi, transposed) if reg._wdev is None else None
         uploaded0 = reg._h2d_bytes
-        check(lib().pfbhip_pd_create(psi._band._h, handles, i64(nband), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale),
-                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(v), ptr(w0), f64(self.sigma), f64(self.tau),
-                                     cint(mode), ct.byref(h)))
+        L = lib()
+        check(L.pfbhip_pd_create(psi._band._h, *_band_args(bands), ptr(xt), f64(g.gamma), ptr(x0), ptr(v), ptr(w0), f64(self.sigma),
+                                 f64(self.tau), cint(mode), ct.byref(h)))
         info, traffic = PDInfo(), PDTraffic()
         try:
-            if reg._wdev is not None:
-                check(lib().pfbhip_pd_set_weight_dev(h, reg._wdev.ptr))
-            while True:
-                out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
-                check(lib().pfbhip_pd_run(h, f64(lam), f64(self.tol), cint(self.maxit), ptr(out), ct.byref(info)))
-                if info.status != 0:
-                    break
-                xdev = ct.c_void_p()
-                check(lib().pfbhip_pd_iterate_dev(h, ct.byref(xdev)))
-                reg._lent = (out, xdev)
-                try:
-                    stop = self.on_converge(out, int(info.iters), float(info.eps))
-                finally:
-                    reg._lent = None
-                if stop or info.iters >= self.maxit - 1:
-                    break
-                # on_converge may have replaced the weights (ReweightOnConverge -> update_weights): resume with them
-                if reg._wdev is not None:
-                    check(lib().pfbhip_pd_set_weight_dev(h, reg._wdev.ptr))
-                else:
-                    check(lib().pfbhip_pd_set_weight(h, ptr(host_weight())))
-            check(lib().pfbhip_pd_get_dual(h, ptr(v)))
-            check(lib().pfbhip_pd_get_traffic(h, ct.byref(traffic)))
+            out = _run_with_events(h, L.pfbhip_pd_run, L.pfbhip_pd_set_weight, L.pfbhip_pd_set_weight_dev, L.pfbhip_pd_iterate_dev,
+                                   info, lam, self.tol, self.maxit, x0, self.on_converge, reg,
+                                   lambda: _device_weight(reg, psi, transposed))
+            check(L.pfbhip_pd_get_dual(h, ptr(v)))
+            check(L.pfbhip_pd_get_traffic(h, ct.byref(traffic)))
         finally:
-            lib().pfbhip_pd_destroy(h)
+            L.pfbhip_pd_destroy(h)
         self._v[...] = v.transpose(0, 1, 3, 2) if transposed else v
         self.last = dict(iters=int(info.iters), status=0 if info.eps < self.tol else 1, eps=float(info.eps),
                          loop_ms=float(info.loop_ms), events=int(traffic.events), h2d_bytes=int(traffic.h2d_bytes) + reg._h2d_bytes - uploaded0,
                          d2h_bytes=int(traffic.d2h_bytes), norm_bytes=int(traffic.norm_bytes),
-                         stages={n: (float(info.stage_ms[i]), int(info.stage_calls[i])) for i, n in enumerate(_lib.PD_STAGE_NAMES)})
+                         stages=_stages(info, _lib.PD_STAGE_NAMES))
         x[...] = out
         return x
 
     def _solve_device(self, x, lam, mode):
         reg, psi = self._reg, self._reg.psi
         bands, comm, local = self._hess_bands(self._grad.hess, psi.nband)
-        nloc = len(local)
         transposed = isinstance(psi, Psi)
         vfull = self._v.transpose(0, 1, 3, 2) if transposed else self._v
-        w = reg.l1weight.transpose(0, 2, 1) if transposed else reg.l1weight
         v = np.ascontiguousarray(vfull[local], dtype=np.float64)
-        w = np.ascontiguousarray(np.broadcast_to(w, v.shape[1:]), dtype=np.float64)
+        w = _device_weight(reg, psi, transposed)
         xs = np.ascontiguousarray(np.asarray(x, dtype=np.float64)[local])
         xt = np.ascontiguousarray(self._grad.xtilde[local])
-        handles = (ct.c_void_p * nloc)(*[b[0]._h for b in bands])
-        nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
-        psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
-        beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
-        scale = np.array([b[3] for b in bands], dtype=np.float64)
-        eta = np.array([b[4] for b in bands], dtype=np.float64)
         info = PDInfo()
-        check(lib().pfbhip_primal_dual(psi._band._h, handles, i64(nloc), ptr(nparts), ptr(psf_slots), ptr(beam_slots),
-                                       ptr(scale), ptr(eta), ptr(xt), f64(self._grad.gamma), ptr(xs), ptr(v),
+        check(lib().pfbhip_primal_dual(psi._band._h, *_band_args(bands), ptr(xt), f64(self._grad.gamma), ptr(xs), ptr(v),
                                        ptr(w), f64(lam), f64(self.sigma), f64(self.tau), cint(mode), f64(self.tol),
                                        cint(self.maxit), None if comm is None else comm._h, ct.byref(info)))
         if comm is None:
@@ -367,7 +398,7 @@ class PrimalDual:
             vall = comm.allreduce_sum(vall).reshape(vfull.shape)
         self._v[...] = vall.transpose(0, 1, 3, 2) if transposed else vall
         self.last = dict(iters=info.iters, status=info.status, eps=info.eps, loop_ms=float(info.loop_ms),
-                         stages={n: (float(info.stage_ms[i]), int(info.stage_calls[i])) for i, n in enumerate(_lib.PD_STAGE_NAMES)})
+                         stages=_stages(info, _lib.PD_STAGE_NAMES))
         x[...] = xall
         return x
 
@@ -404,10 +435,7 @@ class PrimalDual:
             x[...] = xp - self.tau * xout
             if self.primal_prox is not None:
                 self.primal_prox(x)
-            if _lib.any_nonzero(x):
-                eps = float(np.sqrt(((x - xp) ** 2).sum() / max((x**2).sum(), 1e-12)))
-            else:
-                eps = 1.0
+            eps = _rel_change(x, xp)
             if eps < self.tol:
                 events += 1
                 if self.on_converge is None or self.on_converge(x, k, eps):
@@ -520,19 +548,6 @@ class ForwardBackward:
             return None
         return mode
 
-    def _device_weight(self, transposed):
-        """The regulariser's current weight in the device's layout: (nbasis, nxmax, nymax) for a wavelet dictionary (the
-        weight of ``Psi`` is transposed from its (nbasis, nymax, nxmax)), (1, nx, ny) for the identity."""
-        from .operators.psi import IdentityPsi
-
-        reg, psi = self._reg, self._reg.psi
-        w = np.asarray(reg.l1weight if isinstance(reg, L21) else reg.weight, dtype=np.float64)
-        if isinstance(psi, IdentityPsi):
-            return np.ascontiguousarray(np.broadcast_to(w, (1, psi.nx, psi.ny)))
-        if transposed:
-            return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nymax, psi.nxmax)).transpose(0, 2, 1))
-        return np.ascontiguousarray(np.broadcast_to(w, (psi.nbasis, psi.nxmax, psi.nymax)))
-
     def _solve_device(self, x, lam, mode):
         reg, psi, g = self._reg, self._reg.psi, self._grad
         handle, transposed = self._psi_handle(psi)
@@ -542,52 +557,21 @@ class ForwardBackward:
         xt = np.ascontiguousarray(g.xtilde, dtype=np.float64)
         if x0.shape != (nband, psi.nx, psi.ny) or xt.shape != x0.shape:
             raise ValueError(f"x {x0.shape} / xtilde {xt.shape}: expected {(nband, psi.nx, psi.ny)}")
-        handles = (ct.c_void_p * nband)(*[b[0]._h for b in bands])
-        nparts = np.array([len(b[1]) for b in bands], dtype=np.int64)
-        psf_slots = np.array([s for b in bands for s in b[1]], dtype=np.int64)
-        beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
-        scale = np.array([b[3] for b in bands], dtype=np.float64)
-        eta = np.array([b[4] for b in bands], dtype=np.float64)
-        l21 = isinstance(reg, L21)
-        kind = 0 if l21 else 1
         h = ct.c_void_p()
-        # (an L21 weight left in HBM by an earlier update goes to the loop from there, below)
-        w0 = None if l21 and reg._wdev is not None else self._device_weight(transposed)
-        check(lib().pfbhip_fb_create(handle, handles, i64(nband), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale),
-                                     ptr(eta), ptr(xt), f64(g.gamma), ptr(x0), ptr(w0), cint(kind),
-                                     f64(reg.nu), f64(self.step), cint(mode), cint(1 if self.acceleration else 0),
-                                     ct.byref(h)))
+        # (an L21 weight left in HBM by an earlier update goes to the loop from there)
+        w0 = None if getattr(reg, "_wdev", None) is not None else _device_weight(reg, psi, transposed)
+        L = lib()
+        check(L.pfbhip_fb_create(handle, *_band_args(bands), ptr(xt), f64(g.gamma), ptr(x0), ptr(w0), cint(0 if isinstance(reg, L21) else 1),
+                                 f64(reg.nu), f64(self.step), cint(mode), cint(1 if self.acceleration else 0), ct.byref(h)))
         info = FBInfo()
         try:
-            if w0 is None:
-                check(lib().pfbhip_fb_set_weight_dev(h, reg._wdev.ptr))
-            while True:
-                out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
-                check(lib().pfbhip_fb_run(h, f64(lam), f64(self.tol), cint(self.maxit), ptr(out), ct.byref(info)))
-                if info.status != 0 or self.on_converge is None:
-                    break
-                if l21 and handle is not None:  # lend the iterate in HBM to reg.update_weights(out)
-                    xdev = ct.c_void_p()
-                    check(lib().pfbhip_fb_iterate_dev(h, ct.byref(xdev)))
-                    reg._lent = (out, xdev)
-                try:
-                    stop = self.on_converge(out, int(info.iters), float(info.eps))
-                finally:
-                    if l21:
-                        reg._lent = None
-                if stop or info.iters >= self.maxit - 1:
-                    break
-                # on_converge may have replaced the weights (ReweightOnConverge -> update_weights): resume with them
-                if l21 and reg._wdev is not None:
-                    check(lib().pfbhip_fb_set_weight_dev(h, reg._wdev.ptr))
-                else:
-                    check(lib().pfbhip_fb_set_weight(h, ptr(self._device_weight(transposed))))
+            out = _run_with_events(h, L.pfbhip_fb_run, L.pfbhip_fb_set_weight, L.pfbhip_fb_set_weight_dev, L.pfbhip_fb_iterate_dev,
+                                   info, lam, self.tol, self.maxit, x0, self.on_converge, reg,
+                                   lambda: _device_weight(reg, psi, transposed))
         finally:
-            lib().pfbhip_fb_destroy(h)
+            L.pfbhip_fb_destroy(h)
         self.last = dict(iters=int(info.iters), status=0 if info.eps < self.tol else 1, eps=float(info.eps),
-                         loop_ms=float(info.loop_ms), events=int(info.events),
-                         stages={n: (float(info.stage_ms[i]), int(info.stage_calls[i]))
-                                 for i, n in enumerate(_lib.FB_STAGE_NAMES)})
+                         loop_ms=float(info.loop_ms), events=int(info.events), stages=_stages(info, _lib.FB_STAGE_NAMES))
         return out
 
     def solve(self, x, lam):
@@ -607,7 +591,7 @@ class ForwardBackward:
         for k in range(self.maxit):
             x = y - self.step * self._grad(y)
             x = self._apply_prox(x, lam)
-            eps = float(np.sqrt(((x - xp) ** 2).sum() / max(float((x**2).sum()), 1e-12))) if _lib.any_nonzero(x) else 1.0
+            eps = _rel_change(x, xp)
             if eps < self.tol:
                 events += 1
                 if self.on_converge is None or self.on_converge(x, k, eps):
@@ -695,7 +679,7 @@ def primal_dual_numba(x, v, lam, psih, psi, hessnorm, prox, l1weight, reweighter
             clamp(x)
         elif positivity == 2:
             clamp_band(x)
-        eps = float(np.sqrt(((x - xp) ** 2).sum() / max(float((x**2).sum()), 1e-12))) if _lib.any_nonzero(x) else 1.0
+        eps = _rel_change(x, xp)
         if eps < tol:
             if reweighter is None or run >= maxreweight:
                 break
@@ -766,16 +750,8 @@ def _pm_device(aop, imsize, b):
         bands, comm, local = hb
 
         def call(b, tol, maxit, info):
-            nloc = len(local)
             bs = np.ascontiguousarray(b[local])
-            handles = (ct.c_void_p * nloc)(*[x[0]._h for x in bands])
-            nparts = np.array([len(x[1]) for x in bands], dtype=np.int64)
-            psf_slots = np.array([s for x in bands for s in x[1]], dtype=np.int64)
-            beam_slots = np.array([s for x in bands for s in x[2]], dtype=np.int64)
-            scale = np.array([x[3] for x in bands], dtype=np.float64)
-            eta = np.array([x[4] for x in bands], dtype=np.float64)
-            check(lib().pfbhip_psfconv_power_method(handles, i64(nloc), ptr(nparts), ptr(psf_slots), ptr(beam_slots),
-                                                    ptr(scale), ptr(eta), ptr(bs), f64(tol), cint(maxit),
+            check(lib().pfbhip_psfconv_power_method(*_band_args(bands), ptr(bs), f64(tol), cint(maxit),
                                                     None if comm is None else comm._h, ct.byref(info)))
             if comm is None:
                 return bs
