@@ -199,6 +199,10 @@ int pfbhip_gridder_residual_dev(pfbhip_gridder *g, const double *model_dev, cons
 int pfbhip_gridder_vis2dirty_dev(pfbhip_gridder *g, const double *vis_host, const double *wgt_host, double *dirty_dev);
 int pfbhip_gridder_degrid_dev(pfbhip_gridder *g, const double *dirty_dev, double *vis_sorted_dev);
 int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, double *dirty_dev);
+/* dirty2vis whose image is already in HBM (the rendered component model of comps2vis, operators/gridder.py:345-365): the
+ * degrid and the un-sort of pfbhip_gridder_dirty2vis without the image upload; visibilities in (nrow, nchan) row order. */
+int pfbhip_gridder_dirty2vis_dev(pfbhip_gridder *g, const double *dirty_dev, const double *wgt_host /* or NULL */,
+                                 double *vis_host /* (nrow,nchan,2) */);
 
 /* Per-stage device timing (HIP events on the handle's stream).  Stages:
  * 0 grid (scatter kernel)  1 degrid (gather kernel)  2 fft_rows (plain row-FFT passes: first axis, and the
@@ -530,6 +534,47 @@ int pfbhip_fb_set_weight(pfbhip_fb *h, const double *weight_host);
 int pfbhip_fb_set_weight_dev(pfbhip_fb *h, const double *weight_dev);
 int pfbhip_fb_iterate_dev(pfbhip_fb *h, const double **x_dev);
 int pfbhip_fb_destroy(pfbhip_fb *h);
+
+/* ---- component models: fit, render, regrid ------------------------------ */
+/*
+ * The component model of src/pfb_imaging/utils/modelspec.py on the device (comps.hip; DESIGN.md "Component models on the
+ * device").  A handle holds the image geometry, the pixel locations x_index / y_index (int64, ncomps) and the coefficients
+ * (nparam, ncomps) in HBM.  Component c is the c-th pixel in ascending flat index x * ny + y (np.where's order).
+ *
+ * pfbhip_comps_create: from host arrays (the `coefficients`, `location_x`, `location_y` of a model dataset as
+ *   operators/gridder.py:318-320 reads them).  Locations must lie inside the image and be distinct.
+ * pfbhip_comps_fit: modelspec.py:54-59 and :130-135 -- mask = any over the ns = ntime * nband planes of cube (ns, nx, ny)
+ *   != 0, compaction of the set pixels in np.where's order, coeffs[k, c] = sum_s A[k, s] * cube[s, pix_c] with
+ *   A = solve(hess_coeffs, xfit^T wgt) (nparam, ns) formed by the caller.  Exactly one of cube_host / cube_dev is non-NULL.
+ *   *ncomps_out receives the number of components; pfbhip_comps_get downloads locations and coefficients (any pointer may
+ *   be NULL), pfbhip_comps_shape the sizes.
+ * pfbhip_comps_set_region: uploads a region mask (nx, ny) uint8 once per handle (NULL unbinds it).
+ * pfbhip_comps_render / _render_dev: modelspec.py:227-238, :266-275 and operators/gridder.py:345-348 --
+ *   image = 0; image[x_index, y_index] = sum_k basis[k] * coeffs[k] (k ascending); with use_region != 0,
+ *   np.where(region_mask, image, 0).  Every pixel of the target is written: it need not be zero beforehand.
+ * pfbhip_comps_regrid / _regrid_dev: modelspec.py:277-332 -- bilinear interpolation of an image on the grid
+ *   (nxi, nyi, cellxi, cellyi, x0i, y0i), zero-extended by the reference's pad widths without forming a padded copy, at the
+ *   points of (nxo, nyo, cellxo, cellyo, x0o, y0o), times cellxo * cellyo / (cellxi * cellyi).  When the reference's own test
+ *   (:321-326) finds nothing to interpolate the (padded) input is returned as it stands, without the area ratio;
+ *   *interpolated (may be NULL) tells which.  Output points outside the padded grid are an error (bounds_error=True).
+ */
+typedef struct pfbhip_comps pfbhip_comps;
+int pfbhip_comps_create(int64_t nx, int64_t ny, int64_t ncomps, int32_t nparam, const int64_t *x_index_host,
+                        const int64_t *y_index_host, const double *coeffs_host /* (nparam, ncomps) */, pfbhip_comps **out);
+int pfbhip_comps_destroy(pfbhip_comps *h);
+int pfbhip_comps_fit(const double *cube_host, const double *cube_dev, int64_t ns, int64_t nx, int64_t ny,
+                     const double *A_host /* (nparam, ns) */, int32_t nparam, pfbhip_comps **out, int64_t *ncomps_out);
+int pfbhip_comps_shape(const pfbhip_comps *h, int64_t *nx, int64_t *ny, int64_t *ncomps, int32_t *nparam);
+int pfbhip_comps_get(pfbhip_comps *h, int64_t *x_index_host, int64_t *y_index_host, double *coeffs_host);
+int pfbhip_comps_set_region(pfbhip_comps *h, const uint8_t *region_host /* (nx, ny) or NULL */);
+int pfbhip_comps_render(pfbhip_comps *h, const double *basis_host /* [nparam] */, int use_region, double *image_host);
+int pfbhip_comps_render_dev(pfbhip_comps *h, const double *basis_host /* [nparam] */, int use_region, double *image_dev);
+int pfbhip_comps_regrid(const double *in_host, int64_t nxi, int64_t nyi, double cellxi, double cellyi, double x0i, double y0i,
+                        int64_t nxo, int64_t nyo, double cellxo, double cellyo, double x0o, double y0o, double *out_host,
+                        int *interpolated);
+int pfbhip_comps_regrid_dev(const double *in_dev, int64_t nxi, int64_t nyi, double cellxi, double cellyi, double x0i, double y0i,
+                            int64_t nxo, int64_t nyo, double cellxo, double cellyo, double x0o, double y0o, double *out_dev,
+                            int *interpolated);
 
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*

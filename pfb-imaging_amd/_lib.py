@@ -115,6 +115,9 @@ SYMBOLS = (
     "pfbhip_pd_create", "pfbhip_pd_run", "pfbhip_pd_set_weight", "pfbhip_pd_set_weight_dev", "pfbhip_pd_iterate_dev",
     "pfbhip_pd_get_dual", "pfbhip_pd_get_traffic", "pfbhip_pd_destroy",
     "pfbhip_l21_reweight_dev", "pfbhip_l21_rms_dev", "pfbhip_l21_reweight", "pfbhip_l21_rms",
+    "pfbhip_comps_create", "pfbhip_comps_destroy", "pfbhip_comps_fit", "pfbhip_comps_shape", "pfbhip_comps_get",
+    "pfbhip_comps_set_region", "pfbhip_comps_render", "pfbhip_comps_render_dev", "pfbhip_comps_regrid",
+    "pfbhip_comps_regrid_dev", "pfbhip_gridder_dirty2vis_dev",
 )
 
 _lib = None

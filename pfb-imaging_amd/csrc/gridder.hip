@@ -2238,14 +2238,24 @@ static void vis2dirty_host(pfbhip_gridder *g, const T *vis_host, const T *wgt_ho
 }
 
 template <class T>
+static void degrid_to_host(pfbhip_gridder *g, const double *img_dev, const T *wgt_host, T *vis_host);
+
+template <class T>
 static void dirty2vis_host(pfbhip_gridder *g, const T *dirty_host, const T *wgt_host, T *vis_host)
 {
     PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-    hipStream_t st = g->stream;
     g->upload(dirty_host, size_t(g->prm.nx * g->prm.ny), g->d_img.p);
+    degrid_to_host(g, g->d_img.p, wgt_host, vis_host);
+}
+
+// the degrid of an image resident in HBM and the un-sort of its visibilities into the caller's (nrow, nchan) order
+template <class T>
+static void degrid_to_host(pfbhip_gridder *g, const double *img_dev, const T *wgt_host, T *vis_host)
+{
+    hipStream_t st = g->stream;
     g->upload_vis_wgt<T>(nullptr, wgt_host);
     ApplyState a{g->d_grid.p};
-    g->prepare_and_degrid(a, g->d_img.p, nullptr, g->d_sacc.p);
+    g->prepare_and_degrid(a, img_dev, nullptr, g->d_sacc.p);
     if (g->nvis) {
         g->d_vis.ensure(size_t(g->nvis));
         PFB_HIP(hipMemsetAsync(g->d_vis.p, 0, size_t(g->nvis) * sizeof(double2), st));
@@ -2448,6 +2458,15 @@ int pfbhip_gridder_grid_plane(pfbhip_gridder *g, const double *vis_host, const d
 int pfbhip_gridder_dirty2vis(pfbhip_gridder *g, const double *dirty_host, const double *wgt_host, double *vis_host)
 {
     return guarded([&] { dirty2vis_host(g, dirty_host, wgt_host, vis_host); });
+}
+
+// dirty2vis of an image that is already in HBM (a rendered component model): the same degrid and un-sort, no image upload
+int pfbhip_gridder_dirty2vis_dev(pfbhip_gridder *g, const double *dirty_dev, const double *wgt_host, double *vis_host)
+{
+    return guarded([&] {
+        PFB_REQUIRE(g && dirty_dev && (vis_host || g->nvis == 0), "NULL argument");
+        degrid_to_host<double>(g, dirty_dev, wgt_host, vis_host);
+    });
 }
 
 int pfbhip_gridder_set_weights(pfbhip_gridder *g, const double *wgt_host)

@@ -3,6 +3,7 @@
 Mirrors /root/reference/src/pfb_imaging/operators/gridder.py:
     wgridder_conventions      :23-34
     vis2im / im2vis           :37-144
+    comps2vis                 :276-367   (the numpy-level _comps2vis_impl; the dask layer :148-273 stays with the reference)
     grid_partition            :760-923   (dirty, PSF, PSFHAT, beam, wsum, imaging weights per partition)
     residual_from_partitions  :926-1016  (dirty - sum_p R_p^H W_p R_p (beam_p model))
     compute_residual_arrays   the arithmetic of compute_residual :1060-1117 on in-memory arrays
@@ -81,6 +82,119 @@ def _attr(part, name, default=0.0):
     if isinstance(part, dict):
         return part.get("attrs", {}).get(name, part.get(name, default))
     return part.attrs.get(name, default)
+
+
+def comps2vis(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_idx, fbin_cnts, region_mask, mds, modelf, tfunc,
+              ffunc, epsilon=1e-7, nthreads=1, do_wgridding=True, divide_by_n=False, freq_min=-np.inf, freq_max=np.inf,
+              product="I", info=None, _dirty2vis=None):
+    """Model visibilities of a component model, ``_comps2vis_impl`` of the reference (gridder.py:276-367) with the render and
+    the degrid on the device: per (time chunk, band) the ``nparam`` numbers of the basis vector go up, the image is formed in
+    HBM from the resident coefficients and degridded there (``Gridder.dirty2vis_dev``), the visibilities come down.
+
+    ``mds`` is a dict or an attribute object with ``coefficients (nparam, ncomps)``, ``location_x``, ``location_y`` and the
+    attributes ``cell_rad_x, npix_x, npix_y, center_x, center_y, flip_u, flip_v, flip_w``.  ``info`` (a dict, optional)
+    receives ``device_renders``, ``host_renders`` and ``plans``.
+
+    ``modelf`` is checked once per call to be linear in its parameters (:func:`pfb_imaging_amd.comps.basis_vector`); one that
+    is not is evaluated on the host as the reference does and the image uploaded -- never linearised.
+
+    The reference's behaviour is kept where it is peculiar:
+      * ``celly`` is ``mds.cell_rad_x`` (:321-322): pixels are square whatever ``cell_rad_y`` says;
+      * the row slice of a time chunk runs from the first row of its first time to the last row of its last (:335);
+      * nothing is degridded -- the output stays zero -- when ``region_mask`` has no set pixel (:347) or no channel of the band
+        lies in ``[freq_min, freq_max]`` (:340), and nothing at all when no channel of ``freq`` does (:315);
+      * the same visibilities are written to every entry of ``product`` (:349-350; no Stokes conversion);
+      * the output dtype is ``result_type(coefficients, complex64)`` (:314).
+    One difference: the reference degrids ALL rows of ``uvw`` for every time chunk (:351) and assigns the result to the
+    chunk's row slice, which only fits when the call holds one time chunk (as its dask layer arranges, core/degrid.py:266-279);
+    here each chunk degrids its own rows ``uvw[indr]``, the same thing for one chunk and the evident intent for several.
+
+    ``_dirty2vis`` (tests) replaces the device: a callable with ``dirty2vis``'s keywords; images are then rendered on the host.
+    """
+    resize_thread_pool(nthreads)
+    coeffs = _field(mds, "coefficients")
+    nstokes = len(product)
+    vis = np.zeros((uvw.shape[0], freq.size, nstokes), dtype=np.result_type(coeffs.dtype, np.complex64))
+    stats = dict(device_renders=0, host_renders=0, plans=0)
+    if info is not None:
+        info.update(stats)
+    in_range = (freq >= freq_min) & (freq <= freq_max)
+    if not in_range.any() or not np.any(region_mask):
+        return vis  # (with an empty region mask the reference renders every image and then degrids none)
+    xloc, yloc = _field(mds, "location_x"), _field(mds, "location_y")
+    cell = _attr(mds, "cell_rad_x")  # both pixel sizes: the reference reads cell_rad_x for x and for y
+    nx, ny = int(_attr(mds, "npix_x")), int(_attr(mds, "npix_y"))
+    plan_kw = dict(npix_x=nx, npix_y=ny, pixsize_x=float(cell), pixsize_y=float(cell), center_x=float(_attr(mds, "center_x")),
+                   center_y=float(_attr(mds, "center_y")), epsilon=float(epsilon), flip_u=bool(_attr(mds, "flip_u")),
+                   flip_v=bool(_attr(mds, "flip_v")), flip_w=bool(_attr(mds, "flip_w")), do_wgridding=bool(do_wgridding),
+                   divide_by_n=bool(divide_by_n), sigma_min=1.1, sigma_max=2.6)
+
+    def host_image(tt, ff):
+        values = modelf(tt, ff, *coeffs)
+        image = np.zeros((nx, ny), dtype=coeffs.dtype)
+        image[xloc, yloc] = values
+        return np.where(region_mask, image, 0.0)
+
+    # bin starts are relative to the first bin of this call (the caller may hand over a block of a larger problem)
+    row0, time0, chan0 = rbin_idx.min(), tbin_idx.min(), fbin_idx.min()
+    bands = []
+    for first, count in zip(fbin_idx - chan0, fbin_cnts):
+        chans = slice(int(first), int(first + count))
+        if in_range[chans].any():
+            bands.append(chans)
+    handle = image_dev = None
+    linear = None  # decided at the first render; a modelf that fails once stays on the host for the whole call
+    plans = set()
+    try:
+        if _dirty2vis is None:
+            from ..comps import Comps, basis_vector
+
+            handle = Comps(nx, ny, xloc, yloc, coeffs)
+            handle.set_region(region_mask)
+            image_dev = _lib.DeviceArray((nx, ny), np.float64)
+        for first, count in zip(tbin_idx - time0, tbin_cnts):
+            times = slice(int(first), int(first + count))
+            starts, counts = rbin_idx[times] - row0, rbin_cnts[times]
+            rows = slice(int(starts[0]), int(starts[-1] + counts[-1]))
+            uvw_rows = np.ascontiguousarray(uvw[rows], dtype=np.float64)
+            tt = tfunc(np.mean(utime[times]))
+            for chans in bands:
+                ff = ffunc(np.mean(freq[chans]))
+                bvec = None
+                if handle is not None and linear is not False:
+                    bvec = basis_vector(modelf, tt, ff, coeffs.shape[0])
+                    if linear is None:
+                        linear = bvec is not None
+                if bvec is not None:
+                    handle.render_dev(bvec, image_dev, region=True)
+                    stats["device_renders"] += 1
+                else:
+                    image = host_image(tt, ff)
+                    stats["host_renders"] += 1
+                    if handle is not None:
+                        handle.host_renders += 1
+                        image_dev.upload(image)
+                if handle is None:
+                    kw = {k: v for k, v in plan_kw.items() if k not in ("npix_x", "npix_y", "sigma_min", "sigma_max")}
+                    out = _dirty2vis(uvw=uvw_rows, freq=freq[chans], dirty=image, nthreads=nthreads, **kw)
+                else:
+                    g, cached = _get_gridder(uvw_rows, freq[chans], None, **plan_kw)
+                    plans.add(id(g))
+                    try:
+                        out = g.dirty2vis_dev(image_dev)
+                    finally:
+                        if not cached:
+                            g.close()
+                vis[rows, chans, :] = np.asarray(out)[:, :, None]
+    finally:
+        stats["plans"] = len(plans)
+        if info is not None:
+            info.update(stats)
+        if handle is not None:
+            handle.close()
+        if image_dev is not None:
+            image_dev.free()
+    return vis
 
 
 def psf_visibilities(uvw, freq, x0, y0, flip_u=False, flip_v=True, dtype=np.complex128):

@@ -145,6 +145,16 @@ class Gridder:
         check(lib().pfbhip_gridder_dirty2vis(self._h, ptr(dirty), ptr(wgt), ptr(out)))
         return out
 
+    def dirty2vis_dev(self, dirty_dev, wgt=None):
+        """:meth:`dirty2vis` of an image that is already in HBM (``dirty_dev``: float64 DeviceArray of the image shape, e.g.
+        a rendered component model): the same degrid and un-sort, no image upload; visibilities ``(nrow, nchan)`` on the host."""
+        if tuple(dirty_dev.shape) != (self.nx, self.ny) or dirty_dev.dtype != np.float64:
+            raise ValueError(f"dirty_dev must be a float64 DeviceArray of shape {(self.nx, self.ny)}")
+        wgt = self._wgt(wgt)
+        out = _lib.result_empty((self.nrow, self.nchan), np.complex128)
+        check(lib().pfbhip_gridder_dirty2vis_dev(self._h, dirty_dev.ptr, ptr(wgt), ptr(out)))
+        return out
+
     def set_weights(self, wgt):
         if self._is_sp(wgt, "r"):
             check(lib().pfbhip_gridder_set_weights_sp(self._h, ptr(self._sp_wgt(wgt))))
