@@ -576,6 +576,47 @@ int pfbhip_comps_regrid_dev(const double *in_dev, int64_t nxi, int64_t nyi, doub
                             int64_t nxo, int64_t nyo, double cellxo, double cellyo, double x0o, double y0o, double *out_dev,
                             int *interpolated);
 
+/* ---- Gaussian-resolution convolution and restore --------------------------- */
+/*
+ * Replaces convolve2gaussres (src/pfb_imaging/utils/misc.py:123-192) with its gaussian2d (:468-502, nsigma = 5) and
+ * get_padding_info (:107-120), and the arithmetic of restore_image (src/pfb_imaging/utils/restoration.py:71-88), on the
+ * device (restore.hip; DESIGN.md "Gaussian-resolution convolution and restore").
+ *
+ * pfbhip_gaussconv_create: one plan per (nband, nx, ny, pfrac).  Padded sizes nfft = good_size(n + int(pfrac n), real),
+ *   left pad (nfft - n) / 2, the rest on the right (pfbhip_gaussconv_shape returns them).  A geometry whose right pad is
+ *   zero on either axis is refused: the reference's slice(l, -0) returns an empty array there.
+ * pfbhip_gaussconv_apply / _apply_dev (misc.py:142-192): out[b] = fftshift(c2r(r2c(ifftshift(pad(image[b]))) * K_b))[unpad]
+ *   with K_b = gausshat_b, or where(|thishat_b| > 0, gausshat_b / thishat_b, 0) when gausspari is given.  gaussparf is
+ *   (nparf, 3) rows of (emaj, emin, pa), nparf 1 or nband; gausspari (npari, 3) with npari == nband, or NULL.  The kernels
+ *   are gaussian2d on the grids (-(n // 2) + arange(n)) * scale of each axis, divided by their sum with norm_kernel != 0.
+ *   kernf (nparf, nx, ny) / kerni (nband, nx, ny), when non-NULL, are kernels the caller rendered (grids that are no scaled
+ *   pixel offsets): they replace the rendering and are taken as they are (norm_kernel is not applied to them).  With
+ *   gausspari both or neither are given.  image / out / kernf / kerni are host arrays for _apply, device arrays for
+ *   _apply_dev; the parameter arrays are always host arrays.
+ * pfbhip_gaussconv_restore / _restore_dev (restoration.py:71-88): image[b] = conv(model[b]; gaussparf_b) + rconv_b with
+ *   rconv_b = residual[b] / wsum[b] where allclose(gaussparf_b, gausspari_b) (numpy's defaults, decided on the host per
+ *   band), else conv(residual[b] / wsum[b]; gaussparf_b / gausspari_b); pixel-offset grids, kernels not normalised.
+ * Refused with PFBHIP_ERR_INVALID: non-positive axes, NaN or non-positive parameters, emin > emaj, gausspari of the wrong
+ *   length, nparf not in {1, nband}, a zero or non-finite wsum.
+ * pfbhip_gaussconv_debug_fill: test hook, fills every buffer the plan owns with a byte.
+ */
+typedef struct pfbhip_gaussconv pfbhip_gaussconv;
+int pfbhip_gaussconv_create(int64_t nband, int64_t nx, int64_t ny, double pfrac, pfbhip_gaussconv **out);
+int pfbhip_gaussconv_destroy(pfbhip_gaussconv *h);
+int pfbhip_gaussconv_shape(const pfbhip_gaussconv *h, int64_t *nfft_x, int64_t *nfft_y, int64_t *padl_x, int64_t *padl_y);
+int pfbhip_gaussconv_apply(pfbhip_gaussconv *h, const double *image_host, const double *gaussparf, int64_t nparf,
+                           const double *gausspari, int64_t npari, int norm_kernel, double scale_x, double scale_y,
+                           const double *kernf_host, const double *kerni_host, double *out_host);
+int pfbhip_gaussconv_apply_dev(pfbhip_gaussconv *h, const double *image_dev, const double *gaussparf, int64_t nparf,
+                               const double *gausspari, int64_t npari, int norm_kernel, double scale_x, double scale_y,
+                               const double *kernf_dev, const double *kerni_dev, double *out_dev);
+int pfbhip_gaussconv_restore(pfbhip_gaussconv *h, const double *model_host, const double *residual_host, const double *wsum,
+                             const double *gausspari, int64_t npari, const double *gaussparf, int64_t nparf, double *image_host);
+int pfbhip_gaussconv_restore_dev(pfbhip_gaussconv *h, const double *model_dev, const double *residual_dev, const double *wsum,
+                                 const double *gausspari, int64_t npari, const double *gaussparf, int64_t nparf,
+                                 double *image_dev);
+int pfbhip_gaussconv_debug_fill(pfbhip_gaussconv *h, int byte);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

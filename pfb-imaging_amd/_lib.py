@@ -118,6 +118,8 @@ SYMBOLS = (
     "pfbhip_comps_create", "pfbhip_comps_destroy", "pfbhip_comps_fit", "pfbhip_comps_shape", "pfbhip_comps_get",
     "pfbhip_comps_set_region", "pfbhip_comps_render", "pfbhip_comps_render_dev", "pfbhip_comps_regrid",
     "pfbhip_comps_regrid_dev", "pfbhip_gridder_dirty2vis_dev",
+    "pfbhip_gaussconv_create", "pfbhip_gaussconv_destroy", "pfbhip_gaussconv_shape", "pfbhip_gaussconv_apply",
+    "pfbhip_gaussconv_apply_dev", "pfbhip_gaussconv_restore", "pfbhip_gaussconv_restore_dev", "pfbhip_gaussconv_debug_fill",
 )
 
 _lib = None
