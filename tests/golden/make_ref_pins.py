@@ -24,8 +24,10 @@ What is pinned (reference file:line -> what the oracle / product has to reproduc
   opt/primal_dual.py:66-163              primal_dual (legacy) -> opt.py (host loop)
   utils/weighting.py:471-505             reduce_counts        -> (semantic check of the band/time grouping used by the tests)
 
-NOT pinned by this (and it cannot be here): ducc0's floating-point output (wheel absent), the numba kernels
-(_compute_counts, counts_to_weights, the DWT: decorated, numba absent), PyWavelets' filter tables.
+NOT pinned by this script: the decorated numba kernels.  make_numba_pins.py runs those as plain Python under a stand-in
+numba and pins _compute_counts, counts_to_weights (cell index, Hermitian fold, bounds, Briggs scaling), the DWT (index
+formulas, packed layout, padding between levels, both layouts) and dual_update_numba_fast (the strict threshold).
+NOT pinned anywhere (it cannot be here): ducc0's floating-point output (wheel absent), PyWavelets' filter tables.
 
 Run from the repo root in the build container:  python tests/golden/make_ref_pins.py
 It also rewrites conventions_two_sources.npz so that its expected visibilities are the REFERENCE's explicit formula.

@@ -1,5 +1,7 @@
-"""GPU parity of the wavelet dictionary Psi and the l21 / positivity proxes against the CPU oracle
-(oracle/psi.py, a restatement of the reference's numba code; see its header: parity unpinned by fixtures)."""
+"""GPU parity of the wavelet dictionary Psi and the l21 / positivity proxes against the CPU oracle (oracle/psi.py, a
+restatement of the reference's numba code).  The oracle and the kernels are each pinned to the reference's own code, run as
+plain Python (tests/test_numba_pins_cpu.py, tests/test_gpu_numba_pins.py): indexing, packed layout, padding between levels,
+the transposed layout, the dual update's threshold.  PyWavelets' filter tables and ducc0 stay unpinned."""
 
 import numpy as np
 import pytest
