@@ -35,6 +35,7 @@
 #include "eskernel.hpp"
 #include "gridder_kernels_mp.hpp"
 #include "gridder_wd_api.hpp"
+#include "plan_layout.hpp"
 #include "rowfft_api.hpp"
 #include "vismap.hpp"
 
@@ -303,8 +304,6 @@ __global__ void k_corr_image(ImgGeom g, const double *cfu, const double *cfv, co
 //   degrid side: pad+screen (imgT -> B) -> FFT_u(ny rows) -> B2A (transpose+pad, occ rows) -> FFT_v(occ rows)
 //                -> gather
 
-constexpr int TP = 32;  // transpose tile
-
 // The plan works on the TRANSPOSED problem (pfbhip_gridder_create exchanges the two image axes, u <-> v), so its
 // transposed accumulator accT (ny, nx) IS the caller's image layout: the image-side steps are element-wise.
 // accT = x * corr [* beam]   (degrid input)
@@ -516,9 +515,10 @@ struct StageTimer {
     }
 };
 
-// Which kernels and transforms a plan runs.  Decided in three steps of create_impl (sort_key_sub before the sort,
-// choose_kernels after the work lists, choose_transforms after the row-FFT plans), read-only afterwards, and reported as
-// info.scatter_mode / scatter_launches / scatter_block / fft_mode (report_path).
+// Which kernels and transforms a plan runs.  Decided in three steps of plan creation (sort_key_sub in sort_by_tile,
+// choose_kernels once build_work_lists has the work lists, choose_transforms in setup_transforms once the row-FFT plans
+// exist; PlanBuild::path until then), read-only afterwards, and reported as info.scatter_mode / scatter_launches /
+// scatter_block / fft_mode (report_path).
 enum class Scatter { Walk, Block, Rec, OnePlane };   // k_grid_mp, k_grid_blk, k_grid_rec, k_grid_wd
 enum class Gather { Walk, RowWalk, OnePlane };       // k_degrid_mp, k_degrid_rw, k_degrid_wd
 enum class FirstAxis { RocFFT, Rows, Transposing };  // rocFFT rows of A; rowfft_plain + k_a2b / k_b2a; rowfft_a2b / rowfft_b2a
@@ -1333,9 +1333,59 @@ static void report_path(const PlanPath &p, pfbhip_gridder_info &info)
                     (p.axis2 == SecondAxis::Rows ? 4 : 0) | (p.axis1 == FirstAxis::Transposing ? 8 : 0);
 }
 
-static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo, double whi, double tmax, double nmin)
+// what choose_kernel decides: the kernel row, the grid, the w-scheme and its planes
+struct KernelChoice {
+    const KernelRow *row = nullptr;  // W, beta, sigma, eps_max of the ES kernel
+    int64_t nu = 0, nv = 0, npl = 1;
+    double dw = 1.0;
+    int mode = 0, nder = 0;  // w-scheme (info.wmode); kernel functions per axis of the one-plane scheme
+};
+
+// ONE plane, K kernel functions per axis (gridder_kernels_wd.hpp): K = wd_K, the interpolation in
+// s = l^2 + m^2 measured in choose_kernel; the aliases of the k-th derivative term carry ((1 + 2 sigma) l_max)^(2k)
+// where the wanted term has <= l_max^(2k) at weight omega^k / k!: the row's worst-position error times
+// that sum must still pass
+static double wd_alias_amplification(double omega, int K, int64_t nu, int64_t nv, int64_t nx, int64_t ny)
 {
-    const auto &prm = g->prm;
+    const double gg = std::pow(std::max(1.0 + 2.0 * double(nu) / double(nx), 1.0 + 2.0 * double(nv) / double(ny)), 2);
+    double amp = 0.0, term = 1.0;
+    for (int k = 0; k < K; ++k) {
+        amp += term;
+        term *= omega * gg / double(k + 1);
+    }
+    return amp;
+}
+
+// Cost of one Hessian apply (both directions), from the C2 / C5 profiles (profiles/r01g_*):
+//  plane transform, per plane: hand-written row FFTs + fused second axis 2.7e-11 s per grid
+//  point; rocFFT rows + separate pad / crop kernels = measured 2-D transform time + three
+//  streaming passes at 5 TB/s;
+//  scatter + gather: 0.30 ns per visibility and touched plane, independent of W <= 16 (the
+//  diagonal walk always takes 16 steps of LDS atomics / reads).
+// (x 1.2 on the rocFFT path: its measured table is for the large sizes only, and every distinct size
+// costs 1-3 s of rocFFT plan building that the hand-written path does not have)
+// (doubled row-FFT shapes, > 16384 points: unfused second axis, measured 3.7e-11 s per point on C5)
+static double apply_cost(int W, int64_t nu, int64_t nv, bool own, double nvis, int64_t npl, int64_t touched, int nder, bool wgrid)
+{
+    const double own_pt = (nu > 16384 || nv > 16384) ? 3.7e-11 : 2.7e-11;
+    const double plane_cost = own ? own_pt * double(nu) * double(nv)
+                                  : 1.2 * (fft2d_seconds(nu, nv) + 3.0 * 16.0 * double(nu) * double(nv) / 5.0e12);
+    double gridcost = nvis * double(nder > 0 ? touched : std::min<int64_t>(touched, npl)) * 0.30e-9;
+    // (one-plane scatter: the cells a lane holds of the block frame -- 7 rows of 3 x 20 lanes at W = 16, 4 rows of 4 x 16 lanes
+    // up to W = 15 (2 x 2-cell anchoring at 14 / 15, the sort's 4 x 4 blocks below: fewer flushes) -- and the gather's W
+    // steps: measured at C2, grid + degrid W = 16: 2.38 + 1.66 ms, W = 15: 1.88 + 1.63, relative to the 3.9 ms the
+    // constant above was last checked against)
+    if (nder > 0) gridcost *= W >= 16 ? 1.03 : (W >= 14 ? 0.90 : 0.87);
+    // (the multi-plane register-footprint scatters hold the same frames: 4 cells per lane up to W = 15 against 7 at W = 16 --
+    // k_grid_rec at C2 on three polynomial planes, W = 16: grid 2.31 of 4.05 ms of scatter + gather; the gathers walk 16
+    // steps whatever W)
+    else if (wgrid) gridcost *= W >= 16 ? 1.0 : 0.92;
+    return double(npl) * plane_cost + gridcost;
+}
+
+static KernelChoice choose_kernel(const pfbhip_gridder_params &prm, const PlanSwitches &sw, int64_t nvis_all, double lshift, double mshift,
+                                  double nshift, double wlo, double whi, double tmax, double nmin)
+{
     size_t nrows = 0;
     const KernelRow *tab = kernel_table(&nrows);
     // admissible rows: worst-position (image-edge) 1-D error <= epsilon / ndim.  The L2 error over
@@ -1354,16 +1404,13 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
                         ((prm.do_wgridding && prm.divide_by_n) ? std::max(0.25, std::min(1.0, nmin)) : 1.0);
     // (the interpolation bound of the polynomial w-planes is a true maximum already: it keeps its 2/3 epsilon)
     const double eps_w = 0.5 * w_interp_budget(prm, nmin);
-    const double nvis = double(g->nvis);
+    const double nvis = double(nvis_all);
     const bool wgrid = prm.do_wgridding && tmax > 0.0;
     const double pi = 3.14159265358979323846;
     double best_cost = 1e300;
-    const KernelRow *best = nullptr;
-    int64_t bnu = 0, bnv = 0, bnpl = 1;
-    double bdw = 1.0;
-    int bmode = 0, bnder = 0;
+    KernelChoice best;
     // one-plane scheme (wmode 2): phase centre on axis, the record kernels available, not switched off
-    const bool wd_allowed = sw.wmode2 && g->info.lshift == 0.0 && g->info.mshift == 0.0 &&
+    const bool wd_allowed = sw.wmode2 && lshift == 0.0 && mshift == 0.0 &&
                             (sw.scatter == ScatterForce::Auto || sw.scatter == ScatterForce::Rec);
     // its K depends on the geometry alone: the smallest K from the estimate of the polynomial scheme (at least 2) up to
     // WD_MAX_K whose measured interpolation error in s passes 2 eps_w.  0: none does, or the image reaches the horizon
@@ -1372,7 +1419,7 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
     if (wgrid && wd_allowed) {
         const int K0 = poly_planes_needed(wd_omega, 2.0 * eps_w);
         for (int K = K0; K >= 2 && K <= WD_MAX_K; ++K)
-            if (wd_interp_error(K, wd_smax(prm), 0.5 * (whi - wlo), g->info.nshift) <= 2.0 * eps_w) {  // (NaN: not admitted)
+            if (wd_interp_error(K, wd_smax(prm), 0.5 * (whi - wlo), nshift) <= 2.0 * eps_w) {  // (NaN: not admitted)
                 wd_K = K;
                 break;
             }
@@ -1424,23 +1471,11 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
                 int nder = 0;
                 if (wgrid) {
                     if (mode == 2) {
-                        // ONE plane, K kernel functions per axis (gridder_kernels_wd.hpp): K = wd_K, the interpolation in
-                        // s = l^2 + m^2 measured above; the aliases of the k-th derivative term carry ((1 + 2 sigma) l_max)^(2k)
-                        // where the wanted term has <= l_max^(2k) at weight omega^k / k!: the row's worst-position error times
-                        // that sum must still pass
                         if (wd_K == 0) continue;
-                        const double omega = wd_omega;
-                        const int K = wd_K;
-                        const double gg = std::pow(std::max(1.0 + 2.0 * double(nu) / double(prm.nx), 1.0 + 2.0 * double(nv) / double(prm.ny)), 2);
-                        double amp = 0.0, term = 1.0;
-                        for (int k = 0; k < K; ++k) {
-                            amp += term;
-                            term *= omega * gg / double(k + 1);
-                        }
-                        if (prm.force_W <= 0 && r.eps_sup * amp > eps1) continue;
-                        nder = K;
+                        if (prm.force_W <= 0 && r.eps_sup * wd_alias_amplification(wd_omega, wd_K, nu, nv, prm.nx, prm.ny) > eps1) continue;
+                        nder = wd_K;
                         npl = 1;
-                        touched = K;
+                        touched = wd_K;
                     } else if (mode == 0) {
                         dw = 0.5 / r.sigma / tmax;  // the w axis keeps the oversampling the kernel row was designed for
                         npl = int64_t((whi - wlo) / dw + r.W);
@@ -1455,88 +1490,65 @@ static void choose_kernel(pfbhip_gridder *g, const PlanSwitches &sw, double wlo,
                         touched = npl;
                     }
                 }
-                // Cost of one Hessian apply (both directions), from the C2 / C5 profiles (profiles/r01g_*):
-                //  plane transform, per plane: hand-written row FFTs + fused second axis 2.7e-11 s per grid
-                //  point; rocFFT rows + separate pad / crop kernels = measured 2-D transform time + three
-                //  streaming passes at 5 TB/s;
-                //  scatter + gather: 0.30 ns per visibility and touched plane, independent of W <= 16 (the
-                //  diagonal walk always takes 16 steps of LDS atomics / reads).
-                // (x 1.2 on the rocFFT path: its measured table is for the large sizes only, and every distinct size
-                // costs 1-3 s of rocFFT plan building that the hand-written path does not have)
-                // (doubled row-FFT shapes, > 16384 points: unfused second axis, measured 3.7e-11 s per point on C5)
-                const double own_pt = (nu > 16384 || nv > 16384) ? 3.7e-11 : 2.7e-11;
-                const double plane_cost = own ? own_pt * double(nu) * double(nv)
-                                              : 1.2 * (fft2d_seconds(nu, nv) + 3.0 * 16.0 * double(nu) * double(nv) / 5.0e12);
-                double gridcost = nvis * double(nder > 0 ? touched : std::min<int64_t>(touched, npl)) * 0.30e-9;
-                // (one-plane scatter: the cells a lane holds of the block frame -- 7 rows of 3 x 20 lanes at W = 16, 4 rows of 4 x 16 lanes
-                // up to W = 15 (2 x 2-cell anchoring at 14 / 15, the sort's 4 x 4 blocks below: fewer flushes) -- and the gather's W
-                // steps: measured at C2, grid + degrid W = 16: 2.38 + 1.66 ms, W = 15: 1.88 + 1.63, relative to the 3.9 ms the
-                // constant above was last checked against)
-                if (nder > 0) gridcost *= r.W >= 16 ? 1.03 : (r.W >= 14 ? 0.90 : 0.87);
-                // (the multi-plane register-footprint scatters hold the same frames: 4 cells per lane up to W = 15 against 7 at W = 16 --
-                // k_grid_rec at C2 on three polynomial planes, W = 16: grid 2.31 of 4.05 ms of scatter + gather; the gathers walk 16
-                // steps whatever W)
-                else if (wgrid) gridcost *= r.W >= 16 ? 1.0 : 0.92;
-                const double cost = double(npl) * plane_cost + gridcost;
+                const double cost = apply_cost(r.W, nu, nv, own, nvis, npl, touched, nder, wgrid);
                 // cheapest wins; within 1 % the more accurate row does (W is free up to 16, so the best row
                 // that maps to the same grid and plane count usually beats the requested epsilon)
-                const bool better = best == nullptr || cost < 0.99 * best_cost ||
-                                    (cost <= 1.01 * best_cost && r.eps_sup < best->eps_sup);
+                const bool better = best.row == nullptr || cost < 0.99 * best_cost ||
+                                    (cost <= 1.01 * best_cost && r.eps_sup < best.row->eps_sup);
                 if (better) {
                     best_cost = std::min(cost, best_cost);
-                    best = &r;
-                    bnu = nu;
-                    bnv = nv;
-                    bnpl = npl;
-                    bdw = dw;
-                    bmode = mode;
-                    bnder = nder;
+                    best = KernelChoice{&r, nu, nv, npl, dw, mode, nder};
                 }
             }
         }
     }
-    PFB_REQUIRE(best != nullptr || !(wgrid && prm.force_wmode == 3),
+    PFB_REQUIRE(best.row != nullptr || !(wgrid && prm.force_wmode == 3),
                 "force_wmode=2: the one-plane w-scheme needs the phase centre on axis, a field of view inside the horizon "
                 "(max l^2 + m^2 = %g, must be < 1) and 2..%d kernel functions for this field of view and w range (epsilon=%g); "
                 "leave the scheme to the plan", wd_smax(prm), WD_MAX_K, prm.epsilon);
-    PFB_REQUIRE(best != nullptr || !(wgrid && prm.force_wmode == 2),  // (C-ABI encoding: 0 = plan decides, wmode + 1 otherwise)
+    PFB_REQUIRE(best.row != nullptr || !(wgrid && prm.force_wmode == 2),  // (C-ABI encoding: 0 = plan decides, wmode + 1 otherwise)
                 "force_wmode=1: the polynomial w-plane scheme needs more than %d planes for this field of view and w range "
                 "(epsilon=%g); leave the scheme to the plan", MAX_POLY_PLANES, prm.epsilon);
     // (the table's best row has a worst-position error of 2.3e-12; with the margins above the tightest epsilon a plan accepts is
     // ~1.1e-11 with w-gridding, ~7e-12 without, and 1 / n_min times that with divide_by_n)
-    PFB_REQUIRE(best != nullptr, "no ES kernel reaches epsilon=%g with sigma in [%g, %g]: the tightest epsilon this kernel table admits "
+    PFB_REQUIRE(best.row != nullptr, "no ES kernel reaches epsilon=%g with sigma in [%g, %g]: the tightest epsilon this kernel table admits "
                 "is ~1.1e-11 with w-gridding (~7e-12 without; times 1 / min(n) with divide_by_n) at sigma_max >= 2.5",
                 prm.epsilon, prm.sigma_min, prm.sigma_max);
+    return best;
+}
+
+// the choice as the handle keeps it: info, the planes' w, and the Chebyshev nodes / Lagrange denominators of wmode 1
+static void apply_choice(pfbhip_gridder *g, const KernelChoice &c, double wlo, double whi)
+{
+    const double pi = 3.14159265358979323846;
     auto &info = g->info;
-    info.W = best->W;
-    info.beta = best->beta;
-    info.sigma = best->sigma;
-    info.kernel_eps = best->eps_max;
-    info.nu = bnu;
-    info.nv = bnv;
-    info.nplanes = bnpl;
-    info.dw = bdw;
-    info.wmode = bmode;
-    info.nderiv = bnder;
+    info.W = c.row->W;
+    info.beta = c.row->beta;
+    info.sigma = c.row->sigma;
+    info.kernel_eps = c.row->eps_max;
+    info.nu = c.nu;
+    info.nv = c.nv;
+    info.nplanes = c.npl;
+    info.dw = c.dw;
+    info.wmode = c.mode;
+    info.nderiv = c.nder;
     info.occ_rows = 0;
     info.wcenter = 0.5 * (wlo + whi);
     info.whalf = 0.5 * (whi - wlo);
-    info.wmin = (prm.do_wgridding && bmode == 0) ? 0.5 * (wlo + whi) - 0.5 * double(bnpl - 1) * bdw : 0.0;
+    info.wmin = (g->prm.do_wgridding && c.mode == 0) ? 0.5 * (wlo + whi) - 0.5 * double(c.npl - 1) * c.dw : 0.0;
     info.tile = TILE;
-    g->wplanes.assign(size_t(bnpl), 0.0);
-    g->nodes.clear();
-    g->lagr_coef.clear();
-    if (bmode == 0) {
-        for (int64_t p = 0; p < bnpl; ++p) g->wplanes[size_t(p)] = info.wmin + double(p) * bdw;
-    } else if (bmode == 2) {
+    g->wplanes.assign(size_t(c.npl), 0.0);
+    if (c.mode == 0) {
+        for (int64_t p = 0; p < c.npl; ++p) g->wplanes[size_t(p)] = info.wmin + double(p) * c.dw;
+    } else if (c.mode == 2) {
         g->wplanes[0] = info.wcenter;
     } else {
-        for (int64_t p = 0; p < bnpl; ++p) g->nodes.push_back(-std::cos(pi * (2.0 * double(p) + 1.0) / (2.0 * double(bnpl))));
-        for (int64_t p = 0; p < bnpl; ++p) {
-            double c = 1.0;
-            for (int64_t m = 0; m < bnpl; ++m)
-                if (m != p) c /= (g->nodes[size_t(p)] - g->nodes[size_t(m)]);
-            g->lagr_coef.push_back(c);
+        for (int64_t p = 0; p < c.npl; ++p) g->nodes.push_back(-std::cos(pi * (2.0 * double(p) + 1.0) / (2.0 * double(c.npl))));
+        for (int64_t p = 0; p < c.npl; ++p) {
+            double d = 1.0;
+            for (int64_t m = 0; m < c.npl; ++m)
+                if (m != p) d /= (g->nodes[size_t(p)] - g->nodes[size_t(m)]);
+            g->lagr_coef.push_back(d);
             g->wplanes[size_t(p)] = info.wcenter + info.whalf * g->nodes[size_t(p)];
         }
     }
@@ -1562,18 +1574,50 @@ static void nm1_range(const pfbhip_gridder_params &p, double lshift, double mshi
         }
 }
 
-static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq, const uint8_t *mask)
-{
-    auto &prm = g->prm;
+// ---------------------------------------------------------------------------------------
+// plan creation, step by step (create_impl at the end): every step reads the handle and the scratch below and fills in its
+// part of both.  The host combinatorics are in plan_layout.hpp.
+// ---------------------------------------------------------------------------------------
+
+// What one step of plan creation hands to a later one.  It is destroyed when creation ends: nothing of it stays in the handle.
+struct PlanBuild {
     const PlanSwitches sw = read_plan_switches();
     PlanPath path;  // (g->path once complete)
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {  // verbosity >= 1: wall-clock of the plan-creation phases
-        if (prm.verbosity < 1) return;
+    double tmax = 0.0, nm1min = 0.0;  // largest |n - 1 + nshift| and smallest n - 1 of the image
+    double wlo = 0.0, whi = 0.0;      // w range of the unmasked visibilities
+    bool plane_sorted = false;        // sort key (tile, first plane): a work list per pass
+    // the tile sort's device buffers; the values of k_out / v_out are the sorted keys / visibility indices
+    struct SortScratch {
+        DevBuf<uint32_t> k_in, k_out, v_in, v_out;
+        DevBuf<char> tmp;
+        DevBuf<uint32_t> d_tstart;
+        explicit SortScratch(size_t nvis) : k_in(nvis), k_out(nvis), v_in(nvis), v_out(nvis) {}
+    };
+    std::unique_ptr<SortScratch> sort;  // (sort_by_tile .. sorted_coordinates)
+    std::vector<uint32_t> tstart;       // first sorted visibility of every key, nactive at the end; empty without visibilities
+    WorkLists lists;                    // work items of every pass (d_work), their count at CHUNK visibilities each
+    uint32_t chunk_used = CHUNK;        // visibilities per work item
+    std::vector<uint8_t> occ;           // occupied 32-row blocks of the uv-plane (d_occ)
+    // uploaded without a synchronisation of their own: they live until creation's last one
+    std::vector<double> fc, cfu, cfv, cheb;
+    size_t fft_work = 0;      // largest work buffer a rocFFT plan asks for
+    bool any_rocfft = false;  // some transform runs on rocFFT
+    int verbosity = 0;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+
+    void lap(const char *what)  // verbosity >= 1: wall-clock of the plan-creation phases
+    {
+        if (verbosity < 1) return;
         auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[pfbhip] plan: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
-    };
+    }
+};
+
+// (also sets g->nvis, between the checks that bound its factors and the check of the product)
+static void validate_params(pfbhip_gridder *g, const double *uvw, const double *freq)
+{
+    const auto &prm = g->prm;
     PFB_REQUIRE(prm.nrow >= 0 && prm.nchan >= 1, "bad visibility shape (%lld, %lld)", (long long)prm.nrow,
                 (long long)prm.nchan);
     PFB_REQUIRE(prm.nx >= 2 && prm.ny >= 2 && prm.nx <= 65536 && prm.ny <= 65536, "bad image shape (%lld, %lld)",
@@ -1585,7 +1629,12 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     PFB_REQUIRE(g->nvis < (int64_t(1) << 31), "too many visibilities per handle (%lld >= 2^31)", (long long)g->nvis);
     PFB_REQUIRE(uvw != nullptr || prm.nrow == 0, "uvw is NULL");
     PFB_REQUIRE(freq != nullptr, "freq is NULL");
+}
 
+// device, stream, phase-centre geometry, the uploads of uvw / fc / mask and what of MapArgs does not depend on the kernel choice
+static void setup_geometry_and_upload(pfbhip_gridder *g, PlanBuild &pb, const double *uvw, const double *freq, const uint8_t *mask)
+{
+    const auto &prm = g->prm;
     PFB_HIP(hipGetDevice(&g->device));
     PFB_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     g->timer.stream = g->stream;
@@ -1595,20 +1644,20 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // geometry
     info.lshift = prm.flip_u ? -prm.center_x : prm.center_x;
     info.mshift = prm.flip_v ? -prm.center_y : prm.center_y;
-    double nm1min, nm1max;
-    nm1_range(prm, info.lshift, info.mshift, &nm1min, &nm1max);
-    info.nshift = prm.do_wgridding ? -0.5 * (nm1max + nm1min) : 0.0;
-    const double tmax = std::max(std::fabs(nm1max + info.nshift), std::fabs(nm1min + info.nshift));
+    double nm1max;
+    nm1_range(prm, info.lshift, info.mshift, &pb.nm1min, &nm1max);
+    info.nshift = prm.do_wgridding ? -0.5 * (nm1max + pb.nm1min) : 0.0;
+    pb.tmax = std::max(std::fabs(nm1max + info.nshift), std::fabs(pb.nm1min + info.nshift));
     g->shifting = (info.lshift != 0.0) || (info.mshift != 0.0) || (info.nshift != 0.0);
 
     // upload uvw / fc / mask
     const size_t nrow1 = size_t(std::max<int64_t>(prm.nrow, 1));
     g->d_uvw.alloc(nrow1 * 3);
     if (prm.nrow) PFB_HIP(hipMemcpyAsync(g->d_uvw.p, uvw, size_t(prm.nrow) * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    std::vector<double> fc(prm.nchan);
-    for (int64_t c = 0; c < prm.nchan; ++c) fc[c] = freq[c] / SPEED_OF_LIGHT;
+    pb.fc.resize(size_t(prm.nchan));
+    for (int64_t c = 0; c < prm.nchan; ++c) pb.fc[size_t(c)] = freq[c] / SPEED_OF_LIGHT;
     g->d_fc.alloc(size_t(prm.nchan));
-    PFB_HIP(hipMemcpyAsync(g->d_fc.p, fc.data(), fc.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    PFB_HIP(hipMemcpyAsync(g->d_fc.p, pb.fc.data(), pb.fc.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (mask && g->nvis) {
         g->d_mask.alloc(size_t(g->nvis));
         PFB_HIP(hipMemcpyAsync(g->d_mask.p, mask, size_t(g->nvis), hipMemcpyHostToDevice, st));
@@ -1627,31 +1676,36 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     m.py = prm.pixsize_y;
     m.do_w = prm.do_wgridding;
     m.swap_uv = 1;
+}
 
-    // w range over unmasked visibilities
-    double wlo = 0.0, whi = 0.0;
-    if (prm.do_wgridding && g->nvis > 0) {
+// w range over unmasked visibilities
+static void w_range(pfbhip_gridder *g, PlanBuild &pb)
+{
+    hipStream_t st = g->stream;
+    if (g->prm.do_wgridding && g->nvis > 0) {
         const int nb = 512;
         DevBuf<double> d_mm(2 * nb);
-        hipLaunchKernelGGL(k_wrange, dim3(nb), dim3(256), 0, st, m, d_mm.p);
+        hipLaunchKernelGGL(k_wrange, dim3(nb), dim3(256), 0, st, g->map, d_mm.p);
         PFB_HIP(hipGetLastError());
         std::vector<double> mm(2 * nb);
         PFB_HIP(hipMemcpyAsync(mm.data(), d_mm.p, mm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
-        wlo = 1e300;
-        whi = -1e300;
+        PFB_HIP(hipStreamSynchronize(st));  // mm is read here, d_mm is a local
+        pb.wlo = 1e300;
+        pb.whi = -1e300;
         for (int b = 0; b < nb; ++b) {
-            wlo = std::min(wlo, mm[2 * b]);
-            whi = std::max(whi, mm[2 * b + 1]);
+            pb.wlo = std::min(pb.wlo, mm[2 * b]);
+            pb.whi = std::max(pb.whi, mm[2 * b + 1]);
         }
-        if (wlo > whi) wlo = whi = 0.0;  // everything masked
+        if (pb.wlo > pb.whi) pb.wlo = pb.whi = 0.0;  // everything masked
     }
+}
 
-    lap("upload + w range");
-    choose_kernel(g, sw, wlo, whi, tmax, 1.0 + nm1min);
-    PFB_REQUIRE(info.nplanes >= 1 && info.nplanes < 100000, "unreasonable number of w-planes (%lld)",
-                (long long)info.nplanes);
-
+// the rest of MapArgs, the tile counts and the image / grid geometry, once the kernel and the grid are chosen
+static void finish_map_args(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    MapArgs &m = g->map;
     m.nu = int(info.nu);
     m.nv = int(info.nv);
     m.dnu = double(info.nu);
@@ -1671,159 +1725,106 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 
     g->geom = ImgGeom{int(prm.nx), int(prm.ny), int(info.nu), int(info.nv), int(info.nu), int(info.nv), prm.pixsize_x, prm.pixsize_y,
                       info.lshift, info.mshift, info.nshift};
+    // (row pitch of the uv-plane buffer: see the B pitch in setup_transforms; rocFFT row plans on A need the dense pitch)
+    RowFFTPlan probe;
+    const bool own_v = pb.sw.rowfft && rowfft_make_plan(info.nv, &probe);
+    g->geom.apitch = int(info.nv) + (own_v ? 8 : 0);
+    g->plane_stride = size_t(info.nu) * size_t(g->geom.apitch);
+}
 
-    // ---- tile sort of the unmasked visibilities ----
+// ---- tile sort of the unmasked visibilities: keys, radix sort, the start of every key ----
+static void sort_by_tile(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    MapArgs &m = g->map;
+    hipStream_t st = g->stream;
     g->kp_max = int(std::min<int64_t>(KP_MAX, info.nplanes));
-    const int64_t ngroups = ceil_div(info.nplanes, g->kp_max);
     // Wide fields (ES-kernel planes, P > W + planes per pass): a visibility touches only W of the P
     // planes.  Sorting by (tile, first plane) makes the visibilities that touch a pass's planes a
     // contiguous range per tile, so every pass gets its own, shorter work list.
-    const bool plane_sorted = prm.do_wgridding && info.wmode == 0 && info.nplanes > info.W + g->kp_max - 1 &&
-                              info.ntiles * info.nplanes < (int64_t(1) << 32) - 2;
-    m.key_planes = plane_sorted ? int(info.nplanes) : 1;
+    pb.plane_sorted = prm.do_wgridding && info.wmode == 0 && info.nplanes > info.W + g->kp_max - 1 &&
+                      info.ntiles * info.nplanes < (int64_t(1) << 32) - 2;
+    m.key_planes = pb.plane_sorted ? int(info.nplanes) : 1;
     const int64_t nkeys = info.ntiles * m.key_planes;
-    m.key_sub = sort_key_sub(sw, int(info.W), nkeys);
-    std::vector<WorkItem> work;
-    uint32_t chunk_used = CHUNK;
-    size_t coarse_items = 0;  // work items at CHUNK visibilities each (the size measure of the launch-shape decisions below)
-    g->work_off.clear();
-    g->work_cnt.clear();
+    m.key_sub = sort_key_sub(pb.sw, int(info.W), nkeys);
     info.nactive = 0;
-    if (g->nvis > 0) {
-        DevBuf<uint32_t> k_in(size_t(g->nvis)), k_out(size_t(g->nvis)), v_in(size_t(g->nvis)), v_out(size_t(g->nvis));
-        hipLaunchKernelGGL(k_keys, blocks1d(g->nvis), dim3(256), 0, st, m, k_in.p, v_in.p);
+    if (g->nvis == 0) return;
+    pb.sort = std::make_unique<PlanBuild::SortScratch>(size_t(g->nvis));
+    auto &s = *pb.sort;
+    hipLaunchKernelGGL(k_keys, blocks1d(g->nvis), dim3(256), 0, st, m, s.k_in.p, s.v_in.p);
+    PFB_HIP(hipGetLastError());
+    size_t tmp_bytes = 0;
+    PFB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, s.k_in.p, s.k_out.p, s.v_in.p, s.v_out.p, int(g->nvis), 0,
+                                               32, st));
+    s.tmp.alloc(tmp_bytes);
+    PFB_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp.p, tmp_bytes, s.k_in.p, s.k_out.p, s.v_in.p, s.v_out.p, int(g->nvis), 0,
+                                               32, st));
+    s.d_tstart.alloc(size_t(nkeys) + 1);
+    hipLaunchKernelGGL(k_tile_start, blocks1d(nkeys + 1), dim3(256), 0, st, s.k_out.p, g->nvis, uint32_t(nkeys), uint32_t(m.key_sub),
+                       s.d_tstart.p);
+    PFB_HIP(hipGetLastError());
+    pb.lap("keys + radix sort");
+    pb.tstart.resize(size_t(nkeys) + 1);
+    PFB_HIP(hipMemcpyAsync(pb.tstart.data(), s.d_tstart.p, pb.tstart.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PFB_HIP(hipStreamSynchronize(st));  // tstart is read from here on
+    info.nactive = pb.tstart[size_t(nkeys)];
+    pb.lap("tile starts");
+}
+
+// the work items of every pass
+static void build_work_lists(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &info = g->info;
+    if (g->nvis > 0) pb.chunk_used = gather_chunk(info.wmode, info.nactive);
+    pb.lists = split_work(pb.tstart, info.ntiles, g->map.key_planes, info.nplanes, info.W, g->kp_max, pb.plane_sorted, pb.chunk_used);
+    g->work_off = pb.lists.work_off;
+    g->work_cnt = pb.lists.work_cnt;
+    if (g->nvis > 0) pb.lap("work lists");
+}
+
+// grid coordinates and source index of the active visibilities in sorted order; the sort's buffers go
+static void sorted_coordinates(pfbhip_gridder *g, PlanBuild &pb)
+{
+    if (g->nvis == 0) return;
+    const auto &info = g->info;
+    hipStream_t st = g->stream;
+    const size_t na1 = size_t(std::max<int64_t>(info.nactive, 1));
+    g->d_pu.alloc(na1);
+    g->d_pv.alloc(na1);
+    g->d_pw.alloc(na1);
+    g->d_src.alloc(na1);
+    if (info.nactive) {
+        hipLaunchKernelGGL(k_records, blocks1d(info.nactive), dim3(256), 0, st, g->map, pb.sort->v_out.p, info.nactive, g->d_pu.p,
+                           g->d_pv.p, g->d_pw.p, g->d_src.p);
         PFB_HIP(hipGetLastError());
-        size_t tmp_bytes = 0;
-        PFB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p, int(g->nvis), 0,
-                                                   32, st));
-        DevBuf<char> tmp(tmp_bytes);
-        PFB_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p, int(g->nvis), 0,
-                                                   32, st));
-        DevBuf<uint32_t> d_tstart(size_t(nkeys) + 1);
-        hipLaunchKernelGGL(k_tile_start, blocks1d(nkeys + 1), dim3(256), 0, st, k_out.p, g->nvis, uint32_t(nkeys), uint32_t(m.key_sub),
-                           d_tstart.p);
-        PFB_HIP(hipGetLastError());
-        lap("keys + radix sort");
-        std::vector<uint32_t> tstart(size_t(nkeys) + 1);
-        PFB_HIP(hipMemcpyAsync(tstart.data(), d_tstart.p, tstart.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
-        info.nactive = tstart[size_t(nkeys)];
-        lap("tile starts");
-        const int64_t P = m.key_planes;
-        // visibilities per work item (<= CHUNK): smaller items balance the launch tail, larger ones amortise the per-item
-        // prologue / tile flush
-        uint32_t chunk = CHUNK;
-        if (info.wmode == 2) {  // the one-plane gather (256-thread workgroups, 768 slots): about three items per slot, 512..4096 each
-            chunk = 512;
-            while (chunk < CHUNK && double(chunk) * 1.5 < double(info.nactive) / (3.0 * 768.0)) chunk *= 2;
-        }
-        chunk_used = chunk;
-        for (int64_t grp = 0; grp < (plane_sorted ? ngroups : 1); ++grp) {
-            // planes [q, q + kp) are touched by visibilities whose first plane lies in [q - W + 1, q + kp - 1]
-            const int64_t q = grp * g->kp_max, kp = std::min<int64_t>(g->kp_max, info.nplanes - q);
-            const int64_t lo_p = plane_sorted ? std::max<int64_t>(0, q - info.W + 1) : 0;
-            const int64_t hi_p = plane_sorted ? std::min<int64_t>(P - 1, q + kp - 1) : 0;
-            const size_t first = work.size();
-            for (int64_t t = 0; t < info.ntiles; ++t) {
-                const uint32_t b0 = tstart[size_t(t * P + lo_p)], b1 = tstart[size_t(t * P + hi_p + 1)];
-                // a tile's visibilities in equal parts of <= chunk (4096 + 904 would leave a short item behind a long one)
-                const uint32_t nt = b1 - b0, parts = (nt + chunk - 1) / chunk;
-                coarse_items += (nt + CHUNK - 1) / CHUNK;
-                for (uint32_t q = 0; q < parts; ++q)
-                    work.push_back(WorkItem{uint32_t(t), b0 + uint32_t(uint64_t(nt) * q / parts), b0 + uint32_t(uint64_t(nt) * (q + 1) / parts), 0});
-            }
-            // Longest-processing-time-first: heavy chunks are dispatched first, the many tiny ones of the
-            // sparse outer uv-plane fill the tail (the uv density is strongly peaked at the centre).
-            std::stable_sort(work.begin() + first, work.end(),
-                             [](const WorkItem &x, const WorkItem &y) { return (x.end - x.begin) > (y.end - y.begin); });
-            g->work_off.push_back(first);
-            g->work_cnt.push_back(work.size() - first);
-        }
-        lap("work lists");
-        const size_t na1 = size_t(std::max<int64_t>(info.nactive, 1));
-        g->d_pu.alloc(na1);
-        g->d_pv.alloc(na1);
-        g->d_pw.alloc(na1);
-        g->d_src.alloc(na1);
-        if (info.nactive) {
-            hipLaunchKernelGGL(k_records, blocks1d(info.nactive), dim3(256), 0, st, m, v_out.p, info.nactive, g->d_pu.p,
-                               g->d_pv.p, g->d_pw.p, g->d_src.p);
-            PFB_HIP(hipGetLastError());
-        }
-        PFB_HIP(hipStreamSynchronize(st));
     }
-    if (g->work_off.empty()) {
-        g->work_off.push_back(0);
-        g->work_cnt.push_back(0);
-    }
-    // (row pitch of the uv-plane buffer: see the B pitch below; rocFFT row plans on A need the dense pitch)
-    {
-        RowFFTPlan probe;
-        const bool own_v = sw.rowfft && rowfft_make_plan(info.nv, &probe);
-        g->geom.apitch = int(info.nv) + (own_v ? 8 : 0);
-    }
-    g->plane_stride = size_t(info.nu) * size_t(g->geom.apitch);
-    {
-        const size_t npass = std::max<size_t>(g->work_cnt.size(), 1);
-        const WorkShape ws{m.key_sub, work.size(), work.size() / npass, coarse_items / npass,
-                           g->plane_stride * size_t(g->kp_max) * sizeof(double2)};
-        path = choose_kernels(sw, prm, info, g->kp_max, ws);
-    }
-    {
-        // colour slices of every group's list (LPT order kept inside a slice); chunks of a tile that has several in the
-        // slice are flagged shared (pad = 1) and keep the atomic flush
-        // The one-plane scatter runs 256-thread workgroups: an item of 4096 visibilities is 1024 per wave, longer than a whole
-        // colour launch of a mid-size plan should take (4096^2, 4e6 visibilities: grid 1.61 ms -> 1.02 with items of <= 1024; C2
-        // indifferent between 1024 and 4096).  Its lists are cut finer than the gather's: about three items per workgroup
-        // slot and launch, 512..2048 visibilities each.
-        uint32_t schunk = chunk_used;
-        if (info.wmode == 2) {
-            const double per_launch = double(info.nactive) / (path.coloured ? 4.0 : 1.0);
-            uint32_t c = 512;
-            while (c < 2048 && double(c) * 1.5 < per_launch / (3.0 * 768.0)) c *= 2;
-            schunk = std::min(c, chunk_used);
-        }
-        std::vector<WorkItem> wcol;
-        wcol.reserve(work.size());
-        g->col_off.clear();
-        g->col_cnt.clear();
-        std::vector<uint32_t> seen;
-        for (size_t grp = 0; grp < g->work_off.size(); ++grp) {
-            const size_t b0 = g->work_off[grp], b1 = b0 + g->work_cnt[grp];
-            seen.assign(size_t(info.ntiles), 0);
-            for (size_t i = b0; i < b1; ++i) seen[work[i].tile]++;
-            for (int col = 0; col < 4; ++col) {
-                g->col_off.push_back(wcol.size());
-                for (size_t i = b0; i < b1; ++i) {
-                    const uint32_t tu = work[i].tile / uint32_t(m.ntv), tv = work[i].tile % uint32_t(m.ntv);
-                    const int c = path.coloured ? int((tu & 1u) * 2u + (tv & 1u)) : 0;
-                    if (c != col) continue;
-                    WorkItem w = work[i];
-                    const uint32_t nt = w.end - w.begin, parts = (nt + schunk - 1) / schunk;
-                    w.pad = (!path.coloured || seen[w.tile] > 1 || parts > 1) ? 1u : 0u;
-                    for (uint32_t q = 0; q < std::max(parts, 1u); ++q) {
-                        WorkItem wq = w;
-                        wq.begin = w.begin + uint32_t(uint64_t(nt) * q / std::max(parts, 1u));
-                        wq.end = w.begin + uint32_t(uint64_t(nt) * (q + 1) / std::max(parts, 1u));
-                        wcol.push_back(wq);
-                    }
-                }
-                if (schunk < chunk_used)  // (the finer split interleaves the parts of neighbouring items: heaviest first again)
-                    std::stable_sort(wcol.begin() + std::ptrdiff_t(g->col_off.back()), wcol.end(),
-                                     [](const WorkItem &x, const WorkItem &y) { return (x.end - x.begin) > (y.end - y.begin); });
-                g->col_cnt.push_back(wcol.size() - g->col_off.back());
-            }
-        }
-        if (g->col_off.empty()) {
-            g->col_off.assign(4, 0);
-            g->col_cnt.assign(4, 0);
-        }
-        g->d_work_col.alloc(std::max<size_t>(wcol.size(), 1));
-        if (!wcol.empty())
-            PFB_HIP(hipMemcpyAsync(g->d_work_col.p, wcol.data(), wcol.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipStreamSynchronize(st));  // wcol is a local
-    }
-    // per-visibility records of the record scatter, the row-walk gather and the one-plane kernels
+    PFB_HIP(hipStreamSynchronize(st));  // the sort's buffers are released
+    pb.sort.reset();
+}
+
+// the colour slices of the work lists (d_work_col), cut to the scatter's item size
+static void upload_colour_slices(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    const auto &info = g->info;
+    hipStream_t st = g->stream;
+    const uint32_t schunk = scatter_chunk(info.wmode, info.nactive, pb.path.coloured, pb.chunk_used);
+    ColourSlices cs = colour_slices(pb.lists.work, g->work_off, g->work_cnt, info.ntiles, g->map.ntv, pb.path.coloured, schunk, pb.chunk_used);
+    g->col_off = std::move(cs.col_off);
+    g->col_cnt = std::move(cs.col_cnt);
+    g->d_work_col.alloc(std::max<size_t>(cs.wcol.size(), 1));
+    if (!cs.wcol.empty())
+        PFB_HIP(hipMemcpyAsync(g->d_work_col.p, cs.wcol.data(), cs.wcol.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+    PFB_HIP(hipStreamSynchronize(st));  // cs.wcol is a local
+}
+
+// per-visibility records of the record scatter, the row-walk gather and the one-plane kernels; the work items (d_work)
+static void build_records(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    auto &info = g->info;
+    const PlanPath &path = pb.path;
+    const auto &work = pb.lists.work;
+    hipStream_t st = g->stream;
     if (path.scatter == Scatter::Rec || path.scatter == Scatter::OnePlane || path.gather != Gather::Walk) {
         g->d_rec.alloc(size_t(info.nactive) + REC_PAD);
         g->d_pval.alloc((size_t(info.nactive) + REC_PAD) * size_t(info.wmode == 2 ? info.nderiv : g->kp_max));
@@ -1835,7 +1836,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             PFB_HIP(hipGetLastError());
             if (path.gather == Gather::RowWalk) {
                 g->d_kw.alloc((size_t(info.nactive) + REC_PAD) * size_t(g->kp_max));
-                // (the planes / polynomial nodes are set by choose_kernel; the work list is not needed here)
+                // (the planes / polynomial nodes are set by apply_choice; the work list is not needed here)
                 GroupArgs ga = g->group_args(0, int(info.nplanes));
                 hipLaunchKernelGGL((k_plane_weights<W>), blocks1d(info.nactive + REC_PAD), dim3(256), 0, st, ga, info.nactive, g->d_kw.p);
                 PFB_HIP(hipGetLastError());
@@ -1845,129 +1846,122 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     }
     info.nwork = int64_t(work.size());
     g->d_work.alloc(std::max<size_t>(work.size(), 1));
-    if (!work.empty())
+    if (!work.empty())  // (pb.lists.work outlives creation's last synchronisation)
         PFB_HIP(hipMemcpyAsync(g->d_work.p, work.data(), work.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+}
 
-    lap("records");
-    // ---- kernel polynomial table ----
-    {
-        double perr = 0.0;
-        std::vector<double> ktab = kernel_poly_table(info.W, info.beta, &perr);
-        PFB_REQUIRE(perr <= 0.25 * info.kernel_eps, "kernel polynomial too coarse (err %g vs kernel eps %g)", perr,
-                    info.kernel_eps);
-        g->d_ktab.alloc(ktab.size());
-        PFB_HIP(hipMemcpyAsync(g->d_ktab.p, ktab.data(), ktab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        if (info.wmode == 2) {
-            // one-plane scheme: derivative tables of the kernel polynomial, interpolation nodes in s, per-visibility coefficients
-            const int K = info.nderiv, W = info.W, D1 = kernel_poly_degree(W) + 1;
-            WdArgs &wa = g->wd;
-            wa = WdArgs{};
-            wa.K = K;
-            wa.W = W;
-            wa.bc = path.bc;
-            wa.whalf = info.whalf;
-            wa.nshift = info.nshift;
-            std::vector<double> dtab(size_t(K) * W * D1, 0.0);
-            std::copy(ktab.begin(), ktab.end(), dtab.begin());
-            // x = (a + 1 - W/2 - (z + 1) / 2) 2 / W  =>  d^2/dx^2 = W^2 d^2/dz^2
-            for (int k = 1; k < K; ++k)
-                for (int a = 0; a < W; ++a) {
-                    const double *src = &dtab[(size_t(k - 1) * W + a) * D1];
-                    double *dst = &dtab[(size_t(k) * W + a) * D1];
-                    for (int q = 0; q + 2 < D1; ++q) dst[q] = src[q + 2] * double((q + 2) * (q + 1)) * double(W) * double(W);
-                }
-            g->d_dtab.alloc(dtab.size());
-            PFB_HIP(hipMemcpyAsync(g->d_dtab.p, dtab.data(), dtab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-            wa.dtab = g->d_dtab.p;
-            const double smax = wd_smax(prm);
-            info.smax = smax;
-            const double au = std::pow(double(info.nu) * prm.pixsize_x / (pi_const * double(W)), 2) / smax;
-            const double av = std::pow(double(info.nv) * prm.pixsize_y / (pi_const * double(W)), 2) / smax;
-            for (int q = 0; q < K; ++q) {
-                wa.su[q] = std::pow(-au, q);
-                wa.sv[q] = std::pow(-av, q);
-            }
-            wd_interp_nodes(K, smax, info.nshift, wa.tq, wa.M);
-            g->d_cw.alloc((size_t(info.nactive) + REC_PAD) * size_t(K));
-            wa.cw = g->d_cw.p;
-            wd_launch_coeffs(wa, info.nactive, g->d_pw.p, g->d_cw.p, st);
-            // the interpolation in s on a dense grid of (dw, s) against the closed form: what choose_kernel admitted the plan on
-            const double worst = wd_interp_error(K, smax, info.whalf, info.nshift), bound = w_interp_budget(prm, 1.0 + nm1min);
-            if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] one-plane w-scheme: K = %d, interpolation error %.3g\n", K, worst);
-            PFB_REQUIRE(worst <= bound, "one-plane w-scheme: interpolation error %g exceeds its share %g of epsilon %g", worst, bound,
-                        prm.epsilon);
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+// one-plane scheme: derivative tables of the kernel polynomial, interpolation nodes in s, per-visibility coefficients.
+// Returns the derivative table, which the caller keeps until its upload is synchronised.
+static std::vector<double> setup_one_plane(pfbhip_gridder *g, const PlanBuild &pb, const std::vector<double> &ktab)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    hipStream_t st = g->stream;
+    const int K = info.nderiv, W = info.W, D1 = kernel_poly_degree(W) + 1;
+    WdArgs &wa = g->wd;
+    wa = WdArgs{};
+    wa.K = K;
+    wa.W = W;
+    wa.bc = pb.path.bc;
+    wa.whalf = info.whalf;
+    wa.nshift = info.nshift;
+    std::vector<double> dtab = wd_derivative_table(ktab, K, W, D1);
+    g->d_dtab.alloc(dtab.size());
+    PFB_HIP(hipMemcpyAsync(g->d_dtab.p, dtab.data(), dtab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    wa.dtab = g->d_dtab.p;
+    const double smax = wd_smax(prm);
+    info.smax = smax;
+    const double au = std::pow(double(info.nu) * prm.pixsize_x / (pi_const * double(W)), 2) / smax;
+    const double av = std::pow(double(info.nv) * prm.pixsize_y / (pi_const * double(W)), 2) / smax;
+    for (int q = 0; q < K; ++q) {
+        wa.su[q] = std::pow(-au, q);
+        wa.sv[q] = std::pow(-av, q);
     }
+    wd_interp_nodes(K, smax, info.nshift, wa.tq, wa.M);
+    g->d_cw.alloc((size_t(info.nactive) + REC_PAD) * size_t(K));
+    wa.cw = g->d_cw.p;
+    wd_launch_coeffs(wa, info.nactive, g->d_pw.p, g->d_cw.p, st);
+    // the interpolation in s on a dense grid of (dw, s) against the closed form: what choose_kernel admitted the plan on
+    const double worst = wd_interp_error(K, smax, info.whalf, info.nshift), bound = w_interp_budget(prm, 1.0 + pb.nm1min);
+    if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] one-plane w-scheme: K = %d, interpolation error %.3g\n", K, worst);
+    PFB_REQUIRE(worst <= bound, "one-plane w-scheme: interpolation error %g exceeds its share %g of epsilon %g", worst, bound,
+                prm.epsilon);
+    return dtab;
+}
 
-    // ---- correction image ----
+// ---- kernel polynomial table ----
+static void upload_kernel_tables(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    const auto &info = g->info;
+    hipStream_t st = g->stream;
+    double perr = 0.0;
+    std::vector<double> ktab = kernel_poly_table(info.W, info.beta, &perr);
+    PFB_REQUIRE(perr <= 0.25 * info.kernel_eps, "kernel polynomial too coarse (err %g vs kernel eps %g)", perr,
+                info.kernel_eps);
+    g->d_ktab.alloc(ktab.size());
+    PFB_HIP(hipMemcpyAsync(g->d_ktab.p, ktab.data(), ktab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    std::vector<double> dtab;
+    if (info.wmode == 2) dtab = setup_one_plane(g, pb, ktab);
+    PFB_HIP(hipStreamSynchronize(st));  // ktab and dtab are locals
+}
+
+// ---- correction image ----
+static void build_correction_image(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    const auto &info = g->info;
+    hipStream_t st = g->stream;
     const int64_t npix = prm.nx * prm.ny;
     KernelFT ft(info.W, info.beta);
-    std::vector<double> cfu = ft.correction_1d(prm.nx, info.nu);
-    std::vector<double> cfv = (prm.ny == prm.nx && info.nv == info.nu) ? cfu : ft.correction_1d(prm.ny, info.nv);
-    g->d_cfu.alloc(cfu.size());
-    g->d_cfv.alloc(cfv.size());
-    PFB_HIP(hipMemcpyAsync(g->d_cfu.p, cfu.data(), cfu.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    PFB_HIP(hipMemcpyAsync(g->d_cfv.p, cfv.data(), cfv.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    std::vector<double> cheb{1.0};
+    pb.cfu = ft.correction_1d(prm.nx, info.nu);
+    pb.cfv = (prm.ny == prm.nx && info.nv == info.nu) ? pb.cfu : ft.correction_1d(prm.ny, info.nv);
+    g->d_cfu.alloc(pb.cfu.size());
+    g->d_cfv.alloc(pb.cfv.size());
+    PFB_HIP(hipMemcpyAsync(g->d_cfu.p, pb.cfu.data(), pb.cfu.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    PFB_HIP(hipMemcpyAsync(g->d_cfv.p, pb.cfv.data(), pb.cfv.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    pb.cheb.assign(1, 1.0);
     double zmax = 1.0;
-    const bool use_psiw = prm.do_wgridding && tmax > 0.0 && info.wmode == 0;
+    const bool use_psiw = prm.do_wgridding && pb.tmax > 0.0 && info.wmode == 0;
     if (use_psiw) {
-        zmax = tmax * info.dw * (1.0 + 1e-12);
-        cheb = ft.inverse_cheb(zmax);
+        zmax = pb.tmax * info.dw * (1.0 + 1e-12);
+        pb.cheb = ft.inverse_cheb(zmax);
     }
-    g->d_cheb.alloc(cheb.size());
-    PFB_HIP(hipMemcpyAsync(g->d_cheb.p, cheb.data(), cheb.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    g->d_cheb.alloc(pb.cheb.size());
+    PFB_HIP(hipMemcpyAsync(g->d_cheb.p, pb.cheb.data(), pb.cheb.size() * sizeof(double), hipMemcpyHostToDevice, st));
     g->d_corr.alloc(size_t(npix));
     hipLaunchKernelGGL(k_corr_image, blocks1d(npix), dim3(256), 0, st, g->geom, g->d_cfu.p, g->d_cfv.p, g->d_cheb.p,
-                       int(cheb.size()), info.dw, zmax, prm.do_wgridding ? 1 : 0, use_psiw ? 1 : 0, prm.divide_by_n,
+                       int(pb.cheb.size()), info.dw, zmax, prm.do_wgridding ? 1 : 0, use_psiw ? 1 : 0, prm.divide_by_n,
                        g->d_corr.p);
     PFB_HIP(hipGetLastError());
+}
 
-    lap("kernel table + correction");
-    // ---- scratch + FFT plans ----
+// ---- scratch: the uv-plane buffers (and what the side-stream clear needs), image and sorted-visibility buffers ----
+static void alloc_plane_buffers(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &info = g->info;
+    hipStream_t st = g->stream;
     g->d_grid.alloc(g->plane_stride * size_t(g->kp_max));
-    if (path.side_clear) {
+    if (pb.path.side_clear) {
         g->d_grid2.alloc(g->plane_stride * size_t(g->kp_max));
         PFB_HIP(hipStreamCreateWithFlags(&g->clear_stream, hipStreamNonBlocking));
         PFB_HIP(hipEventCreateWithFlags(&g->ev_clear, hipEventDisableTiming));
         PFB_HIP(hipEventCreateWithFlags(&g->ev_start, hipEventDisableTiming));
         PFB_HIP(hipMemsetAsync(g->d_grid2.p, 0, g->d_grid2.bytes(), st));
     }
-    lap("uv-plane buffers");
-    g->d_img.alloc(size_t(npix));
+    pb.lap("uv-plane buffers");
+    g->d_img.alloc(size_t(g->prm.nx * g->prm.ny));
     g->d_sval.alloc(size_t(std::max<int64_t>(info.nactive, 1)));
     g->d_sacc.alloc(size_t(std::max<int64_t>(info.nactive, 1)));
+}
 
-    // Plane transforms: hand-written row FFT (rowfft.hpp) where the padded sizes are of the form
-    // {1,3,5} x 2^a (every size grid_size() prefers), with the pad / crop / w-screen of the second axis
-    // fused into its load / store; rocFFT row plans otherwise.  PFBHIP_FUSED_FFT=0 / PFBHIP_ROWFFT=0
-    // force the rocFFT paths (used by the tests to keep both alive).
-    if (sw.rowfft || sw.fused_fft) (void)g->rowfft_u.init(info.nu);
-    if (sw.rowfft) (void)g->rowfft_v.init(info.nv);
-    {  // the screen geometry serves the fused kernels and the separate pad / crop kernels alike
-        FusedGeom &fg = g->fgeom;
-        fg.nx = int(prm.nx);
-        fg.ny = int(prm.ny);
-        fg.nu = int(info.nu);
-        fg.px = prm.pixsize_x;
-        fg.py = prm.pixsize_y;
-        fg.lshift = info.lshift;
-        fg.mshift = info.mshift;
-        fg.nshift = info.nshift;
-        if (prm.do_wgridding) fused_geom_fit(fg);
-        if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] w-screen: n-1 polynomial with %d coefficients\n", fg.npoly);
-    }
-    path = choose_transforms(path, sw, prm, g->rowfft_u, g->rowfft_v, g->fgeom.npoly, !work.empty());
-    g->path = path;
-    report_path(path, info);
-    const bool fused = path.axis2 == SecondAxis::Fused;
-    if (path.axis2 == SecondAxis::RocFFT) g->rowfft_u.release();
-    g->plane_groups.clear();
-    g->d_tau.release();
-    if (fused) {
-        // screen form per pass: composite polynomials of the whole phase where it is small, else the separable form (column
-        // table x row factor x residual polynomials; PFBHIP_SEPSCREEN=0 disables), else n - 1 and sincos per pixel and plane
+// screen form per pass of a fused second axis: composite polynomials of the whole phase where it is small, else the separable
+// form (column table x row factor x residual polynomials; PFBHIP_SEPSCREEN=0 disables), else n - 1 and sincos per pixel and plane
+static void fit_screens(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    hipStream_t st = g->stream;
+    if (pb.path.axis2 == SecondAxis::Fused) {
         bool any_sep = false;
         for (int p0 = 0; p0 < info.nplanes; p0 += g->kp_max) {
             FusedPlanes fp;
@@ -1975,7 +1969,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             for (int k = 0; k < FUSED_MAXPLANES; ++k) fp.w[k] = k < fp.kp ? g->wplanes[size_t(p0 + k)] : 0.0;
             // (the doubled shapes' kernels have the separable and the general form only)
             if (prm.do_wgridding && !g->rowfft_u.pl.doubled) fused_planes_fit(g->fgeom, fp);
-            if (fp.nsc == 0 && sw.sepscreen && prm.do_wgridding) fused_planes_fit(g->fgeom, fp, true);
+            if (fp.nsc == 0 && pb.sw.sepscreen && prm.do_wgridding) fused_planes_fit(g->fgeom, fp, true);
             any_sep = any_sep || fp.sep != 0;
             g->plane_groups.push_back(fp);
         }
@@ -1984,7 +1978,7 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
             DevBuf<double> d_w(size_t(info.nplanes));
             PFB_HIP(hipMemcpyAsync(d_w.p, g->wplanes.data(), size_t(info.nplanes) * sizeof(double), hipMemcpyHostToDevice, st));
             fused_screen_table(g->fgeom, d_w.p, int(info.nplanes), g->d_tau.p, st);
-            PFB_HIP(hipStreamSynchronize(st));
+            PFB_HIP(hipStreamSynchronize(st));  // d_w is a local
             for (size_t grp = 0; grp < g->plane_groups.size(); ++grp)
                 g->plane_groups[grp].tau = g->d_tau.p + grp * size_t(g->kp_max) * size_t(prm.nx);
         }
@@ -2006,6 +2000,38 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
         info.screen_composite += (fp.nsc > 0 && !fp.sep) ? 1 : 0;
         info.screen_separable += fp.sep ? 1 : 0;
     }
+}
+
+// Plane transforms: hand-written row FFT (rowfft.hpp) where the padded sizes are of the form
+// {1,3,5} x 2^a (every size grid_size() prefers), with the pad / crop / w-screen of the second axis
+// fused into its load / store; rocFFT row plans otherwise.  PFBHIP_FUSED_FFT=0 / PFBHIP_ROWFFT=0
+// force the rocFFT paths (used by the tests to keep both alive).
+static void setup_transforms(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    const PlanSwitches &sw = pb.sw;
+    if (sw.rowfft || sw.fused_fft) (void)g->rowfft_u.init(info.nu);
+    if (sw.rowfft) (void)g->rowfft_v.init(info.nv);
+    {  // the screen geometry serves the fused kernels and the separate pad / crop kernels alike
+        FusedGeom &fg = g->fgeom;
+        fg.nx = int(prm.nx);
+        fg.ny = int(prm.ny);
+        fg.nu = int(info.nu);
+        fg.px = prm.pixsize_x;
+        fg.py = prm.pixsize_y;
+        fg.lshift = info.lshift;
+        fg.mshift = info.mshift;
+        fg.nshift = info.nshift;
+        if (prm.do_wgridding) fused_geom_fit(fg);
+        if (prm.verbosity > 0) fprintf(stderr, "[pfbhip] w-screen: n-1 polynomial with %d coefficients\n", fg.npoly);
+    }
+    pb.path = choose_transforms(pb.path, sw, prm, g->rowfft_u, g->rowfft_v, g->fgeom.npoly, !pb.lists.work.empty());
+    g->path = pb.path;
+    report_path(pb.path, info);
+    const bool fused = pb.path.axis2 == SecondAxis::Fused;
+    if (pb.path.axis2 == SecondAxis::RocFFT) g->rowfft_u.release();
+    fit_screens(g, pb);
     // Row pitch of B.  A workgroup of the transposing first-axis FFT touches B[y][u] for one u and every y: with a pitch of
     // nu * 16 bytes (a multiple of 2^15 for every size the plan picks) all of a row's 16-byte pieces fall on one L2 /
     // memory channel.  8 more elements (128 bytes) per row walk the channels instead (the rocFFT second axis needs the dense
@@ -2018,188 +2044,167 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     // 16-byte GATHER in that transform's load phase cost 0.3 ms per plane at C2, scattered stores cost 0.1.  The pitch is
     // kept off the power of two for the same reason as bpitch (40 more elements: whole 128-byte lines).  (B is sized for that
     // layout wherever the transposing first axis could run, whether or not the plan takes it.)
-    g->fgeom.tpitch = path.axis1 == FirstAxis::Transposing ? int(prm.ny) + 40 : 0;  // (0: the tile-transpose kernels read B[y][u])
+    g->fgeom.tpitch = pb.path.axis1 == FirstAxis::Transposing ? int(prm.ny) + 40 : 0;  // (0: the tile-transpose kernels read B[y][u])
     if (transposing_possible(fused, g->rowfft_v)) g->bstride = std::max(g->bstride, size_t(info.nu) * size_t(prm.ny + 40));
-    lap("row-FFT tables + w-screens");
+    pb.lap("row-FFT tables + w-screens");
     g->d_gridB.alloc(g->bstride * size_t(fused ? g->kp_max : 1));
-    g->d_accT.alloc(size_t(npix));
-    lap("intermediate plane + image buffers");
+    g->d_accT.alloc(size_t(prm.nx * prm.ny));
+    pb.lap("intermediate plane + image buffers");
+}
 
-    // occupancy of 32-row blocks of the uv-plane: tile rows that hold work, plus the block their
-    // (W-1)-cell halo spills into
-    const int64_t nblk = ceil_div(info.nu, TP);
-    std::vector<uint8_t> occ(size_t(nblk), 0);
-    static_assert(TP == TILE, "row-block occupancy assumes transpose tile == uv tile");
-    // (every block a footprint row can fall in: with a short last block -- nu % 32 < W - 1 -- the footprints of the tile
-    // before it run THROUGH that block and wrap into block 0; marking only the first and the last row's block left it out)
-    for (const WorkItem &wi : work) {
-        const int64_t tu = wi.tile / uint32_t(m.ntv);
-        for (int64_t r = tu * TILE; r <= tu * TILE + TILE + info.W - 2; ++r) occ[size_t((r % info.nu) / TP)] = 1;
+// Which parts of the uv-plane the work items' footprints reach: 32-row blocks (d_occ) and their spans, and per tile row the
+// column runs of touched tiles.  The transposing first-axis transforms load / store only these (d_colruns: RunLoad /
+// RunStore), so they are also what has to be cleared of the scatter's planes (d_clear_rects: side-stream clear of
+// single-pass plans, clear_planes()).
+static void setup_occupancy(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    const auto &work = pb.lists.work;
+    hipStream_t st = g->stream;
+    pb.occ = row_block_occupancy(work, g->map.ntv, info.nu, info.W);
+    std::vector<uint8_t> touched;
+    try {
+        touched = touched_tiles(work, info.ntiles, g->map.ntv, info.nu, info.nv, info.W);
+    } catch (const LayoutError &e) {
+        PFB_REQUIRE(false, "%s", e.what());
     }
-    // tiles a footprint cell of some work item can fall in (the item's own tile and the tiles its (W - 1)-cell halo reaches,
-    // wrapped; through a short last tile if the grid size is not a multiple of TILE).  Per TILE with work, and per row /
-    // column of its region rather than per cell: the per-cell, per-item form of this loop was 0.1 s of the 0.13 s a C2 plan
-    // takes and 3.1 s of C5's 3.3 (18 449 / 400 000 work items x 47^2 cells x two passes).
-    std::vector<uint8_t> touched_tiles;
+    const ColumnRuns cr = column_runs(touched, info.nu, info.nv, g->map.ntv);
+    static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "Int4 is uploaded as int4");
     if (!work.empty()) {
-        const int64_t ntu_t = ceil_div(info.nu, TILE), ntv_t = m.ntv;
-        touched_tiles.assign(size_t(ntu_t * ntv_t), 0);
-        std::vector<uint8_t> seen(size_t(info.ntiles), 0);
-        for (const WorkItem &wi : work) {
-            if (seen[wi.tile]) continue;
-            seen[wi.tile] = 1;
-            const int64_t tu = wi.tile / uint32_t(m.ntv), tv = wi.tile % uint32_t(m.ntv);
-            constexpr int MAXT = 8;  // (own tile, short last tile, tile 0, ...: four on the smallest grids)
-            int64_t tr[MAXT], tc[MAXT];
-            int ntr = 0, ntc = 0;
-            for (int64_t r = tu * TILE; r <= tu * TILE + TILE + info.W - 2; ++r) {
-                const int64_t t = (r % info.nu) / TILE;
-                if (ntr == 0 || (tr[ntr - 1] != t && ntr < MAXT)) tr[ntr++] = t;
-                PFB_REQUIRE(tr[ntr - 1] == t, "tile rows of a footprint region");
-            }
-            for (int64_t q = tv * TILE; q <= tv * TILE + TILE + info.W - 2; ++q) {
-                const int64_t t = (q % info.nv) / TILE;
-                if (ntc == 0 || (tc[ntc - 1] != t && ntc < MAXT)) tc[ntc++] = t;
-                PFB_REQUIRE(tc[ntc - 1] == t, "tile columns of a footprint region");
-            }
-            for (int a = 0; a < ntr; ++a)
-                for (int b = 0; b < ntc; ++b) touched_tiles[size_t(tr[a] * ntv_t + tc[b])] = 1;
+        info.used_cells = cr.cells;
+        if (!cr.rects.empty() && cr.cells * 10 < cr.full * 8) {  // (fragmented or nearly full coverage: plain memsets of whole rows)
+            g->d_clear_rects.alloc(cr.rects.size());
+            PFB_HIP(hipMemcpyAsync(g->d_clear_rects.p, cr.rects.data(), cr.rects.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+            PFB_HIP(hipStreamSynchronize(st));  // (as before the split; cr.rects lives to the end of this step)
+            // (the plain first-axis transform runs IN PLACE on the scatter's planes: whole rows to clear)
+            if (pb.path.axis1 == FirstAxis::Transposing) g->n_clear_rects = int(cr.rects.size());
         }
+        if (prm.verbosity > 0)
+            fprintf(stderr, "[pfbhip] scatter-plane clear: %lld of %lld cells in %zu rectangles\n", (long long)cr.cells,
+                    (long long)cr.full, cr.rects.size());
     }
-    // Column runs per tile row: the runs of touched tile columns, the whole row for three or more runs (or without work).
-    // The transposing first-axis transforms load / store only these (d_colruns: RunLoad / RunStore), so they are also what
-    // has to be cleared of the scatter's planes (d_clear_rects: side-stream clear of single-pass plans, clear_planes()).
-    {
-        const int64_t ntu_t = ceil_div(info.nu, TILE), ntv_t = m.ntv;
-        std::vector<int4> runs_t(size_t(ntu_t), make_int4(0, int(info.nv), 0, 0));
-        if (!work.empty()) {
-            std::vector<int4> rects;
-            int64_t cells = 0, full = 0;
-            constexpr int SLICE = 8;  // rows per rectangle: enough workgroups to fill the chip
-            for (int64_t tu = 0; tu < ntu_t; ++tu) {
-                std::vector<std::pair<int, int>> rr;
-                for (int64_t tv = 0; tv < ntv_t;) {
-                    if (!touched_tiles[size_t(tu * ntv_t + tv)]) { ++tv; continue; }
-                    int64_t e = tv;
-                    while (e < ntv_t && touched_tiles[size_t(tu * ntv_t + e)]) ++e;
-                    rr.emplace_back(int(tv * TILE), int(std::min<int64_t>(e * TILE, info.nv)));
-                    tv = e;
-                }
-                if (rr.size() >= 3) rr.assign(1, {0, int(info.nv)});
-                const int row0 = int(tu * TILE), nrows = int(std::min<int64_t>(TILE, info.nu - row0));
-                for (auto &run : rr) {
-                    const int col0 = run.first, ncols = run.second - run.first;
-                    for (int q = 0; q < nrows; q += SLICE) rects.push_back(make_int4(row0 + q, std::min(SLICE, nrows - q), col0, ncols));
-                    cells += int64_t(nrows) * ncols;
-                }
-                if (!rr.empty()) full += int64_t(nrows) * info.nv;
-                rr.resize(2, {0, 0});
-                runs_t[size_t(tu)] = make_int4(rr[0].first, rr[0].second, rr[1].first, rr[1].second);
-            }
-            info.used_cells = cells;
-            if (!rects.empty() && cells * 10 < full * 8) {  // (fragmented or nearly full coverage: plain memsets of whole rows)
-                g->d_clear_rects.alloc(rects.size());
-                PFB_HIP(hipMemcpyAsync(g->d_clear_rects.p, rects.data(), rects.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-                PFB_HIP(hipStreamSynchronize(st));
-                // (the plain first-axis transform runs IN PLACE on the scatter's planes: whole rows to clear)
-                if (path.axis1 == FirstAxis::Transposing) g->n_clear_rects = int(rects.size());
-            }
-            if (prm.verbosity > 0)
-                fprintf(stderr, "[pfbhip] scatter-plane clear: %lld of %lld cells in %zu rectangles\n", (long long)cells,
-                        (long long)full, rects.size());
-        }
-        g->d_colruns.alloc(runs_t.size());
-        PFB_HIP(hipMemcpyAsync(g->d_colruns.p, runs_t.data(), runs_t.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipStreamSynchronize(st));
-    }
+    g->d_colruns.alloc(cr.runs_t.size());
+    PFB_HIP(hipMemcpyAsync(g->d_colruns.p, cr.runs_t.data(), cr.runs_t.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    PFB_HIP(hipStreamSynchronize(st));  // cr is a local
     // spans of consecutive occupied blocks (at most a handful for a centrally concentrated uv coverage)
-    std::vector<std::pair<int64_t, int64_t>> runs;
-    for (int64_t bk = 0; bk < nblk;) {
-        if (!occ[size_t(bk)]) { ++bk; continue; }
-        int64_t e = bk;
-        while (e < nblk && occ[size_t(e)]) ++e;
-        runs.emplace_back(bk, e);
-        bk = e;
-    }
-    if (runs.size() > 4) {  // fragmented coverage: transform everything
-        std::fill(occ.begin(), occ.end(), uint8_t(1));
-        runs.assign(1, {0, nblk});
-    }
-    g->d_occ.alloc(size_t(nblk));
-    PFB_HIP(hipMemcpyAsync(g->d_occ.p, occ.data(), occ.size(), hipMemcpyHostToDevice, st));
-
-    size_t wmax = 0;
-    bool any_rocfft = false;
-    auto make_rows = [&](int64_t len, int64_t batch, bool forward) {
-        rocfft_setup_once();
-        any_rocfft = true;
-        rocfft_plan pl = nullptr;
-        size_t lengths[1] = {size_t(len)};
-        rocfft_status st = rocfft_status_success;
-        // (rocFFT allocates inside plan creation: on failure the cache of released blocks gives way, once)
-        if (!retry_after_cache_flush([&] {
-                st = rocfft_plan_create(&pl, rocfft_placement_inplace,
-                                        forward ? rocfft_transform_type_complex_forward : rocfft_transform_type_complex_inverse,
-                                        rocfft_precision_double, 1, lengths, size_t(batch), nullptr);
-                return st == rocfft_status_success;
-            }))
-            PFB_ROCFFT(st);
-        size_t w = 0;
-        PFB_ROCFFT(rocfft_plan_get_work_buffer_size(pl, &w));
-        wmax = std::max(wmax, w);
-        return pl;
-    };
-    g->occ_rows = 0;
-    for (auto &r : runs) {
+    for (auto &r : occupied_spans(pb.occ, info.nu)) {
         pfbhip_gridder::RowSpan sp;
-        sp.row0 = r.first * TP;
-        sp.nrows = std::min<int64_t>(r.second * TP, info.nu) - sp.row0;
-        if (path.axis1 == FirstAxis::RocFFT) {
-            sp.fwd = make_rows(info.nv, sp.nrows, true);
-            sp.bwd = make_rows(info.nv, sp.nrows, false);
-        }
+        sp.row0 = r.first;
+        sp.nrows = r.second;
         g->occ_rows += sp.nrows;
         g->spans.push_back(sp);
     }
-    if (path.axis2 == SecondAxis::RocFFT) {  // second axis on rocFFT only if the hand-written FFT does not take nu
-        g->fftB_fwd = make_rows(info.nu, prm.ny, true);
-        g->fftB_bwd = make_rows(info.nu, prm.ny, false);
-    }
     info.occ_rows = int32_t(g->occ_rows);
-    {
-        if (path.axis1 == FirstAxis::Transposing) {
-            std::vector<int> rows;
-            rows.reserve(size_t(g->occ_rows));
-            for (auto &sp : g->spans)
-                for (int64_t r = 0; r < sp.nrows; ++r) rows.push_back(int(sp.row0 + r));
-            const size_t n = rows.size(), ngroups = n / 8, nfull = ngroups / 8;
-            std::vector<int> map(n);
-            for (size_t b = 0; b < n; ++b) {
-                if (b < nfull * 64) {  // super-group of 64 block ids = 8 XCDs x 8 adjacent rows
-                    const size_t sg = b / 64, r = b % 64, xcd = r % 8, k = r / 8;
-                    map[b] = rows[(sg * 8 + xcd) * 8 + k];
-                } else {
-                    map[b] = rows[b];
-                }
-            }
-            g->d_rowmap.alloc(n);
-            PFB_HIP(hipMemcpyAsync(g->d_rowmap.p, map.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
-            PFB_HIP(hipStreamSynchronize(st));
+    g->d_occ.alloc(pb.occ.size());  // (pb.occ outlives creation's last synchronisation)
+    PFB_HIP(hipMemcpyAsync(g->d_occ.p, pb.occ.data(), pb.occ.size(), hipMemcpyHostToDevice, st));
+}
+
+static rocfft_plan make_row_plan(PlanBuild &pb, int64_t len, int64_t batch, bool forward)
+{
+    rocfft_setup_once();
+    pb.any_rocfft = true;
+    rocfft_plan pl = nullptr;
+    size_t lengths[1] = {size_t(len)};
+    rocfft_status status = rocfft_status_success;
+    // (rocFFT allocates inside plan creation: on failure the cache of released blocks gives way, once)
+    if (!retry_after_cache_flush([&] {
+            status = rocfft_plan_create(&pl, rocfft_placement_inplace,
+                                        forward ? rocfft_transform_type_complex_forward : rocfft_transform_type_complex_inverse,
+                                        rocfft_precision_double, 1, lengths, size_t(batch), nullptr);
+            return status == rocfft_status_success;
+        }))
+        PFB_ROCFFT(status);
+    size_t w = 0;
+    PFB_ROCFFT(rocfft_plan_get_work_buffer_size(pl, &w));
+    pb.fft_work = std::max(pb.fft_work, w);
+    return pl;
+}
+
+// rocFFT row plans where the hand-written row FFT does not take the axis: per span of occupied rows, and for the rows of B
+static void make_rocfft_plans(pfbhip_gridder *g, PlanBuild &pb)
+{
+    const auto &info = g->info;
+    if (pb.path.axis1 == FirstAxis::RocFFT)
+        for (auto &sp : g->spans) {
+            sp.fwd = make_row_plan(pb, info.nv, sp.nrows, true);
+            sp.bwd = make_row_plan(pb, info.nv, sp.nrows, false);
         }
+    if (pb.path.axis2 == SecondAxis::RocFFT) {  // second axis on rocFFT only if the hand-written FFT does not take nu
+        g->fftB_fwd = make_row_plan(pb, info.nu, g->prm.ny, true);
+        g->fftB_bwd = make_row_plan(pb, info.nu, g->prm.ny, false);
     }
-    lap("occupancy, column runs, row map");
-    if (any_rocfft) {
+}
+
+// the row every workgroup of the transposing first-axis transforms takes (d_rowmap)
+static void upload_row_map(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    if (pb.path.axis1 != FirstAxis::Transposing) return;
+    std::vector<std::pair<int64_t, int64_t>> spans;
+    for (auto &sp : g->spans) spans.emplace_back(sp.row0, sp.nrows);
+    const std::vector<int> map = xcd_row_map(spans);
+    g->d_rowmap.alloc(map.size());
+    PFB_HIP(hipMemcpyAsync(g->d_rowmap.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    PFB_HIP(hipStreamSynchronize(g->stream));  // map is a local
+}
+
+// rocFFT's execution info, and the one clear of the scatter's planes
+static void finish_rocfft_and_clear(pfbhip_gridder *g, const PlanBuild &pb)
+{
+    hipStream_t st = g->stream;
+    if (pb.any_rocfft) {
         PFB_ROCFFT(rocfft_execution_info_create(&g->fft_info));
-        if (wmax) {
-            g->d_fftwork.alloc(wmax);
-            PFB_ROCFFT(rocfft_execution_info_set_work_buffer(g->fft_info, g->d_fftwork.p, wmax));
+        if (pb.fft_work) {
+            g->d_fftwork.alloc(pb.fft_work);
+            PFB_ROCFFT(rocfft_execution_info_set_work_buffer(g->fft_info, g->d_fftwork.p, pb.fft_work));
         }
         PFB_ROCFFT(rocfft_execution_info_set_stream(g->fft_info, st));
     }
     // rows of A outside the occupied spans are never written: clear the plane once
     PFB_HIP(hipMemsetAsync(g->d_grid.p, 0, g->d_grid.bytes(), st));
-    PFB_HIP(hipStreamSynchronize(st));
-    lap("rocFFT plans + plane clear");
+    PFB_HIP(hipStreamSynchronize(st));  // every vector of pb that was uploaded without a synchronisation of its own
+}
+
+// Runs once per handle (pfbhip_gridder_create), on a freshly constructed one.
+static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq, const uint8_t *mask)
+{
+    const auto &prm = g->prm;
+    auto &info = g->info;
+    PlanBuild pb;
+    pb.verbosity = prm.verbosity;
+    validate_params(g, uvw, freq);
+    setup_geometry_and_upload(g, pb, uvw, freq, mask);
+    w_range(g, pb);
+    pb.lap("upload + w range");
+    const KernelChoice choice = choose_kernel(prm, pb.sw, g->nvis, info.lshift, info.mshift, info.nshift, pb.wlo, pb.whi, pb.tmax,
+                                              1.0 + pb.nm1min);
+    apply_choice(g, choice, pb.wlo, pb.whi);
+    PFB_REQUIRE(info.nplanes >= 1 && info.nplanes < 100000, "unreasonable number of w-planes (%lld)",
+                (long long)info.nplanes);
+    finish_map_args(g, pb);
+    sort_by_tile(g, pb);
+    build_work_lists(g, pb);
+    sorted_coordinates(g, pb);
+    {  // step 2 of the plan's path: the scatter and gather kernels
+        const size_t nwork = pb.lists.work.size(), npass = std::max<size_t>(g->work_cnt.size(), 1);
+        const WorkShape ws{g->map.key_sub, nwork, nwork / npass, pb.lists.coarse_items / npass,
+                           g->plane_stride * size_t(g->kp_max) * sizeof(double2)};
+        pb.path = choose_kernels(pb.sw, prm, info, g->kp_max, ws);
+    }
+    upload_colour_slices(g, pb);
+    build_records(g, pb);
+    pb.lap("records");
+    upload_kernel_tables(g, pb);
+    build_correction_image(g, pb);
+    pb.lap("kernel table + correction");
+    alloc_plane_buffers(g, pb);
+    setup_transforms(g, pb);
+    setup_occupancy(g, pb);
+    make_rocfft_plans(g, pb);
+    upload_row_map(g, pb);
+    pb.lap("occupancy, column runs, row map");
+    finish_rocfft_and_clear(g, pb);
+    pb.lap("rocFFT plans + plane clear");
     info.device_bytes = g->device_bytes();
 }
 

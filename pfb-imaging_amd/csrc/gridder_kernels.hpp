@@ -14,15 +14,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "plan_layout.hpp"  // CHUNK, WorkItem
 #include "vismap.hpp"
 
 namespace pfbhip {
-
-constexpr int CHUNK = 4096;        // sorted visibilities per work item
-
-struct WorkItem {
-    uint32_t tile, begin, end, pad;
-};
 
 constexpr int MAX_POLY_PLANES = 24;
 

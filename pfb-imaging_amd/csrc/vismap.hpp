@@ -17,9 +17,9 @@
 
 #include <cstdint>
 
-namespace pfbhip {
+#include "plan_layout.hpp"  // TILE
 
-constexpr int TILE = 32;  // uv tile edge in grid cells
+namespace pfbhip {
 
 struct MapArgs {
     const double *uvw;  // (nrow,3)
