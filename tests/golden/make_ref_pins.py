@@ -24,6 +24,9 @@ What is pinned (reference file:line -> what the oracle / product has to reproduc
   opt/primal_dual.py:66-163              primal_dual (legacy) -> opt.py (host loop)
   utils/weighting.py:471-505             reduce_counts        -> (semantic check of the band/time grouping used by the tests)
 
+Pinned elsewhere, by make_clean_pins.py (clean_pins.npz): deconv/hogbom.py:9-63 and deconv/clark.py:11-143, hogbom and
+clark + subminor loaded whole under stand-ins -> tests/_clean_ref.py (CPU) and csrc/clean.hip (GPU).
+
 NOT pinned by this script: the decorated numba kernels.  make_numba_pins.py runs those as plain Python under a stand-in
 numba and pins _compute_counts, counts_to_weights (cell index, Hermitian fold, bounds, Briggs scaling), the DWT (index
 formulas, packed layout, padding between levels, both layouts) and dual_update_numba_fast (the strict threshold).

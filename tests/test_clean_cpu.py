@@ -157,3 +157,183 @@ def test_clean_info_layout_matches_header(tmp_path):
     out = [int(v) for v in subprocess.check_output([str(exe)]).decode().split()]
     C = _lib.CleanInfo
     assert out == [ct.sizeof(C)] + [getattr(C, f).offset for f in fields]
+
+
+# ---- the reference-run pins (tests/golden/clean_pins.npz, made by tests/golden/make_clean_pins.py) --------------------------
+from tests import _clean_cases as cc  # noqa: E402
+
+PINS = np.load(os.path.join(ROOT, "tests", "golden", "clean_pins.npz"))
+
+
+def _pin_model(name, c, key="val"):
+    return cc.dense(PINS[f"{name}_idx"], PINS[f"{name}_{key}"], c["dirty"].shape)
+
+
+def _yardstick(c, clark=ref.clark):
+    """(model, status, k, nminor)"""
+    if c["kind"] == "hogbom":
+        model, _, k, status = ref.hogbom(c["dirty"], c["psf"], **c["kw"])
+        return model, status, k, k
+    model, _, k, status, nminor = clark(c["dirty"], c["psf"], cc.psfhat(c["psf"]), c["wsums"], c["mask"], **c["kw"])
+    return model, status, k, nminor
+
+
+def test_pin_file_lists_every_case_and_holds_numbers_only():
+    assert tuple(PINS["cases"]) == cc.ALL_CASES
+    assert all(PINS[k].dtype.kind in "ifU" for k in PINS.files)
+    assert all(":" in c or "=" in c for c in PINS["cites"])
+
+
+@pytest.mark.parametrize("name", cc.E_CASES + cc.CLARK_T_CASES)
+def test_yardstick_reproduces_reference_pin(name):
+    """Class E and, over numpy.fft as the pin was made, class T: the reference's model bit for bit, its k and its status."""
+    c = cc.case(name)
+    model, status, k, nminor = _yardstick(c)
+    assert (k, status) == (int(PINS[f"{name}_k"]), int(PINS[f"{name}_status"]))
+    assert np.array_equal(model, _pin_model(name, c))
+    if c["kind"] == "clark" and c["kw"]["maxit"] == 1:  # every class E Clark case is cut short by submaxit
+        assert nminor == c["kw"]["submaxit"]
+
+
+def test_yardstick_in_float64_is_within_ten_times_the_float32_pin_disagreement():
+    """H6: the reference's float32 run against the yardstick in float64 on the same numbers (what the device computes)."""
+    c = cc.case("H6")
+    pin = _pin_model("H6", c)
+    assert PINS["H6_val"].dtype == np.float32
+    model, status, k, _ = _yardstick(dict(c, dirty=c["dirty"].astype(np.float64), psf=c["psf"].astype(np.float64)))
+    assert (k, status) == (int(PINS["H6_k"]), int(PINS["H6_status"])) and np.array_equal(model != 0, pin != 0)
+    err, bound = cc.rel_max(model.astype(np.float32), pin), cc.f_bound(PINS["H6_disagreement"])
+    assert err <= bound < 1e-6, (err, bound)
+
+
+def test_class_t_pins_are_conditioned():
+    for name in cc.CLARK_T_CASES:
+        c = cc.case(name)
+        dis = float(PINS[f"{name}_disagreement"])
+        assert dis == cc.rel_max(_pin_model(name, c, "sp_val"), _pin_model(name, c)) and dis < 1e-14
+        assert cc.t_bound(dis) == max(10 * dis, 64 * 2.0 ** -52)
+
+
+def _last_peak(search):
+    flat = search.reshape(-1)
+    pq = flat.size - 1 - int(np.argmax(flat[::-1]))
+    return pq, np.sqrt(flat[pq])
+
+
+def _clark_variant(**sw):
+    """tests/_clean_ref.py's clark with one convention switched to a plausible wrong one"""
+    peak = _last_peak if sw.get("last_max") else ref.peak
+
+    def subminor(a, psf, pidx, qidx, model, wsums, gamma, th, maxit, mask):
+        nband, nxp, nyp = psf.shape
+        nxo2, nyo2 = nxp // 2, nyp // 2
+        idx = np.arange(pidx.size)
+        weight = mask[pidx, qidx] if sw.get("sub_mask") else 1.0
+        pq, amax = peak(ref.search_image(a) * weight)
+        p, q = pidx[pq], qidx[pq]
+        k = 0
+        while amax > th and k < maxit:
+            sign = 1 if sw.get("unreflected") else -1
+            pp, qq = nxo2 + sign * (pidx - p), nyo2 + sign * (qidx - q)
+            if sw.get("wrap"):
+                pp, qq = pp % nxp, qq % nyp
+            inb = (pp >= 0) & (pp < nxp) & (qq >= 0) & (qq < nyp)
+            after = idx[inb] >= pq if sw.get("strict_before") else idx[inb] > pq
+            for b in range(nband):
+                xb = a[b, pq]
+                g = gamma * xb
+                model[b, p, q] += g / wsums[b]
+                g2 = g if sw.get("copy_xhat") else gamma * (xb - (g * psf[b, nxo2, nyo2]) / wsums[b])
+                a[b, inb] = a[b, inb] - (np.where(after, g2, g) * psf[b, pp[inb], qq[inb]]) / wsums[b]
+            pq, amax = peak(ref.search_image(a) * weight)
+            p, q = pidx[pq], qidx[pq]
+            k += 1
+        return k
+
+    def clark(dirty, psf, psfhat, wsums, mask, threshold, gamma, pf, maxit, subpf, submaxit):
+        major_mask = np.ones_like(mask) if sw.get("no_major_mask") else mask
+        model, residual = np.zeros_like(dirty), dirty.copy()
+        search = ref.search_image(residual) * major_mask
+        pq, rmax = peak(search)
+        tol = max(pf * rmax, threshold)
+        k = nminor = 0
+        while rmax > tol and k < maxit:
+            subth = subpf * rmax
+            pidx, qidx = np.where(search > subth * subth)
+            nminor += subminor(residual[:, pidx, qidx], psf, pidx, qidx, model, wsums, gamma, subth, submaxit, mask)
+            residual = dirty - ref.psf_convolve_cube(model, psfhat, psf.shape[2])
+            search = ref.search_image(residual) * major_mask
+            pq, rmax = peak(search)
+            k += 1
+        return model, residual, k, int(k >= maxit), nminor
+
+    return clark
+
+
+def test_variant_scaffold_with_no_switch_is_the_yardstick():
+    for name in ("C1_4096", "C4_6", "C5_half_mask", "T1"):
+        c = cc.case(name)
+        got, want = _yardstick(c, _clark_variant()), _yardstick(c)
+        assert np.array_equal(got[0], want[0]) and got[1:] == want[1:]
+
+
+# wrong variant -> the pins that must notice it
+VARIANTS = {
+    "unreflected": ("C4_6", "C4_5", "C4G_6", "C4G_5"),
+    "copy_xhat": ("C4_6", "C4G_6", "C1_4096"),
+    "last_max": ("H3", "H4_wave_1", "H4_sign_1", "H4_group_1", "H4_trip_1", "H4_trip_2", "C5_adjacent", "C5_far_lds", "C5_far_grid"),
+    "wrap": ("C1_4096", "C1_4097", "C2_193"),
+    "no_major_mask": ("C5_masked_peak", "T1"),
+    "sub_mask": ("C5_half_mask",),
+    "strict_before": ("C4_6", "C4_5", "C4G_6", "C4G_5"),
+}
+
+
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+def test_pins_catch_wrong_variant(variant, monkeypatch):
+    """Each plausible wrong reading of the reference changes the model of every pin named for it."""
+    if variant == "last_max":
+        monkeypatch.setattr(ref, "peak", _last_peak)  # Hogbom's search too
+    for name in VARIANTS[variant]:
+        c = cc.case(name)
+        model = _yardstick(c, _clark_variant(**{variant: True}))[0]
+        assert not np.array_equal(model, _pin_model(name, c)), f"{variant} passes {name}"
+
+
+def test_c3_notices_a_compaction_that_forgets_its_running_base():
+    """k_cl_compact walks its chunk of 257 pixels in two trips of 256 threads and must add the first trip's total to its base.
+    Restated here without that: the second trip's pixel lands on the chunk's first slot, and the slots left over keep what
+    fresh device memory holds (pixel (0, 0), value 0).  The sub-minor loop on that active set must not give C3's pin."""
+    c = cc.case("C3")
+    nband, nx, ny = c["dirty"].shape
+    search = ref.search_image(c["dirty"]) * c["mask"]
+    _, rmax = ref.peak(search)
+    subth = c["kw"]["subpf"] * rmax
+    flag = search.reshape(-1) > subth * subth
+    A, nchunk = int(flag.sum()), -(-nx * ny // cc.C3_CHUNK)
+    assert nchunk == 1024 and A > cc.TRIP
+
+    def compact(forget):
+        t_of = np.full(A, -1)
+        base = 0
+        for g in range(nchunk):
+            t0, t1 = g * cc.C3_CHUNK, min((g + 1) * cc.C3_CHUNK, nx * ny)
+            start = base
+            for t00 in range(t0, t1, 256):
+                ts = np.arange(t00, min(t00 + 256, t1))
+                ts = ts[flag[ts]]
+                t_of[start:start + ts.size] = ts
+                if not forget:
+                    start += ts.size
+            base += int(flag[t0:t1].sum())
+        return t_of
+
+    good = compact(False)
+    assert np.array_equal(good, np.flatnonzero(flag))
+    t_of = compact(True)
+    assert (t_of < 0).sum() > 1000
+    pidx, qidx = np.divmod(np.where(t_of < 0, 0, t_of), ny)
+    a = np.where(t_of < 0, 0.0, c["dirty"].reshape(nband, -1)[:, np.maximum(t_of, 0)])
+    model = np.zeros_like(c["dirty"])
+    ref.subminor(a, c["psf"], pidx, qidx, model, c["wsums"], c["kw"]["gamma"], subth, c["kw"]["submaxit"])
+    assert not np.array_equal(model, _pin_model("C3", c))
