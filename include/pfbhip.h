@@ -576,6 +576,58 @@ int pfbhip_comps_regrid_dev(const double *in_dev, int64_t nxi, int64_t nyi, doub
                             int64_t nxo, int64_t nyo, double cellxo, double cellyo, double x0o, double y0o, double *out_dev,
                             int *interpolated);
 
+/* ---- direct DFT of point components ---------------------------------------- */
+/*
+ * The exact measurement equation summed source by source (dft.hip; DESIGN.md "Direct DFT of point components"): the
+ * definition the gridder approximates (tests/test_hessian_approx.py:44-67 of the reference, its explicit_wdegridder), the
+ * transient injection of src/pfb_imaging/utils/stokes2im.py:491-558, and the degrid of operators/gridder.py:345-351 for a
+ * model of isolated pixels.  No image, no plan, no FFT, no epsilon.
+ *
+ * pfbhip_dft_create: a handle keeps uvw (nrow, 3) [m], freq (nchan) [Hz] and an optional mask (nrow, nchan) uint8 in HBM.
+ * pfbhip_dft_conv: the caller's conventions.  su, sv, sw multiply u, v, w (the gridder's flips: -1 when flipped); sgn is the
+ *   sign of the exponent (-1: the gridder's dirty2vis, stokes2im.py:354 freqfactor); do_wgridding = 0 sets n - 1 to 0;
+ *   divide_by_n divides every source by N = n; accumulate (predict only) adds into vis and leaves masked samples
+ *   untouched instead of writing them as 0.  The call works on the channels [chan0, chan0 + nchan) of the handle
+ *   (nchan = 0: all of them); vis, wgt and chanf then have that many columns.
+ * pfbhip_dft_predict / _dev: for every unmasked (r, c)
+ *     vis[r, c] (+)= wgt[r, c] sum_s amp[s] rowf[s, r] chanf[s, c] / N_s
+ *                    exp(sgn 2 pi i f_c / c0 (su u_r l_s + sv v_r m_s - sw w_r (n_s - 1) + off_r))
+ *   (stokes2im.py:518-558 with rowf = tprofile, chanf = fprofile * beam, off = w_diff; test_hessian_approx.py:44-67 with
+ *   all three absent).  lm (nsrc, 2), amp (nsrc), rowf (nsrc, nrow), chanf (nsrc, nchan) and off (nrow) [m] are host
+ *   arrays; rowf, chanf, off and wgt may be NULL (ones, ones, zeros, ones).  n - 1 = -(l^2 + m^2) / (1 + sqrt(1 - l^2 - m^2)),
+ *   and -sqrt(l^2 + m^2 - 1) - 1 beyond the horizon, as ducc0 has it.  vis is (nrow, nchan) complex128, wgt (nrow, nchan):
+ *   host arrays for _predict, device arrays for _predict_dev.
+ * pfbhip_dft_predict_comps / _dev: the same sum with the sources taken from a resident component model
+ *   (operators/gridder.py:318-351): l = lshift + (x_index - nx / 2) cellx, m = mshift + (y_index - ny / 2) celly,
+ *   amp_s = sum_k basis[k] coeffs[k, s] (k ascending), 0 outside the handle's region mask with use_region != 0.
+ * pfbhip_dft_image / _dev: the adjoint, out[s] = sum_{r, c} mask wgt Re(vis[r, c] exp(-sgn 2 pi i ...)) / N_s, out (nsrc) a
+ *   host array (the dirty image of the reference's explicit gridder at a list of positions).  Sums run in a fixed order:
+ *   two calls on the same input give the same bits.
+ */
+typedef struct pfbhip_dft pfbhip_dft;
+typedef struct pfbhip_dft_conv {
+    double su, sv, sw, sgn;
+    int32_t do_wgridding, divide_by_n, accumulate, reserved;
+    int64_t chan0, nchan;
+} pfbhip_dft_conv;
+int pfbhip_dft_create(int64_t nrow, int64_t nchan, const double *uvw_host, const double *freq_host, const uint8_t *mask_host,
+                      pfbhip_dft **out);
+int pfbhip_dft_destroy(pfbhip_dft *h);
+int pfbhip_dft_predict(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc, const double *lm, const double *amp,
+                       const double *rowf, const double *chanf, const double *off, const double *wgt_host, double *vis_host);
+int pfbhip_dft_predict_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc, const double *lm, const double *amp,
+                           const double *rowf, const double *chanf, const double *off, const double *wgt_dev, double *vis_dev);
+int pfbhip_dft_predict_comps(pfbhip_dft *h, const pfbhip_dft_conv *conv, pfbhip_comps *comps, const double *basis_host,
+                             int use_region, double cellx, double celly, double lshift, double mshift, const double *off,
+                             const double *wgt_host, double *vis_host);
+int pfbhip_dft_predict_comps_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, pfbhip_comps *comps, const double *basis_host,
+                                 int use_region, double cellx, double celly, double lshift, double mshift, const double *off,
+                                 const double *wgt_dev, double *vis_dev);
+int pfbhip_dft_image(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc, const double *lm, const double *off,
+                     const double *wgt_host, const double *vis_host, double *out_host);
+int pfbhip_dft_image_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc, const double *lm, const double *off,
+                         const double *wgt_dev, const double *vis_dev, double *out_host);
+
 /* ---- Gaussian-resolution convolution and restore --------------------------- */
 /*
  * Replaces convolve2gaussres (src/pfb_imaging/utils/misc.py:123-192) with its gaussian2d (:468-502, nsigma = 5) and

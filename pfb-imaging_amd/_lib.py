@@ -78,6 +78,11 @@ class CGInfo(ct.Structure):
     _fields_ = [("iters", i32), ("status", i32), ("eps", f64), ("phi", f64)]
 
 
+class DFTConv(ct.Structure):
+    _fields_ = [("su", f64), ("sv", f64), ("sw", f64), ("sgn", f64), ("do_wgridding", i32), ("divide_by_n", i32),
+                ("accumulate", i32), ("reserved", i32), ("chan0", i64), ("nchan", i64)]
+
+
 class CleanInfo(ct.Structure):
     _fields_ = [("iters", i32), ("status", i32), ("minor_iters", i64), ("idle_launches", i64), ("nsub_lds", i64),
                 ("nsub_grid", i64), ("rmax", f64), ("loop_ms", f64), ("conv_ms", f64), ("search_ms", f64),
@@ -120,6 +125,8 @@ SYMBOLS = (
     "pfbhip_comps_regrid_dev", "pfbhip_gridder_dirty2vis_dev",
     "pfbhip_gaussconv_create", "pfbhip_gaussconv_destroy", "pfbhip_gaussconv_shape", "pfbhip_gaussconv_apply",
     "pfbhip_gaussconv_apply_dev", "pfbhip_gaussconv_restore", "pfbhip_gaussconv_restore_dev", "pfbhip_gaussconv_debug_fill",
+    "pfbhip_dft_create", "pfbhip_dft_destroy", "pfbhip_dft_predict", "pfbhip_dft_predict_dev", "pfbhip_dft_predict_comps",
+    "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
 )
 
 _lib = None

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "comps_api.hpp"
 
 namespace pfbhip {
 
@@ -226,16 +227,6 @@ static void regrid_async(hipStream_t st, const double *in_dev, int64_t nxi, int6
 }  // namespace pfbhip
 
 using namespace pfbhip;
-
-struct pfbhip_comps {
-    int64_t nx = 0, ny = 0, ncomps = 0;
-    int nparam = 0;
-    bool has_region = false;
-    DevBuf<int64_t> xi, yi, pix;
-    DevBuf<double> coeffs, basis, image;  // (nparam, ncomps); the basis vector of the last render; scratch of the host render
-    DevBuf<uint8_t> region;
-    hipStream_t stream() const { return hipStreamPerThread; }
-};
 
 namespace {
 

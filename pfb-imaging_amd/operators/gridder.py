@@ -86,14 +86,19 @@ def _attr(part, name, default=0.0):
 
 def comps2vis(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_idx, fbin_cnts, region_mask, mds, modelf, tfunc,
               ffunc, epsilon=1e-7, nthreads=1, do_wgridding=True, divide_by_n=False, freq_min=-np.inf, freq_max=np.inf,
-              product="I", info=None, _dirty2vis=None):
+              product="I", info=None, _dirty2vis=None, method="grid"):
     """Model visibilities of a component model, ``_comps2vis_impl`` of the reference (gridder.py:276-367) with the render and
     the degrid on the device: per (time chunk, band) the ``nparam`` numbers of the basis vector go up, the image is formed in
     HBM from the resident coefficients and degridded there (``Gridder.dirty2vis_dev``), the visibilities come down.
 
     ``mds`` is a dict or an attribute object with ``coefficients (nparam, ncomps)``, ``location_x``, ``location_y`` and the
     attributes ``cell_rad_x, npix_x, npix_y, center_x, center_y, flip_u, flip_v, flip_w``.  ``info`` (a dict, optional)
-    receives ``device_renders``, ``host_renders`` and ``plans``.
+    receives ``device_renders``, ``host_renders`` and ``plans`` (and ``dft_predicts`` with ``method="dft"``).
+
+    ``method="dft"`` sums the measurement equation directly over the components instead (:class:`pfb_imaging_amd.dft.DFT`): no
+    image, no plan, no ``epsilon`` -- one handle per time chunk's rows, one ``predict_comps`` per band, the same bookkeeping.
+    It is the cheaper path below some number of components (DESIGN.md "Direct DFT of point components" has the measurement);
+    nothing chooses it automatically.
 
     ``modelf`` is checked once per call to be linear in its parameters (:func:`pfb_imaging_amd.comps.basis_vector`); one that
     is not is evaluated on the host as the reference does and the image uploaded -- never linearised.
@@ -111,11 +116,17 @@ def comps2vis(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_i
 
     ``_dirty2vis`` (tests) replaces the device: a callable with ``dirty2vis``'s keywords; images are then rendered on the host.
     """
+    if method not in ("grid", "dft"):
+        raise ValueError(f"method must be 'grid' or 'dft', not {method!r}")
+    if method == "dft" and _dirty2vis is not None:
+        raise ValueError("_dirty2vis stands in for the gridder: it has no meaning with method='dft'")
     resize_thread_pool(nthreads)
     coeffs = _field(mds, "coefficients")
     nstokes = len(product)
     vis = np.zeros((uvw.shape[0], freq.size, nstokes), dtype=np.result_type(coeffs.dtype, np.complex64))
     stats = dict(device_renders=0, host_renders=0, plans=0)
+    if method == "dft":
+        stats["dft_predicts"] = 0
     if info is not None:
         info.update(stats)
     in_range = (freq >= freq_min) & (freq <= freq_max)
@@ -142,6 +153,10 @@ def comps2vis(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_i
         chans = slice(int(first), int(first + count))
         if in_range[chans].any():
             bands.append(chans)
+    if method == "dft":
+        _comps2vis_dft(vis, uvw, utime, freq, rbin_idx - row0, rbin_cnts, tbin_idx - time0, tbin_cnts, bands, region_mask, coeffs,
+                       xloc, yloc, plan_kw, modelf, tfunc, ffunc, stats, info)
+        return vis
     handle = image_dev = None
     linear = None  # decided at the first render; a modelf that fails once stays on the host for the whole call
     plans = set()
@@ -195,6 +210,50 @@ def comps2vis(uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, fbin_i
         if image_dev is not None:
             image_dev.free()
     return vis
+
+
+def _comps2vis_dft(vis, uvw, utime, freq, rbin_idx, rbin_cnts, tbin_idx, tbin_cnts, bands, region_mask, coeffs, xloc, yloc, plan_kw,
+                   modelf, tfunc, ffunc, stats, info):
+    """``comps2vis(method="dft")``: fills ``vis`` in place; bin starts are already relative to this call's first bins."""
+    from ..comps import Comps, basis_vector
+    from ..dft import DFT, lm_of_pixels
+
+    geom = dict(cellx=plan_kw["pixsize_x"], celly=plan_kw["pixsize_y"], center_x=plan_kw["center_x"], center_y=plan_kw["center_y"],
+                flip_u=plan_kw["flip_u"], flip_v=plan_kw["flip_v"], flip_w=plan_kw["flip_w"])
+    conv = dict(sgn=-1.0, do_wgridding=plan_kw["do_wgridding"], divide_by_n=plan_kw["divide_by_n"])
+    nx, ny = plan_kw["npix_x"], plan_kw["npix_y"]
+    handle = Comps(nx, ny, xloc, yloc, coeffs)
+    linear = None  # as in the gridded path: decided at the first render
+    try:
+        handle.set_region(region_mask)
+        for first, count in zip(tbin_idx, tbin_cnts):
+            times = slice(int(first), int(first + count))
+            starts, counts = rbin_idx[times], rbin_cnts[times]
+            rows = slice(int(starts[0]), int(starts[-1] + counts[-1]))
+            tt = tfunc(np.mean(utime[times]))
+            with DFT(uvw[rows], freq) as d:
+                for chans in bands:
+                    ff = ffunc(np.mean(freq[chans]))
+                    bvec = None
+                    if linear is not False:
+                        bvec = basis_vector(modelf, tt, ff, coeffs.shape[0])
+                        if linear is None:
+                            linear = bvec is not None
+                    if bvec is not None:
+                        out = d.predict_comps(handle, bvec, region=True, chans=chans, **geom, **conv)
+                        stats["device_renders"] += 1
+                    else:  # a nonlinear modelf: its values on the host, as the reference forms them, then the same sum
+                        values = np.where(np.asarray(region_mask)[xloc, yloc], modelf(tt, ff, *coeffs), 0.0)
+                        lm, su, sv, sw = lm_of_pixels(xloc, yloc, nx, ny, **geom)
+                        out = d.predict(lm, values, signs=(su, sv, sw), chans=chans, **conv)
+                        stats["host_renders"] += 1
+                        handle.host_renders += 1
+                    stats["dft_predicts"] += 1
+                    vis[rows, chans, :] = out[:, :, None]
+    finally:
+        if info is not None:
+            info.update(stats)
+        handle.close()
 
 
 def psf_visibilities(uvw, freq, x0, y0, flip_u=False, flip_v=True, dtype=np.complex128):
