@@ -669,6 +669,48 @@ int pfbhip_gaussconv_restore_dev(pfbhip_gaussconv *h, const double *model_dev, c
                                  double *image_dev);
 int pfbhip_gaussconv_debug_fill(pfbhip_gaussconv *h, int byte);
 
+/* ---- clean-beam fit -------------------------------------------------------- */
+/*
+ * Replaces fitcleanbeam (src/pfb_imaging/utils/misc.py:529-613) with its objective psf_errorsq (:505-526), on the device
+ * (cleanbeam.hip; DESIGN.md "Clean-beam fit").  The swap rule and the pixel-size scaling of :615-625 stay with the caller.
+ *
+ * pfbhip_cleanbeam_fit / _fit_dev: per band of psf (nband, nx, ny; a host array for _fit, a device array for _fit_dev), with
+ *   c = 2 sqrt(2 ln 2) and psfv = psf / max(psf):
+ *     lobe   = the 4-connected component of {psfv > level} that holds (nx / 2, ny / 2)            (:559-567)
+ *     p0     = (emaj0, emin0, pa0) from the lobe's weighted second moments and its rotated extents  (:569-591)
+ *     region = {xx^2 + yy^2 < (nsigma emaj0 / c)^2} on pixel offsets from (nx / 2, ny / 2)         (:596-603)
+ *     pars   = argmin sum_region (psfv - exp(-c^2 q / 2))^2 over emaj >= 0, emin >= 0, 0 <= pa <= pi,  (:604-611)
+ *              q = [x y] R diag(1 / emaj^2, 1 / emin^2) R^T [x y]^T, R = [[-sin pa, -cos pa], [cos pa, -sin pa]]
+ *   by a projected Levenberg-Marquardt iteration from p0 (the reference stops L-BFGS-B at factr = 1e7 instead).  pars is
+ *   (nband, 3) in pixels, pixels, radians, unswapped: pars[b][0] < pars[b][1] is possible.  An all-zero band gives NaNs.
+ *   info (nband records, may be NULL) is filled before any refusal is reported.
+ * Refused with PFBHIP_ERR_INVALID: a band whose maximum is not positive although it has non-zero data; a centre pixel that
+ *   is not above level (the reference then fits the background); a lobe that still touches a 256-pixel window away from
+ *   the image's edge (its FWHM would exceed PFBHIP_CB_MAX_WINDOW pixels).
+ */
+#define PFBHIP_CB_MAX_WINDOW 256
+#define PFBHIP_CB_MAX_ITER 200
+#define PFBHIP_CB_MAX_RAISE 30
+enum {
+    PFBHIP_CB_CONVERGED = 0,   /* the projected step fell below 1e-12 (1 + |p|) */
+    PFBHIP_CB_ALL_ZERO = 1,    /* NaN row */
+    PFBHIP_CB_ITER_CAP = 2,    /* PFBHIP_CB_MAX_ITER iterations: pars is the last accepted point */
+    PFBHIP_CB_RAISE_CAP = 3,   /* PFBHIP_CB_MAX_RAISE damping raises in one iteration: pars is the last accepted point */
+    PFBHIP_CB_SWEEP_CAP = 4,   /* the flood fill ran window^2 / 2 rounds (PFBHIP_ERR_RUNTIME) */
+    PFBHIP_CB_BAD_PEAK = 5,    /* refusals */
+    PFBHIP_CB_CENTRE_LOW = 6,
+    PFBHIP_CB_LOBE_TOO_WIDE = 7
+};
+typedef struct {
+    int32_t status, window, nit, nlobe; /* PFBHIP_CB_*, final window width, LM iterations, lobe pixels */
+    int64_t nfit;                       /* pixels in the fit region */
+    double f, p0[3];                    /* objective at pars; the start point */
+} pfbhip_cleanbeam_info;
+int pfbhip_cleanbeam_fit(const double *psf_host, int64_t nband, int64_t nx, int64_t ny, double level, double nsigma,
+                         double *pars /* nband*3, pixel units, unswapped */, pfbhip_cleanbeam_info *info /* nband, may be NULL */);
+int pfbhip_cleanbeam_fit_dev(const double *psf_dev, int64_t nband, int64_t nx, int64_t ny, double level, double nsigma,
+                             double *pars /* nband*3, pixel units, unswapped */, pfbhip_cleanbeam_info *info /* nband, may be NULL */);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

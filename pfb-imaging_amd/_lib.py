@@ -89,6 +89,13 @@ class CleanInfo(ct.Structure):
                 ("compact_ms", f64), ("sub_lds_ms", f64), ("sub_grid_ms", f64)]
 
 
+CB_STATUS_NAMES = ("converged", "all_zero", "iter_cap", "raise_cap", "sweep_cap", "bad_peak", "centre_low", "lobe_too_wide")
+
+
+class CleanbeamInfo(ct.Structure):
+    _fields_ = [("status", i32), ("window", i32), ("nit", i32), ("nlobe", i32), ("nfit", i64), ("f", f64), ("p0", f64 * 3)]
+
+
 # every symbol include/pfbhip.h declares (tests check the library exports all of them)
 SYMBOLS = (
     "pfbhip_last_error", "pfbhip_device_count", "pfbhip_set_device", "pfbhip_get_device", "pfbhip_device_name",
@@ -125,6 +132,7 @@ SYMBOLS = (
     "pfbhip_comps_regrid_dev", "pfbhip_gridder_dirty2vis_dev",
     "pfbhip_gaussconv_create", "pfbhip_gaussconv_destroy", "pfbhip_gaussconv_shape", "pfbhip_gaussconv_apply",
     "pfbhip_gaussconv_apply_dev", "pfbhip_gaussconv_restore", "pfbhip_gaussconv_restore_dev", "pfbhip_gaussconv_debug_fill",
+    "pfbhip_cleanbeam_fit", "pfbhip_cleanbeam_fit_dev",
     "pfbhip_dft_create", "pfbhip_dft_destroy", "pfbhip_dft_predict", "pfbhip_dft_predict_dev", "pfbhip_dft_predict_comps",
     "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
 )

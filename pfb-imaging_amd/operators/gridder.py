@@ -17,6 +17,7 @@ import numpy as np
 from .. import _lib
 from .. import fft as _fft
 from ..misc import resize_thread_pool
+from ..utils.misc import fitcleanbeam
 from ..utils.weighting import counts_to_weights, imaging_weights
 from ..wgridder import Gridder, _get_gridder, dirty2vis, vis2dirty
 
@@ -281,12 +282,12 @@ def _eval_beam(beam_image, l_in, m_in, ll, mm):
 
 
 def grid_partition(part, counts, nx, ny, nx_psf, ny_psf, cell_rad, robustness=None, nx_pad=None, ny_pad=None, l0=0.0,
-                   m0=0.0, nthreads=1, epsilon=1e-7, do_wgridding=True, double_accum=True):
+                   m0=0.0, nthreads=1, epsilon=1e-7, do_wgridding=True, double_accum=True, do_psfpars=False):
     """Image-space products of one data partition (gridder.py:760-923): ``DIRTY``, ``PSF``,
     ``PSFHAT``, ``BEAM``, ``WSUM`` and the imaging ``WEIGHT``.  One :class:`Gridder` handle per
     output grid serves all correlations (the tile sort is weight-independent).  ``PSFPARSN``
-    (clean-beam fit, utils/misc.fitcleanbeam) is host post-processing outside this path and is
-    not returned."""
+    (the clean-beam fit of the PSF in pixel units, utils/misc.fitcleanbeam on the device) is
+    added with ``do_psfpars=True``."""
     resize_thread_pool(nthreads)
     flip_u, flip_v, flip_w, x0, y0 = wgridder_conventions(l0, m0)
     uvw = _field(part, "UVW")
@@ -336,7 +337,10 @@ def grid_partition(part, counts, nx, ny, nx_psf, ny_psf, cell_rad, robustness=No
         psfhat = _fft.r2c(psf, axes=(1, 2), nthreads=nthreads, forward=True, inorm=0, centred=True)
     else:
         psfhat = _fft.r2c(ifftshift(psf, axes=(1, 2)), axes=(1, 2), nthreads=nthreads, forward=True, inorm=0)
-    return {"DIRTY": dirty, "PSF": psf, "PSFHAT": psfhat, "BEAM": beam, "WSUM": wsum, "WEIGHT": wgt}
+    out = {"DIRTY": dirty, "PSF": psf, "PSFHAT": psfhat, "BEAM": beam, "WSUM": wsum, "WEIGHT": wgt}
+    if do_psfpars:
+        out["PSFPARSN"] = fitcleanbeam(psf, level=0.5, pixsize=1.0)
+    return out
 
 
 class PartitionResidual:
@@ -460,7 +464,8 @@ def compute_residual_arrays(dirty, model, uvw, freq, wgt, mask, beam, cell_rad, 
 def image_data_products_arrays(uvw, freq, vis, wgt, mask, nx, ny, nx_psf, ny_psf, cellx, celly, model=None, beam=None,
                                robustness=None, l0=0.0, m0=0.0, nthreads=1, epsilon=1e-7, do_wgridding=True, double_accum=True,
                                l2_reweight_dof=None, wgtp=1.0, do_dirty=True, do_psf=True, do_residual=True, do_weight=True,
-                               do_noise=False, do_beam=False, min_padding=1.7, filter_counts_level=5.0, npix_super=0, rng=None):
+                               do_noise=False, do_beam=False, min_padding=1.7, filter_counts_level=5.0, npix_super=0, rng=None,
+                               do_psfpars=False):
     """The arithmetic of ``image_data_products`` (gridder.py:375-757) on in-memory arrays of one (time, band) chunk:
     ``vis, wgt (ncorr, nrow, nchan)``, ``mask (nrow, nchan)``, ``model / beam (ncorr, nx, ny)``.
 
@@ -469,7 +474,8 @@ def image_data_products_arrays(uvw, freq, vis, wgt, mask, nx, ny, nx_psf, ny_psf
     :func:`~pfb_imaging_amd.utils.weighting.imaging_weights`) -> ``WSUM`` -> ``DIRTY`` -> ``PSF`` (+ ``PSFHAT =
     r2c(ifftshift(PSF))``) -> ``RESIDUAL`` -> ``NOISE``.  One device plan per output grid serves every correlation and
     every product on that grid (the tile sort does not depend on weights or values).  The zarr / xarray side
-    (dataset concatenation, beam interpolation, ``fitcleanbeam``, writing ``dso``) stays with the caller.
+    (dataset concatenation, beam interpolation, writing ``dso``) stays with the caller.  ``do_psfpars=True`` (needs
+    ``do_psf``) adds ``PSFPARSN = fitcleanbeam(PSF, level=0.5, pixsize=1.0)`` as gridder.py:666 stores it, fitted on the device.
 
     Returns ``(products, outputs)``: ``products`` holds the arrays the reference stores in ``dso`` (``WEIGHT, UVW, MASK,
     WSUM, DIRTY, PSF, PSFHAT, MODEL, RESIDUAL, NOISE, BEAM`` as requested) and ``outputs`` its return dict
@@ -558,6 +564,10 @@ def image_data_products_arrays(uvw, freq, vis, wgt, mask, nx, ny, nx_psf, ny_psf
             products["PSFHAT"] = _fft.r2c(psf, axes=(1, 2), nthreads=nthreads, forward=True, inorm=0, centred=True)
         else:
             products["PSFHAT"] = _fft.r2c(ifftshift(psf, axes=(1, 2)), axes=(1, 2), nthreads=nthreads, forward=True, inorm=0)
+        if do_psfpars:
+            products["PSFPARSN"] = fitcleanbeam(psf, level=0.5, pixsize=1.0)
+    elif do_psfpars:
+        raise ValueError("do_psfpars needs do_psf: PSFPARSN is fitted to the PSF")
     if do_beam:
         products["BEAM"] = np.ones((ncorr, nx, ny)) if beam is None else np.asarray(beam)
     outputs = {"residual": products["RESIDUAL"] if (do_residual and model is not None) else products.get("DIRTY"),

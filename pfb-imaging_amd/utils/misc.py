@@ -1,9 +1,11 @@
 """Image-geometry helpers of ``pfb_imaging.utils.misc`` that sit on the hot path's boundary."""
 
+import ctypes as ct
 import logging
 
 import numpy as np
 
+from .. import _lib
 from ..fft import good_size
 
 LIGHTSPEED = 299792458.0
@@ -135,3 +137,70 @@ def convolve2gaussres(image, xx, yy, gaussparf, nthreads=1, gausspari=None, pfra
     kernf = np.stack([gaussian2d(xx, yy, p, normalise=norm_kernel) for p in gaussparf.reshape(-1, 3)])
     kerni = None if gausspari is None else np.stack([gaussian2d(xx, yy, p, normalise=norm_kernel) for p in gausspari])
     return plan.apply(image, gaussparf, gausspari, kernf=kernf, kerni=kerni)
+
+
+def _finish_cleanbeam(pars, pixsize=1.0):
+    """The reference's last step on the solver's results ``pars (nband, 3)`` in pixels, pixels, radians
+    (reference utils/misc.py:615-625): a row whose first axis is the shorter one has its axes swapped and
+    ``pi / 2`` added to its angle; the axes are scaled by ``pixsize``.  NaN rows (all-zero bands) stay NaN.  Host code."""
+    pars = np.array(pars, dtype=np.float64).reshape(-1, 3)
+    swap = pars[:, 0] < pars[:, 1]
+    out = pars.copy()
+    out[swap, 0], out[swap, 1] = pars[swap, 1], pars[swap, 0]
+    out[swap, 2] = pars[swap, 2] + np.pi / 2
+    out[:, :2] *= pixsize
+    return out
+
+
+def _cleanbeam_raw(psf, level=0.5, nsigma=10.0):
+    """``(pars, info)`` of the device fit: ``pars (nband, 3)`` unswapped in pixel units and one dict per band of the
+    ``pfbhip_cleanbeam_info`` record (``status`` as a name of ``_lib.CB_STATUS_NAMES``).  ``psf`` is a host array or a
+    :class:`~pfb_imaging_amd._lib.DeviceArray`.  Refusals raise ``ValueError``; a fit that stops at a cap does not."""
+    _lib.require_gpu()
+    on_dev = isinstance(psf, _lib.DeviceArray)
+    if not on_dev:
+        psf = _lib.as_c(psf, np.float64)
+    elif psf.dtype != np.float64:
+        raise ValueError(f"the PSF cube on the device must be float64, not {psf.dtype}")
+    if len(psf.shape) != 3:
+        raise ValueError(f"psf must be (nband, nx, ny), not shape {psf.shape}")
+    nband, nx, ny = psf.shape
+    pars = np.empty((nband, 3), dtype=np.float64)
+    info = (_lib.CleanbeamInfo * nband)()
+    call = _lib.lib().pfbhip_cleanbeam_fit_dev if on_dev else _lib.lib().pfbhip_cleanbeam_fit
+    _lib.check(call(psf.ptr if on_dev else _lib.ptr(psf), _lib.i64(nband), _lib.i64(nx), _lib.i64(ny), _lib.f64(level),
+                    _lib.f64(nsigma), _lib.ptr(pars), ct.cast(info, _lib.vp)))
+    recs = [dict(status=_lib.CB_STATUS_NAMES[r.status], window=r.window, nit=r.nit, nlobe=r.nlobe, nfit=r.nfit, f=r.f,
+                 p0=np.array(r.p0[:])) for r in info]
+    return pars, recs
+
+
+def _fitcleanbeam(psf, level, pixsize, nsigma):
+    pars, recs = _cleanbeam_raw(psf, level, nsigma)
+    for b, r in enumerate(recs):
+        if r["status"] in ("iter_cap", "raise_cap"):  # (the reference prints its warning on L-BFGS-B's flag)
+            logging.getLogger(__name__).warning(f"WARNING - psf fit of band {b} stopped at a cap ({r['status']}, {r['nit']} iterations)")
+    return _finish_cleanbeam(pars, pixsize)
+
+
+def fitcleanbeam(psf, level=0.5, pixsize=1.0, nsigma=10.0):
+    """The Gaussian that approximates the main lobe of each band of ``psf (nband, nx, ny)``, fitted on the GPU
+    (reference utils/misc.py:529-627; csrc/cleanbeam.hip).
+
+    Per band: the main lobe is the 4-connected region above ``level`` of the peak around the centre pixel; its weighted second
+    moments give the start; the Gaussian is fitted to the normalised PSF within ``nsigma`` standard deviations of the start's
+    major axis.  Returns ``(nband, 3)`` rows ``(emaj * pixsize, emin * pixsize, pa)``, NaNs for an all-zero band.
+
+    Two differences from the reference: a centre pixel that is not above ``level`` raises ``ValueError`` (the reference fits
+    the background), and the result is the minimiser of the reference's objective under its bounds, not the point at which
+    L-BFGS-B's ``factr=1e7`` stops -- for nearly circular beams the angles can differ by tenths of a radian at equal
+    misfit.  A band whose maximum is not positive, or whose main lobe is wider than 256 pixels, raises ``ValueError``."""
+    return _fitcleanbeam(psf, level, pixsize, nsigma)
+
+
+def fitcleanbeam_dev(psf_dev, level=0.5, pixsize=1.0, nsigma=10.0):
+    """:func:`fitcleanbeam` of a cube that is resident on the device (a float64 ``_lib.DeviceArray`` of shape
+    ``(nband, nx, ny)``): nothing but the three numbers per band crosses to the host."""
+    if not isinstance(psf_dev, _lib.DeviceArray):
+        raise TypeError("fitcleanbeam_dev takes a _lib.DeviceArray; use fitcleanbeam for host arrays")
+    return _fitcleanbeam(psf_dev, level, pixsize, nsigma)
