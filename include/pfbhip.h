@@ -229,6 +229,10 @@ int pfbhip_c2r_2d(const double *in_host, int64_t nbatch, int64_t n0, int64_t n1 
  * benchmarks: in-place transform of (nrows, n) complex doubles, n = m 2^a (m in 1,3,5,7,9,15), 1024 <= n <= 16384, or 20480 / 24576 / 32768.
  * ms_out (may be NULL) receives the device time per transform when reps > 1. */
 int pfbhip_debug_rowfft(double *data_host, int64_t n, int64_t nrows, int inverse, int reps, double *ms_out);
+/* The same transform, once, on a chosen family of the per-length kernel shapes: family 0 is the one above (both components in
+ * LDS where they fit), family 1 the one the fused second-axis kernels of the gridder are built on (one component at a time,
+ * padded exchanges, one workgroup per CU).  Any other family, or an unsupported n, is an error.  ms_out (may be NULL): device time. */
+int pfbhip_debug_rowfft_shape(double *data_host, int64_t n, int64_t nrows, int inverse, int family, double *ms_out);
 
 /* ---- PSF-convolution operator family -------------------------------- */
 /*

@@ -109,7 +109,7 @@ SYMBOLS = (
     "pfbhip_gridder_vis2dirty_sp", "pfbhip_gridder_dirty2vis_sp", "pfbhip_gridder_set_weights_sp", "pfbhip_gridder_hessian_sp",
     "pfbhip_gridder_degrid_dev", "pfbhip_gridder_grid_dev", "pfbhip_gridder_profile", "pfbhip_gridder_profile_get",
     "pfbhip_gridder_cg", "pfbhip_gridder_cg_dev",
-    "pfbhip_r2c_2d", "pfbhip_r2c_2d_centred", "pfbhip_c2r_2d", "pfbhip_debug_rowfft",
+    "pfbhip_r2c_2d", "pfbhip_r2c_2d_centred", "pfbhip_c2r_2d", "pfbhip_debug_rowfft", "pfbhip_debug_rowfft_shape",
     "pfbhip_psi_create", "pfbhip_psi_destroy", "pfbhip_psi_shape", "pfbhip_psi_dot", "pfbhip_psi_hdot",
     "pfbhip_psi_dot_dev", "pfbhip_psi_hdot_dev", "pfbhip_dual_update", "pfbhip_l21_vtilde_sum_dev",
     "pfbhip_l21_scale_dev", "pfbhip_prox_21m", "pfbhip_positivity", "pfbhip_positivity_dev", "pfbhip_primal_dual",

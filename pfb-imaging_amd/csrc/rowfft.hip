@@ -149,6 +149,31 @@ void rowfft_plain(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inver
     PFB_HIP(hipGetLastError());
 }
 
+// The plain kernel on the shape family of the fused second-axis kernels, RfShape<L, K, false> (one component at a time in LDS,
+// XPAD, one workgroup per CU; the doubled lengths over that S1): tests reach its exchanges at a chosen length without a plan.
+static void rowfft_plain_nodual(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inverse, hipStream_t stream)
+{
+    const size_t pitch = size_t(pl.N);
+    switch (pl.N) {
+#define RF_X(L, K)                                                                         \
+    case (L << K):                                                                         \
+        if (inverse) launch_plain<RfShape<L, K, false>, true>(pl, data_dev, nrows, pitch, stream); \
+        else launch_plain<RfShape<L, K, false>, false>(pl, data_dev, nrows, pitch, stream);        \
+        break;
+        RF_FOR_SHAPES(RF_X)
+#undef RF_X
+#define RF_X(L, K)                                                                                        \
+    case 2 * (L << K):                                                                                    \
+        if (inverse) launch_plain<RfShape2<RfShape<L, K, false>>, true>(pl, data_dev, nrows, pitch, stream);     \
+        else launch_plain<RfShape2<RfShape<L, K, false>>, false>(pl, data_dev, nrows, pitch, stream);            \
+        break;
+        RF_FOR_SHAPES2(RF_X)
+#undef RF_X
+        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", pl.N);
+    }
+    PFB_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------------------
 // first-axis passes with the transpose folded in (no separate k_a2b / k_b2a pass over the plane)
 // ---------------------------------------------------------------------------------------
@@ -1363,6 +1388,36 @@ int pfbhip_debug_rowfft(double *data_host, int64_t n, int64_t nrows, int inverse
             if (ms_out) *ms_out = ms / reps;
         }
         rowfft_plain(pl, d.p, int(nrows), inverse != 0, nullptr);
+        PFB_HIP(hipDeviceSynchronize());
+        PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    });
+}
+
+// The same transform on a chosen shape family: 0 = RfShape<L, K> (what pfbhip_debug_rowfft runs), 1 = RfShape<L, K, false>, the
+// family of the fused second-axis kernels.  One transform; its device time (ms) through *ms_out if not NULL.
+int pfbhip_debug_rowfft_shape(double *data_host, int64_t n, int64_t nrows, int inverse, int family, double *ms_out)
+{
+    return guarded([&] {
+        PFB_REQUIRE(data_host && nrows >= 1 && nrows < (int64_t(1) << 31), "bad arguments");
+        PFB_REQUIRE(family == 0 || family == 1, "shape family %d: 0 (RfShape<L, K>) or 1 (RfShape<L, K, false>)", family);
+        RowFFT plan;
+        PFB_REQUIRE(plan.init(n), "row length %lld is not supported by the hand-written FFT", (long long)n);
+        const size_t tot = size_t(n) * size_t(nrows);
+        DevBuf<double2> d(tot);
+        PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
+        hipEvent_t a, b;
+        PFB_HIP(hipEventCreate(&a));
+        PFB_HIP(hipEventCreate(&b));
+        PFB_HIP(hipEventRecord(a, nullptr));
+        if (family == 0) rowfft_plain(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
+        else rowfft_plain_nodual(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
+        PFB_HIP(hipEventRecord(b, nullptr));
+        PFB_HIP(hipEventSynchronize(b));
+        float ms = 0;
+        PFB_HIP(hipEventElapsedTime(&ms, a, b));
+        if (ms_out) *ms_out = ms;
         PFB_HIP(hipDeviceSynchronize());
         PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
         (void)hipEventDestroy(a);
