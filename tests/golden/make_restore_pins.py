@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Reference-RUN fixtures of the Gaussian-resolution convolution and the restore step: ``restore_pins.npz``.
+"""Reference-RUN fixtures of the Gaussian-resolution convolution and the restore step: ``restore_pins.npz`` (cases A-D) and
+``restore_edge_pins.npz`` (the edge cases E-L of tests/_restore_ref.py; of each only the numpy-FFT output, the scalar
+disagreement with the scipy-FFT run and min / max ``|thishat|``; K is composed per band as D is).
 
 Like make_ref_pins.py (whose ``take()`` this script imports), this reads the reference's files AT GENERATION TIME, takes the
 undecorated top-level functions ``gaussian2d``, ``get_padding_info`` and ``convolve2gaussres`` out of the parsed module and
@@ -61,10 +63,9 @@ def standins(fft):
     return r2c, c2r
 
 
-def compute():
-    """every array of the fixture, by name"""
+def reference():
+    """the namespace of the reference's functions with their imports bound, and the cites"""
     from oracle.wgridder import good_size
-    from tests import _restore_ref as ref
 
     rel = "src/pfb_imaging/utils/misc.py"
     ns, found = take(rel, ["gaussian2d", "get_padding_info", "convolve2gaussres"])
@@ -73,6 +74,67 @@ def compute():
               "ducc0.fft.r2c / c2r bound to numpy.fft (_np) and scipy.fft (_sp) stand-ins with ducc0's axes / inorm / lastsize / out",
               "ducc0.fft.good_size bound to oracle.wgridder.good_size"]
     ns.update(good_size=good_size, ifftshift=np.fft.ifftshift, fftshift=np.fft.fftshift)
+    return ns, cites
+
+
+def compute_edge():
+    """every array of ``restore_edge_pins.npz``: per run of ``_restore_ref.EDGE_RUNS`` and for the restore K the numpy-FFT
+    output, its disagreement with the scipy-FFT run (a scalar) and, of a ratio run, min / max of ``|thishat|`` per band"""
+    from tests import _restore_ref as ref
+
+    ns, cites = reference()
+    out = {}
+
+    def both(image, xx, yy, gaussparf, gausspari, pfrac, norm):
+        res = []
+        for fft in (np.fft, scipy.fft):
+            ns["r2c"], ns["c2r"] = standins(fft)
+            res.append(ns["convolve2gaussres"](image.copy(), xx, yy, gaussparf, gausspari=gausspari, pfrac=pfrac, norm_kernel=norm))
+        return res
+
+    for tag, (name, norm) in ref.EDGE_RUNS.items():
+        c = ref.case(name)
+        out[f"{tag}_np"], sp = both(c["image"], c["xx"], c["yy"], c["gaussparf"], c["gausspari"], c["pfrac"], norm)
+        out[f"{tag}_disagreement"] = ref.rel_max(sp, out[f"{tag}_np"])
+        mine = ref.convolve(c["image"], c["xx"], c["yy"], c["gaussparf"], c["gausspari"], c["pfrac"], norm)
+        line = f"{tag}: numpy vs scipy stand-ins {out[f'{tag}_disagreement']:.3e}; tests/_restore_ref.py vs numpy run " \
+               f"{ref.rel_max(mine, out[f'{tag}_np']):.3e}"
+        if c["gausspari"] is not None:
+            hat = np.abs(ref.thishat(c, norm))
+            out[f"{tag}_min_over_max_thishat"] = hat.min(axis=(1, 2)) / hat.max(axis=(1, 2))
+            assert out[f"{tag}_min_over_max_thishat"].min() >= 1e-6, (tag, out[f"{tag}_min_over_max_thishat"])
+            line += f"; min / max |thishat| {out[f'{tag}_min_over_max_thishat'].min():.1e}"
+        print(line)
+
+    # K, composed per band as restore_image is called (see D below)
+    k = ref.case("K")
+    xx, yy = ref.offsets(*k["model"].shape[1:])
+    img = [np.empty_like(k["model"]), np.empty_like(k["model"])]
+    hats = []
+    for b in range(k["model"].shape[0]):
+        residual = k["residual"][b:b + 1] / k["wsum"][b:b + 1, None, None]
+        mconv = both(k["model"][b:b + 1], xx, yy, k["gaussparf"][b], None, 0.2, False)
+        if np.allclose(k["gaussparf"][b], k["gausspari"][b]):
+            rconv = [residual, residual]
+        else:
+            rconv = both(residual, xx, yy, k["gaussparf"][b], k["gausspari"][b:b + 1], 0.2, False)
+            hat = np.abs(ref.thishat(dict(image=residual, xx=xx, yy=yy, gausspari=k["gausspari"][b:b + 1], pfrac=0.2)))
+            hats.append(hat.min() / hat.max())
+        for i in range(2):
+            img[i][b] = (mconv[i] + rconv[i])[0]
+    out["K_np"], out["K_disagreement"], out["K_min_over_max_thishat"] = img[0], ref.rel_max(img[1], img[0]), np.array(hats)
+    assert min(hats) >= 1e-6, hats
+    print(f"K: numpy vs scipy stand-ins {out['K_disagreement']:.3e}; tests/_restore_ref.py vs numpy run "
+          f"{ref.rel_max(ref.restore(**k), img[0]):.3e}; min / max |thishat| {min(hats):.1e}")
+    out["cites"] = np.array(cites)
+    return out
+
+
+def compute():
+    """every array of ``restore_pins.npz``, by name"""
+    from tests import _restore_ref as ref
+
+    ns, cites = reference()
     out = {}
 
     # ---- padding and kernel ----------------------------------------------------------------------------------------
@@ -140,13 +202,25 @@ def compute():
     return out
 
 
+def same(path, out):
+    """whether the file at ``path`` holds exactly ``out`` (a fixture that would not change is not written again: the
+    archive's time stamps would change its bytes)"""
+    if not os.path.exists(path):
+        return False
+    old = np.load(path)
+    return sorted(old.files) == sorted(out) and all(np.array_equal(old[k], np.asarray(out[k])) for k in old.files)
+
+
 def main():
-    out = compute()
-    path = os.path.join(HERE, "restore_pins.npz")
-    np.savez_compressed(path, **out)
-    print("\n".join(out["cites"]))
-    print("restore_pins.npz", os.path.getsize(path))
-    assert os.path.getsize(path) < 500_000
+    for name, out in (("restore_pins.npz", compute()), ("restore_edge_pins.npz", compute_edge())):
+        path = os.path.join(HERE, name)
+        if same(path, out):
+            print(name, "unchanged")
+        else:
+            np.savez_compressed(path, **out)
+        print("\n".join(out["cites"]))
+        print(name, os.path.getsize(path))
+        assert os.path.getsize(path) < 500_000
 
 
 if __name__ == "__main__":
