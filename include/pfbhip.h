@@ -715,6 +715,33 @@ int pfbhip_cleanbeam_fit(const double *psf_host, int64_t nband, int64_t nx, int6
 int pfbhip_cleanbeam_fit_dev(const double *psf_dev, int64_t nband, int64_t nx, int64_t ny, double level, double nsigma,
                              double *pars /* nband*3, pixel units, unswapped */, pfbhip_cleanbeam_info *info /* nband, may be NULL */);
 
+/* ---- primary beams ----------------------------------------------------------- */
+/*
+ * Replaces the two scipy call sites of the primary beam (beam.hip).
+ *
+ * pfbhip_beam_regrid replaces eval_beam (src/pfb_imaging/utils/beam.py:75-89, called at operators/gridder.py:454 and :848):
+ *   RegularGridInterpolator((l_in, m_in), beam[c], method="linear", bounds_error=False, fill_value=1.0) for every
+ *   correlation of beam (ncorr, nl, nm) in one launch.  l_in (nl) and m_in (nm) are strictly ascending nodes, uniform or
+ *   not.  general == 0: l_out (nx), m_out (ny) span the output grid; general != 0: l_out, m_out are (nx, ny) coordinate
+ *   arrays.  out is (ncorr, nx, ny).  Index i with node[i] <= x < node[i + 1] clipped to [0, n - 2], weight
+ *   t = (x - node[i]) / (node[i + 1] - node[i]); a point with either coordinate outside [node[0], node[n - 1]] is exactly
+ *   1.0 (the last node is inside); a correlation whose beam is identically 1.0 gives exact ones (:85-86, decided by a
+ *   device reduction).
+ * pfbhip_beam_rotate_mean replaces the rotation loop of src/pfb_imaging/utils/stokes2vis_msv4.py:405-409:
+ *   out[c] = mean over angles of ndimage.rotate(beam0[c], angle, reshape=False, mode="nearest") (cubic splines), beam0 and
+ *   out (ncorr, n0, n1), angles in degrees.  Edge pad by 12, B-spline prefilter with scipy's reflect initialisation, then
+ *   one pass over the output that evaluates the 4x4 B-spline at every angle.
+ * All arrays are host arrays.  device_ms, when not NULL, receives the time of the kernels alone (device events; the
+ *   copies are outside).
+ * Refused with PFBHIP_ERR_INVALID: NULL arrays, fewer than two nodes on an axis, nodes that are not finite or not strictly
+ *   ascending, non-positive sizes, no angle or an angle that is not finite.
+ */
+int pfbhip_beam_regrid(const double *beam_host, int32_t ncorr, int64_t nl, int64_t nm, const double *l_in, const double *m_in,
+                       const double *l_out, const double *m_out, int general, int64_t nx, int64_t ny, double *out_host,
+                       double *device_ms /* may be NULL */);
+int pfbhip_beam_rotate_mean(const double *beam0_host, int32_t ncorr, int64_t n0, int64_t n1, const double *angles_deg,
+                            int32_t nangles, double *out_host, double *device_ms /* may be NULL */);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

@@ -135,6 +135,7 @@ SYMBOLS = (
     "pfbhip_cleanbeam_fit", "pfbhip_cleanbeam_fit_dev",
     "pfbhip_dft_create", "pfbhip_dft_destroy", "pfbhip_dft_predict", "pfbhip_dft_predict_dev", "pfbhip_dft_predict_comps",
     "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
+    "pfbhip_beam_regrid", "pfbhip_beam_rotate_mean",
 )
 
 _lib = None

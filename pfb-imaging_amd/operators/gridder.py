@@ -17,6 +17,7 @@ import numpy as np
 from .. import _lib
 from .. import fft as _fft
 from ..misc import resize_thread_pool
+from ..utils.beam import eval_beam
 from ..utils.misc import fitcleanbeam
 from ..utils.weighting import counts_to_weights, imaging_weights
 from ..wgridder import Gridder, _get_gridder, dirty2vis, vis2dirty
@@ -272,7 +273,7 @@ def psf_visibilities(uvw, freq, x0, y0, flip_u=False, flip_v=True, dtype=np.comp
 
 
 def _eval_beam(beam_image, l_in, m_in, ll, mm):
-    """/root/reference/src/pfb_imaging/utils/beam.py:75-89 (host-side, not on the hot path)."""
+    """/root/reference/src/pfb_imaging/utils/beam.py:75-89 on the host: grid_partition takes it only when no device is present."""
     if (beam_image == 1.0).all():
         return np.ones_like(ll)
     from scipy.interpolate import RegularGridInterpolator
@@ -307,6 +308,8 @@ def grid_partition(part, counts, nx, ny, nx_psf, ny_psf, cell_rad, robustness=No
     beam_in = _field(part, "BEAM")
     if beam_in.shape[-2:] == (nx, ny):
         beam = np.array(beam_in, dtype=float)
+    elif _lib.device_count() > 0:  # every correlation in one device call (utils/beam.py, csrc/beam.hip)
+        beam = eval_beam(np.asarray(beam_in)[:ncorr], _field(part, "l_beam"), _field(part, "m_beam"), np.rad2deg(x), np.rad2deg(y))
     else:
         xx, yy = np.meshgrid(np.rad2deg(x), np.rad2deg(y), indexing="ij")
         l_beam, m_beam = _field(part, "l_beam"), _field(part, "m_beam")
