@@ -742,6 +742,50 @@ int pfbhip_beam_regrid(const double *beam_host, int32_t ncorr, int64_t nl, int64
 int pfbhip_beam_rotate_mean(const double *beam0_host, int32_t ncorr, int64_t n0, int64_t n1, const double *angles_deg,
                             int32_t nangles, double *out_host, double *device_ms /* may be NULL */);
 
+/* ---- Stokes visibilities: weight_data --------------------------------------- */
+/*
+ * Replaces weight_data (src/pfb_imaging/utils/weighting.py:274-468, called at utils/stokes2vis.py:196-209,
+ * utils/stokes2vis_msv4.py:294 and utils/stokes2im.py:447-460) on the device (stokes.hip).
+ *
+ * pfbhip_stokes_spec is what stokes_expr_funcs (src/pfb_imaging/utils/stokes.py:89-155) selects: nc correlations (2 or 4),
+ *   a diagonal (full_jones == 0) or full 2x2 Jones term, linear or circular feeds, and ns products as ascending indices
+ *   into IQUV.  corr_first != 0 writes vis / wgt as (ns, nrow, nchan) (the transpose of utils/stokes2im.py:561-562)
+ *   instead of (nrow, nchan, ns).
+ * pfbhip_weight_data: for every sample of a row that a time bin covers (rows tbin_idx[t] - min(tbin_idx) ... +
+ *   tbin_counts[t], weighting.py:380-387) with no correlation flagged (:391, :442), p = ant1[row], q = ant2[row]:
+ *     vis[k] = sum_c Tinv[k][c] vec(Jp^-1 V Jq^-H)[c],   wgt[k] = sum_c w_c |((Jp (x) conj(Jq)) T)[c][k]|^2
+ *   with T of utils/stokes.py:33 / :35 and two-correlation data widened as weighting.py:257-266 does; every other sample
+ *   is 0.  data (nrow, nchan, nc) complex, weight (nrow, nchan, nc), flag (nrow, nchan, nc) bytes, jones
+ *   (ntime, nant, nchan, 2) or (ntime, nant, nchan, 2, 2) complex128 (direction 0 of the reference's array), tbin_idx and
+ *   tbin_counts (nbin), ant1 and ant2 (nrow).  mask (nrow, nchan) uint8, when not NULL, receives ~flag.any(-1)
+ *   (utils/stokes2im.py:463-464, utils/stokes2vis.py:285-286).  Arithmetic is f64; the _sp entry takes complex64 / float32
+ *   data and weights and returns complex64 / float32, widened and narrowed on the device (jones stays complex128).
+ * pfbhip_weight_data_dev: the same with vis, wgt and mask device arrays that stay in HBM; the inputs are host arrays.
+ * device_ms, when not NULL, receives the time of a second, warm launch of the kernel (device events; copies outside).
+ * Refused with PFBHIP_ERR_INVALID before anything reaches the device: a spec the reference refuses (full Jones with two
+ *   correlations, a product two correlations do not give), a time bin outside [0, nrow], more bins than ntime, an antenna
+ *   of a covered row outside [0, nant), NULL arrays.
+ * pfbhip_debug_copy16: bench hook, the mean time of a 16-byte-per-lane device copy of nbytes.
+ */
+typedef struct pfbhip_stokes_spec {
+    int32_t nc, full_jones, circular, ns;
+    int32_t product[4];
+    int32_t corr_first, reserved;
+} pfbhip_stokes_spec;
+int pfbhip_weight_data(const pfbhip_stokes_spec *spec, int64_t nrow, int64_t nchan, int64_t nant, int64_t ntime, int64_t nbin,
+                       const double *data_host, const double *weight_host, const uint8_t *flag_host, const double *jones_host,
+                       const int64_t *tbin_idx, const int64_t *tbin_counts, const int32_t *ant1, const int32_t *ant2,
+                       double *vis_host, double *wgt_host, uint8_t *mask_host /* may be NULL */, double *device_ms /* may be NULL */);
+int pfbhip_weight_data_sp(const pfbhip_stokes_spec *spec, int64_t nrow, int64_t nchan, int64_t nant, int64_t ntime, int64_t nbin,
+                          const float *data_host, const float *weight_host, const uint8_t *flag_host, const double *jones_host,
+                          const int64_t *tbin_idx, const int64_t *tbin_counts, const int32_t *ant1, const int32_t *ant2,
+                          float *vis_host, float *wgt_host, uint8_t *mask_host /* may be NULL */, double *device_ms /* may be NULL */);
+int pfbhip_weight_data_dev(const pfbhip_stokes_spec *spec, int64_t nrow, int64_t nchan, int64_t nant, int64_t ntime, int64_t nbin,
+                           const double *data_host, const double *weight_host, const uint8_t *flag_host, const double *jones_host,
+                           const int64_t *tbin_idx, const int64_t *tbin_counts, const int32_t *ant1, const int32_t *ant2,
+                           double *vis_dev, double *wgt_dev, uint8_t *mask_dev /* may be NULL */, double *device_ms /* may be NULL */);
+int pfbhip_debug_copy16(int64_t nbytes, int32_t reps, double *ms);
+
 /* ---- band reduce over xGMI (RCCL) ------------------------------------ */
 /*
  * Replaces the driver-side band sums of the reference

@@ -96,6 +96,11 @@ class CleanbeamInfo(ct.Structure):
     _fields_ = [("status", i32), ("window", i32), ("nit", i32), ("nlobe", i32), ("nfit", i64), ("f", f64), ("p0", f64 * 3)]
 
 
+class StokesSpec(ct.Structure):
+    _fields_ = [("nc", i32), ("full_jones", i32), ("circular", i32), ("ns", i32), ("product", i32 * 4), ("corr_first", i32),
+                ("reserved", i32)]
+
+
 # every symbol include/pfbhip.h declares (tests check the library exports all of them)
 SYMBOLS = (
     "pfbhip_last_error", "pfbhip_device_count", "pfbhip_set_device", "pfbhip_get_device", "pfbhip_device_name",
@@ -136,6 +141,7 @@ SYMBOLS = (
     "pfbhip_dft_create", "pfbhip_dft_destroy", "pfbhip_dft_predict", "pfbhip_dft_predict_dev", "pfbhip_dft_predict_comps",
     "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
     "pfbhip_beam_regrid", "pfbhip_beam_rotate_mean",
+    "pfbhip_weight_data", "pfbhip_weight_data_sp", "pfbhip_weight_data_dev", "pfbhip_debug_copy16",
 )
 
 _lib = None

@@ -3,12 +3,16 @@
 Mirrors /root/reference/src/pfb_imaging/utils/weighting.py: ``_compute_counts`` (:81-140) and
 ``counts_to_weights`` (:143-208).  The integer uv-cell index is bit-exact against the CPU
 oracle; the scatter-add uses hardware f64 atomics, so counts agree to summation order.
+
+``weight_data`` (:274-468) forms the Stokes visibilities and weights the rest consumes (csrc/stokes.hip).
 """
+
+import ctypes as ct
 
 import numpy as np
 
 from .. import _lib
-from .._lib import as_c, check, f64, i64, lib, ptr
+from .._lib import as_c, check, f64, i32, i64, lib, ptr
 
 
 def uvcell_index(uvw, freq, mask, nx, ny, cell_size_x, cell_size_y, usign=1.0, vsign=-1.0):
@@ -104,3 +108,120 @@ def imaging_weights(uvw, freq, mask, weight, nx_pad, ny_pad, cell_size_x, cell_s
     if w is not weight:
         weight[...] = w
     return (weight, counts) if return_counts else weight
+
+
+def as_contiguous_readonly_view(a):
+    """A C-contiguous view of ``a`` that cannot be written through; a copy only where ``a`` is not contiguous
+    (weighting.py:508-520: how the reference's callers hand their arrays to ``weight_data``)."""
+    v = np.ascontiguousarray(a).view()
+    v.flags.writeable = False
+    return v
+
+
+def _antennas(ant, nrow, name):
+    ant = np.asarray(ant)
+    if ant.shape != (nrow,):
+        raise ValueError(f"{name} {ant.shape} != {(nrow,)}")
+    if ant.dtype.kind not in "iu":
+        raise TypeError(f"{name} must be an integer array, not {ant.dtype}")
+    if ant.dtype != np.int32:
+        # (the library checks the range against nant; this keeps a wide index from wrapping into it)
+        if ant.size and (int(ant.min()) < -(2**31) or int(ant.max()) >= 2**31):
+            raise ValueError(f"{name} holds indices that are no antenna numbers")
+    return as_c(ant, np.int32)
+
+
+def _weight_data_args(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode, corr_first):
+    """Everything ``weight_data`` and ``weight_data_dev`` check and convert before the library is called."""
+    from .stokes import STOKES, stokes_products
+
+    data, jones = np.asarray(data), np.asarray(jones)
+    chosen = stokes_products(product, pol, nc, wgt_mode, jones.ndim)
+    ncorr = int(nc)
+    if data.ndim != 3 or data.shape[2] != ncorr:
+        raise ValueError(f"data {data.shape} must be (nrow, nchan, {ncorr})")
+    if data.dtype not in (np.complex64, np.complex128):
+        raise TypeError(f"data must be complex64 or complex128, not {data.dtype}")
+    single = data.dtype == np.complex64
+    nrow, nchan, _ = data.shape
+    weight, flag = np.asarray(weight), np.asarray(flag)
+    if weight.shape != data.shape or flag.shape != data.shape:
+        raise ValueError(f"weight {weight.shape} and flag {flag.shape} must have the shape of data {data.shape}")
+    full = jones.ndim == 6
+    if jones.shape[2] != nchan or jones.shape[3] < 1 or jones.shape[4:] != ((2, 2) if full else (2,)):
+        raise ValueError(f"jones {jones.shape} must be (ntime, nant, {nchan}, ndir, {'2, 2' if full else '2'})")
+    ntime, nant = jones.shape[:2]
+    if nant < 1:
+        raise ValueError("jones has no antennas")
+    tbin_idx, tbin_counts = as_c(tbin_idx, np.int64), as_c(tbin_counts, np.int64)
+    if tbin_idx.ndim != 1 or tbin_idx.shape != tbin_counts.shape:
+        raise ValueError(f"tbin_idx {tbin_idx.shape} and tbin_counts {tbin_counts.shape} must be equal-length vectors")
+    if not chosen:
+        raise ValueError(f"product {product!r} selects no Stokes parameter")
+    # The library refuses bad indices itself (pfbhip_weight_data); the same checks here come before the device entry
+    # allocates its outputs.
+    if tbin_idx.size > ntime:
+        raise ValueError(f"jones has {ntime} time slots for {tbin_idx.size} time bins")
+    start = tbin_idx - tbin_idx.min() if tbin_idx.size else tbin_idx
+    bad = np.flatnonzero((tbin_counts < 0) | (start + tbin_counts > nrow))
+    if bad.size:
+        t = int(bad[0])
+        raise ValueError(f"time bin {t} covers rows [{start[t]}, {start[t] + tbin_counts[t]}) of {nrow}")
+    edges = np.zeros(nrow + 1, dtype=np.int64)
+    np.add.at(edges, start, 1)
+    np.add.at(edges, start + tbin_counts, -1)
+    covered = np.cumsum(edges)[:nrow] > 0
+    for name, ant in (("ant1", ant1), ("ant2", ant2)):
+        a = np.asarray(ant)
+        if a.shape == (nrow,) and a.dtype.kind in "iu" and ((a[covered] < 0) | (a[covered] >= nant)).any():
+            raise ValueError(f"{name} holds antennas outside [0, {nant})")
+    spec = _lib.StokesSpec(ncorr, int(full), int(pol == "circular"), len(chosen), (i32 * 4)(*[STOKES.index(s) for s in chosen]),
+                           int(bool(corr_first)), 0)
+    real = np.float32 if single else np.float64
+    arrays = (as_c(data, data.dtype), as_c(weight, real), as_c(flag != 0 if flag.dtype != np.bool_ else flag, np.uint8),
+              as_c(jones[:, :, :, 0], np.complex128), tbin_idx, tbin_counts, _antennas(ant1, nrow, "ant1"), _antennas(ant2, nrow, "ant2"))
+    sizes = (i64(nrow), i64(nchan), i64(nant), i64(ntime), i64(tbin_idx.size))
+    return spec, sizes, arrays, (nrow, nchan, len(chosen)), single
+
+
+def weight_data(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode, info=None):
+    """Stokes visibilities and weights from raw correlations with the Jones correction applied (weighting.py:274-468), on the
+    device (``pfbhip_weight_data``, csrc/stokes.hip).
+
+    ``data, weight, flag`` are ``(nrow, nchan, nc)``; ``jones`` is ``(ntime, nant, nchan, ndir, 2)`` (diagonal) or
+    ``(..., 2, 2)``, of which direction 0 is used; rows ``tbin_idx[t] - tbin_idx.min() ... + tbin_counts[t]`` belong to
+    Jones time ``t``.  Returns ``(vis, wgt)`` of shape ``(nrow, nchan, ns)`` with the products in the order I, Q, U, V; ``vis``
+    has the dtype of ``data`` and ``wgt`` its real dtype.  Samples with any correlation flagged and rows in no bin are zero.
+    Inputs may be read-only and need not be contiguous.  ``info`` (a dict) receives ``device_ms``, the kernel's time."""
+    spec, sizes, arrays, shape, single = _weight_data_args(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol,
+                                                          product, nc, wgt_mode, False)
+    vis = _lib.result_empty(shape, np.complex64 if single else np.complex128)
+    wgt = _lib.result_empty(shape, np.float32 if single else np.float64)
+    ms = f64(0.0)
+    f = lib().pfbhip_weight_data_sp if single else lib().pfbhip_weight_data
+    check(f(ct.byref(spec), *sizes, *(ptr(a) for a in arrays), ptr(vis), ptr(wgt), None, ct.byref(ms) if info is not None else None))
+    if info is not None:
+        info["device_ms"] = ms.value
+    return vis, wgt
+
+
+def weight_data_dev(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode, corr_first=True,
+                    with_mask=True, info=None):
+    """:func:`weight_data` with the results left on the device: ``(vis, wgt, mask)`` as ``DeviceArray``\\ s, complex128 and
+    float64 of shape ``(ns, nrow, nchan)`` with ``corr_first`` (the layout ``grid_partition`` takes), else
+    ``(nrow, nchan, ns)``; ``mask`` is ``~flag.any(-1)`` as uint8 ``(nrow, nchan)``, or None without ``with_mask``.
+    complex64 data is widened on the host first."""
+    data = np.asarray(data)
+    if data.dtype == np.complex64:
+        data = data.astype(np.complex128)
+    spec, sizes, arrays, (nrow, nchan, ns), _ = _weight_data_args(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol,
+                                                                  product, nc, wgt_mode, corr_first)
+    shape = (ns, nrow, nchan) if corr_first else (nrow, nchan, ns)
+    vis, wgt = _lib.DeviceArray(shape, np.complex128), _lib.DeviceArray(shape, np.float64)
+    mask = _lib.DeviceArray((nrow, nchan), np.uint8) if with_mask else None
+    ms = f64(0.0)
+    check(lib().pfbhip_weight_data_dev(ct.byref(spec), *sizes, *(ptr(a) for a in arrays), vis.ptr, wgt.ptr,
+                                       mask.ptr if with_mask else None, ct.byref(ms) if info is not None else None))
+    if info is not None:
+        info["device_ms"] = ms.value
+    return vis, wgt, mask
