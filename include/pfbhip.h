@@ -15,7 +15,9 @@
  * Threading: a handle is single-caller (like the reference's operators, which
  * share scratch: src/pfb_imaging/operators/hessian.py:481-485); different
  * handles may be used from different host threads.  Each handle owns a HIP
- * stream; calls are synchronous with respect to the host unless stated.
+ * stream; calls are synchronous with respect to the host unless stated.  That
+ * holds on failure too: a call does not return, whatever its status, while the
+ * device still reads or writes memory the caller passed.
  */
 #ifndef PFBHIP_H
 #define PFBHIP_H

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 
 namespace pfbhip {
@@ -285,33 +286,6 @@ static double2 cos_sin_deg(double deg)
     return make_double2(std::cos(rad), std::sin(rad));
 }
 
-struct EventTimer {  // elapsed device time between start() and stop() on one stream, when the caller asked for it
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool on;
-    explicit EventTimer(bool enable) : on(enable)
-    {
-        if (!on) return;
-        PFB_HIP(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) {
-            (void)hipEventDestroy(e0);
-            throw std::runtime_error("hipEventCreate failed");
-        }
-    }
-    ~EventTimer()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    void start(hipStream_t st) { if (on) PFB_HIP(hipEventRecord(e0, st)); }
-    void stop(hipStream_t st) { if (on) PFB_HIP(hipEventRecord(e1, st)); }
-    double ms()  // after the stream has been synchronised
-    {
-        float t = 0.f;
-        if (on) PFB_HIP(hipEventElapsedTime(&t, e0, e1));
-        return double(t);
-    }
-};
-
 static void require_ascending(const double *node, int64_t n, const char *name)
 {
     for (int64_t i = 0; i < n; ++i) PFB_REQUIRE(std::isfinite(node[i]), "%s[%lld] is not finite", name, (long long)i);
@@ -345,7 +319,7 @@ int pfbhip_beam_regrid(const double *beam_host, int32_t ncorr, int64_t nl, int64
         DevBuf<int32_t> ix, jy, notones{size_t(ncorr)};
         if (!general) tx.alloc(size_t(nx)), ty.alloc(size_t(ny)), ix.alloc(size_t(nx)), jy.alloc(size_t(ny));
         EventTimer timer(device_ms != nullptr);
-        try {
+        synced(st, [&] {
             PFB_HIP(hipMemcpyAsync(beam.p, beam_host, beam.bytes(), hipMemcpyHostToDevice, st));
             PFB_HIP(hipMemcpyAsync(dl.p, l_in, dl.bytes(), hipMemcpyHostToDevice, st));
             PFB_HIP(hipMemcpyAsync(dm.p, m_in, dm.bytes(), hipMemcpyHostToDevice, st));
@@ -375,11 +349,7 @@ int pfbhip_beam_regrid(const double *beam_host, int32_t ncorr, int64_t nl, int64
             PFB_HIP(hipGetLastError());
             timer.stop(st);
             PFB_HIP(hipMemcpyAsync(out_host, out.p, out.bytes(), hipMemcpyDeviceToHost, st));
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            throw;
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        });
         if (device_ms) *device_ms = timer.ms();
     });
 }
@@ -402,7 +372,7 @@ int pfbhip_beam_rotate_mean(const double *beam0_host, int32_t ncorr, int64_t n0,
         DevBuf<double> in{nin}, half{npad}, coef{npad}, out{nin};
         DevBuf<double2> cs{size_t(nangles)};
         EventTimer timer(device_ms != nullptr);
-        try {
+        synced(st, [&] {
             PFB_HIP(hipMemcpyAsync(in.p, beam0_host, in.bytes(), hipMemcpyHostToDevice, st));
             PFB_HIP(hipMemcpyAsync(cs.p, table.data(), cs.bytes(), hipMemcpyHostToDevice, st));
             timer.start(st);
@@ -416,11 +386,7 @@ int pfbhip_beam_rotate_mean(const double *beam0_host, int32_t ncorr, int64_t n0,
             PFB_HIP(hipGetLastError());
             timer.stop(st);
             PFB_HIP(hipMemcpyAsync(out_host, out.p, out.bytes(), hipMemcpyDeviceToHost, st));
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            throw;
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        });
         if (device_ms) *device_ms = timer.ms();
     });
 }

@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "pipeline_api.hpp"
 
@@ -456,13 +457,10 @@ struct pfbhip_clean {
     std::vector<double> psf_peak;
     CleanHostState *hs = nullptr;  // pinned read-back
     hipEvent_t ev_sync = nullptr;
-    hipEvent_t ev[6] = {};
     ~pfbhip_clean()
     {
         if (hs) (void)hipHostFree(hs);
         if (ev_sync) (void)hipEventDestroy(ev_sync);
-        for (auto e : ev)
-            if (e) (void)hipEventDestroy(e);
         if (pc) (void)pfbhip_psfconv_destroy(pc);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -526,12 +524,7 @@ int64_t run_batched(pfbhip_clean *c, int64_t budget, bool sub, F &&step)
     return launched;
 }
 
-double elapsed(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    PFB_HIP(hipEventElapsedTime(&ms, a, b));
-    return double(ms);
-}
+enum ClarkStage { T_CONV, T_SEARCH, T_COMPACT, T_LDS, T_GRID, T_COUNT };  // stage times of pfbhip_clean_info
 
 }  // namespace
 
@@ -589,11 +582,11 @@ int pfbhip_clean_create(int64_t nband, int64_t nx, int64_t ny, int64_t nx_psf, i
             c->qidx.alloc(size_t(nx) * size_t(ny));
             c->cnt.alloc(CL_MAXBLK);
         }
-        PFB_HIP(hipMemcpyAsync(c->psf.p, psf_host, size_t(nband) * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        PFB_HIP(hipHostMalloc((void **)&c->hs, sizeof(CleanHostState), hipHostMallocDefault));
-        PFB_HIP(hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming));
-        for (auto &e : c->ev) PFB_HIP(hipEventCreate(&e));
-        PFB_HIP(hipStreamSynchronize(c->stream));
+        synced(c->stream, [&] {
+            PFB_HIP(hipMemcpyAsync(c->psf.p, psf_host, size_t(nband) * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            PFB_HIP(hipHostMalloc((void **)&c->hs, sizeof(CleanHostState), hipHostMallocDefault));
+            PFB_HIP(hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming));
+        });
         *out = c.release();
     });
 }
@@ -613,23 +606,26 @@ int pfbhip_clean_hogbom(pfbhip_clean *c, const double *dirty_host, double thresh
             PFB_REQUIRE(c->psf_peak[size_t(b)] > 0.0, "the PSF of band %lld has no positive peak", (long long)b);
         const size_t cube = size_t(c->nband) * size_t(c->npix());
         hipStream_t s = c->stream;
-        PFB_HIP(hipMemcpyAsync(c->wsum.p, c->psf_peak.data(), size_t(c->nband) * sizeof(double), hipMemcpyHostToDevice, s));
-        PFB_HIP(hipMemcpyAsync(c->resid.p, dirty_host, cube * sizeof(double), hipMemcpyHostToDevice, s));
-        PFB_HIP(hipMemsetAsync(c->model.p, 0, cube * sizeof(double), s));
-        c->reset_state();
-        const CleanParams cp{threshold, gamma, pf, 0.0, maxit, 0};
-        PFB_HIP(hipStreamSynchronize(s));
-        const auto t0 = std::chrono::steady_clock::now();
-        c->image_search(false, false, false);
-        c->finish(cp, FIN_HOGBOM, true);
-        const int64_t launched = run_batched(c, maxit, false, [&] {
-            c->image_search(true, false, false);
-            c->finish(cp, FIN_HOGBOM, false);
+        int64_t launched = 0;
+        double ms = 0.0;
+        synced(s, [&] {
+            PFB_HIP(hipMemcpyAsync(c->wsum.p, c->psf_peak.data(), size_t(c->nband) * sizeof(double), hipMemcpyHostToDevice, s));
+            PFB_HIP(hipMemcpyAsync(c->resid.p, dirty_host, cube * sizeof(double), hipMemcpyHostToDevice, s));
+            PFB_HIP(hipMemsetAsync(c->model.p, 0, cube * sizeof(double), s));
+            c->reset_state();
+            const CleanParams cp{threshold, gamma, pf, 0.0, maxit, 0};
+            PFB_HIP(hipStreamSynchronize(s));
+            const auto t0 = std::chrono::steady_clock::now();
+            c->image_search(false, false, false);
+            c->finish(cp, FIN_HOGBOM, true);
+            launched = run_batched(c, maxit, false, [&] {
+                c->image_search(true, false, false);
+                c->finish(cp, FIN_HOGBOM, false);
+            });
+            ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            PFB_HIP(hipMemcpyAsync(model_host, c->model.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
+            if (residual_host) PFB_HIP(hipMemcpyAsync(residual_host, c->resid.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
         });
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        PFB_HIP(hipMemcpyAsync(model_host, c->model.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (residual_host) PFB_HIP(hipMemcpyAsync(residual_host, c->resid.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
-        PFB_HIP(hipStreamSynchronize(s));
         if (info) {
             *info = pfbhip_clean_info{};
             info->iters = int32_t(c->hs->k);
@@ -661,103 +657,98 @@ int pfbhip_clean_clark(pfbhip_clean *c, const double *dirty_host, const double *
         const int64_t npix = c->npix();
         const size_t cube = size_t(c->nband) * size_t(npix);
         hipStream_t s = c->stream;
-        PFB_HIP(hipMemcpyAsync(c->wsum.p, wsums, size_t(c->nband) * sizeof(double), hipMemcpyHostToDevice, s));
-        PFB_HIP(hipMemcpyAsync(c->dirty.p, dirty_host, cube * sizeof(double), hipMemcpyHostToDevice, s));
-        PFB_HIP(hipMemcpyAsync(c->mask.p, mask_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, s));
-        PFB_HIP(hipMemcpyAsync(c->resid.p, c->dirty.p, cube * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PFB_HIP(hipMemsetAsync(c->model.p, 0, cube * sizeof(double), s));
-        c->reset_state();
-        const CleanParams cp{threshold, gamma, pf, subpf, maxit, submaxit};
-        const int g = c->grid(npix);
-        const int64_t chunk = ceil_div(npix, g);
-        const int64_t lds_max = CL_LDS_BYTES / (8 * c->nband);
-        allow_dynamic_lds(reinterpret_cast<const void *>(&k_cl_sub_lds), int(CL_LDS_BYTES));
-        double t_conv = 0, t_search = 0, t_compact = 0, t_lds = 0, t_grid = 0;
-        int64_t nsub_lds = 0, nsub_grid = 0, idle = 0;
-        hipEvent_t *e = c->ev;
-        PFB_HIP(hipStreamSynchronize(s));
-        const auto t0 = std::chrono::steady_clock::now();
-        bool first = true;
-        for (;;) {
-            // residual = dirty - conv(model) (skipped before the first sub-minor loop), masked search, stop test, active set
-            PFB_HIP(hipEventRecord(e[0], s));
-            if (!first) {
-                PFB_HIP(hipMemcpyAsync(c->resid.p, c->dirty.p, cube * sizeof(double), hipMemcpyDeviceToDevice, s));
-                for (int64_t b = 0; b < c->nband; ++b)
-                    psfconv_apply_async(c->pc, c->model.p + size_t(b) * size_t(npix), b, -1, 0, 0.0, -1.0, 0.0, 1,
-                                        c->resid.p + size_t(b) * size_t(npix));
-            }
-            PFB_HIP(hipEventRecord(e[1], s));
-            c->image_search(false, true, true);
-            c->finish(cp, FIN_MAJOR, first);
-            PFB_HIP(hipEventRecord(e[2], s));
-            hipLaunchKernelGGL(k_cl_count, dim3(g), dim3(CL_THREADS), 0, s, c->st.p, c->srch.p, npix, chunk, c->cnt.p);
-            PFB_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(CL_FIN), 0, s, c->st.p, c->cnt.p, g);
-            PFB_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_cl_compact, dim3(g), dim3(CL_THREADS), 0, s, c->st.p, c->srch.p, c->resid.p, int(c->nband),
-                               c->nx, c->ny, chunk, c->cnt.p, c->pidx.p, c->qidx.p, c->aset.p);
-            PFB_HIP(hipGetLastError());
-            PFB_HIP(hipEventRecord(e[3], s));
-            c->read_state();
-            t_conv += elapsed(e[0], e[1]);
-            t_search += elapsed(e[1], e[2]);
-            t_compact += elapsed(e[2], e[3]);
-            first = false;
-            if (c->hs->done) break;
-            // sub-minor loop over the active set
-            const int64_t A = c->hs->A;
-            PFB_HIP(hipEventRecord(e[4], s));
-            if (A <= lds_max) {
-                hipLaunchKernelGGL(k_cl_sub_lds, dim3(1), dim3(CL_LDS_THREADS), size_t(c->nband * A) * sizeof(double), s, c->st.p,
-                                   cp, int(c->nband), c->aset.p, c->pidx.p, c->qidx.p, c->psf.p, c->nxp, c->nyp, c->wsum.p,
-                                   c->model.p, c->nx, c->ny, c->nminor.p);
+        double t_ms[T_COUNT] = {}, ms = 0.0;
+        int64_t t_calls[T_COUNT] = {}, idle = 0;
+        StageTimer tm(s, true);
+        synced(s, [&] {
+            PFB_HIP(hipMemcpyAsync(c->wsum.p, wsums, size_t(c->nband) * sizeof(double), hipMemcpyHostToDevice, s));
+            PFB_HIP(hipMemcpyAsync(c->dirty.p, dirty_host, cube * sizeof(double), hipMemcpyHostToDevice, s));
+            PFB_HIP(hipMemcpyAsync(c->mask.p, mask_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, s));
+            PFB_HIP(hipMemcpyAsync(c->resid.p, c->dirty.p, cube * sizeof(double), hipMemcpyDeviceToDevice, s));
+            PFB_HIP(hipMemsetAsync(c->model.p, 0, cube * sizeof(double), s));
+            c->reset_state();
+            const CleanParams cp{threshold, gamma, pf, subpf, maxit, submaxit};
+            const int g = c->grid(npix);
+            const int64_t chunk = ceil_div(npix, g);
+            const int64_t lds_max = CL_LDS_BYTES / (8 * c->nband);
+            allow_dynamic_lds(reinterpret_cast<const void *>(&k_cl_sub_lds), int(CL_LDS_BYTES));
+            PFB_HIP(hipStreamSynchronize(s));
+            const auto t0 = std::chrono::steady_clock::now();
+            bool first = true;
+            for (;;) {
+                // residual = dirty - conv(model) (skipped before the first sub-minor loop), masked search, stop test, active set
+                tm.begin(T_CONV);
+                if (!first) {
+                    PFB_HIP(hipMemcpyAsync(c->resid.p, c->dirty.p, cube * sizeof(double), hipMemcpyDeviceToDevice, s));
+                    for (int64_t b = 0; b < c->nband; ++b)
+                        psfconv_apply_async(c->pc, c->model.p + size_t(b) * size_t(npix), b, -1, 0, 0.0, -1.0, 0.0, 1,
+                                            c->resid.p + size_t(b) * size_t(npix));
+                }
+                tm.end();
+                tm.begin(T_SEARCH);
+                c->image_search(false, true, true);
+                c->finish(cp, FIN_MAJOR, first);
+                tm.end();
+                tm.begin(T_COMPACT);
+                hipLaunchKernelGGL(k_cl_count, dim3(g), dim3(CL_THREADS), 0, s, c->st.p, c->srch.p, npix, chunk, c->cnt.p);
                 PFB_HIP(hipGetLastError());
-                PFB_HIP(hipEventRecord(e[5], s));
-                PFB_HIP(hipEventSynchronize(e[5]));
-                t_lds += elapsed(e[4], e[5]);
-                ++nsub_lds;
-            } else {
-                const int ga = c->grid(A);
-                c->last_parts = ga;
-                hipLaunchKernelGGL(k_cl_active<false>, dim3(ga), dim3(CL_THREADS), 0, s, c->st.p, int(c->nband), c->aset.p,
-                                   c->pidx.p, c->qidx.p, c->psf.p, c->nxp, c->nyp, c->wsum.p, c->pv.p, c->pi.p);
+                hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(CL_FIN), 0, s, c->st.p, c->cnt.p, g);
                 PFB_HIP(hipGetLastError());
-                c->finish(cp, FIN_SUB, true);
-                const int64_t before = c->hs->nminor;
-                const int64_t launched = run_batched(c, submaxit, true, [&] {
-                    hipLaunchKernelGGL(k_cl_active<true>, dim3(ga), dim3(CL_THREADS), 0, s, c->st.p, int(c->nband), c->aset.p,
+                hipLaunchKernelGGL(k_cl_compact, dim3(g), dim3(CL_THREADS), 0, s, c->st.p, c->srch.p, c->resid.p, int(c->nband),
+                                   c->nx, c->ny, chunk, c->cnt.p, c->pidx.p, c->qidx.p, c->aset.p);
+                PFB_HIP(hipGetLastError());
+                tm.end();
+                c->read_state();
+                tm.collect(t_ms, t_calls);
+                first = false;
+                if (c->hs->done) break;
+                // sub-minor loop over the active set
+                const int64_t A = c->hs->A;
+                tm.begin(A <= lds_max ? T_LDS : T_GRID);
+                if (A <= lds_max) {
+                    hipLaunchKernelGGL(k_cl_sub_lds, dim3(1), dim3(CL_LDS_THREADS), size_t(c->nband * A) * sizeof(double), s, c->st.p,
+                                       cp, int(c->nband), c->aset.p, c->pidx.p, c->qidx.p, c->psf.p, c->nxp, c->nyp, c->wsum.p,
+                                       c->model.p, c->nx, c->ny, c->nminor.p);
+                    PFB_HIP(hipGetLastError());
+                } else {
+                    const int ga = c->grid(A);
+                    c->last_parts = ga;
+                    hipLaunchKernelGGL(k_cl_active<false>, dim3(ga), dim3(CL_THREADS), 0, s, c->st.p, int(c->nband), c->aset.p,
                                        c->pidx.p, c->qidx.p, c->psf.p, c->nxp, c->nyp, c->wsum.p, c->pv.p, c->pi.p);
                     PFB_HIP(hipGetLastError());
-                    c->finish(cp, FIN_SUB, false);
-                });
-                idle += launched - (c->hs->nminor - before);
-                PFB_HIP(hipEventRecord(e[5], s));
-                PFB_HIP(hipEventSynchronize(e[5]));
-                t_grid += elapsed(e[4], e[5]);
-                ++nsub_grid;
-                c->last_parts = g;
+                    c->finish(cp, FIN_SUB, true);
+                    const int64_t before = c->hs->nminor;
+                    const int64_t launched = run_batched(c, submaxit, true, [&] {
+                        hipLaunchKernelGGL(k_cl_active<true>, dim3(ga), dim3(CL_THREADS), 0, s, c->st.p, int(c->nband), c->aset.p,
+                                           c->pidx.p, c->qidx.p, c->psf.p, c->nxp, c->nyp, c->wsum.p, c->pv.p, c->pi.p);
+                        PFB_HIP(hipGetLastError());
+                        c->finish(cp, FIN_SUB, false);
+                    });
+                    idle += launched - (c->hs->nminor - before);
+                    c->last_parts = g;
+                }
+                tm.end();
+                tm.collect(t_ms, t_calls);
             }
-        }
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        PFB_HIP(hipMemcpyAsync(model_host, c->model.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (residual_host) PFB_HIP(hipMemcpyAsync(residual_host, c->resid.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
-        PFB_HIP(hipStreamSynchronize(s));
+            ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            PFB_HIP(hipMemcpyAsync(model_host, c->model.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
+            if (residual_host) PFB_HIP(hipMemcpyAsync(residual_host, c->resid.p, cube * sizeof(double), hipMemcpyDeviceToHost, s));
+        });
         if (info) {
             *info = pfbhip_clean_info{};
             info->iters = int32_t(c->hs->k);
             info->status = c->hs->k >= maxit ? 1 : 0;
             info->minor_iters = c->hs->nminor;
             info->idle_launches = idle;
-            info->nsub_lds = nsub_lds;
-            info->nsub_grid = nsub_grid;
+            info->nsub_lds = t_calls[T_LDS];
+            info->nsub_grid = t_calls[T_GRID];
             info->rmax = c->hs->rmax;
             info->loop_ms = ms;
-            info->conv_ms = t_conv;
-            info->search_ms = t_search;
-            info->compact_ms = t_compact;
-            info->sub_lds_ms = t_lds;
-            info->sub_grid_ms = t_grid;
+            info->conv_ms = t_ms[T_CONV];
+            info->search_ms = t_ms[T_SEARCH];
+            info->compact_ms = t_ms[T_COMPACT];
+            info->sub_lds_ms = t_ms[T_LDS];
+            info->sub_grid_ms = t_ms[T_GRID];
         }
     });
 }

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 
 namespace pfbhip {
@@ -407,31 +408,27 @@ static void cleanbeam_run(const double *psf_dev, int64_t nband, int64_t nx, int6
     DevBuf<int> d_pnz(size_t(nband) * npeak);
     DevBuf<pfbhip_cleanbeam_info> d_info(size_t(nband) + 0);
     const bool timing = std::getenv("PFBHIP_CLEANBEAM_TIMING") != nullptr;  // hipEvent times of the two kernels on stderr
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (timing)
-        for (auto &e : ev) PFB_HIP(hipEventCreate(&e));
-    if (timing) PFB_HIP(hipEventRecord(ev[0], nullptr));
-    hipLaunchKernelGGL(k_cb_peak, dim3(npeak, uint32_t(nband)), dim3(CB_THREADS), 0, nullptr, psf_dev, n, d_pmax.p, d_pnz.p);
-    PFB_HIP(hipGetLastError());
-    if (timing) PFB_HIP(hipEventRecord(ev[1], nullptr));
-    const int lds = PFBHIP_CB_MAX_WINDOW * PFBHIP_CB_MAX_WINDOW;
-    allow_dynamic_lds(reinterpret_cast<const void *>(&k_cb_fit), lds);  // 64 KiB of window on top of the static scratch
-    const CbArgs a{psf_dev, int(nx), int(ny), npeak, level, nsigma, 2.0 * std::sqrt(2.0 * std::log(2.0)),
-                   d_pmax.p, d_pnz.p, d_pars.p, d_info.p};
-    hipLaunchKernelGGL(k_cb_fit, dim3(uint32_t(nband)), dim3(CB_THREADS), lds, nullptr, a);
-    PFB_HIP(hipGetLastError());
-    if (timing) PFB_HIP(hipEventRecord(ev[2], nullptr));
+    EventTimer t_peak(timing), t_fit(timing);
     std::vector<pfbhip_cleanbeam_info> h_info(static_cast<size_t>(nband));
-    PFB_HIP(hipMemcpy(pars, d_pars.p, d_pars.bytes(), hipMemcpyDeviceToHost));
-    PFB_HIP(hipMemcpy(h_info.data(), d_info.p, d_info.bytes(), hipMemcpyDeviceToHost));
-    if (timing) {
-        float t_peak = 0.f, t_fit = 0.f;
-        PFB_HIP(hipEventElapsedTime(&t_peak, ev[0], ev[1]));
-        PFB_HIP(hipEventElapsedTime(&t_fit, ev[1], ev[2]));
-        for (auto &e : ev) (void)hipEventDestroy(e);
+    synced(nullptr, [&] {
+        t_peak.start(nullptr);
+        hipLaunchKernelGGL(k_cb_peak, dim3(npeak, uint32_t(nband)), dim3(CB_THREADS), 0, nullptr, psf_dev, n, d_pmax.p, d_pnz.p);
+        PFB_HIP(hipGetLastError());
+        t_peak.stop(nullptr);
+        t_fit.start(nullptr);
+        const int lds = PFBHIP_CB_MAX_WINDOW * PFBHIP_CB_MAX_WINDOW;
+        allow_dynamic_lds(reinterpret_cast<const void *>(&k_cb_fit), lds);  // 64 KiB of window on top of the static scratch
+        const CbArgs a{psf_dev, int(nx), int(ny), npeak, level, nsigma, 2.0 * std::sqrt(2.0 * std::log(2.0)),
+                       d_pmax.p, d_pnz.p, d_pars.p, d_info.p};
+        hipLaunchKernelGGL(k_cb_fit, dim3(uint32_t(nband)), dim3(CB_THREADS), lds, nullptr, a);
+        PFB_HIP(hipGetLastError());
+        t_fit.stop(nullptr);
+        PFB_HIP(hipMemcpy(pars, d_pars.p, d_pars.bytes(), hipMemcpyDeviceToHost));
+        PFB_HIP(hipMemcpy(h_info.data(), d_info.p, d_info.bytes(), hipMemcpyDeviceToHost));
+    });
+    if (timing)
         fprintf(stderr, "pfbhip_cleanbeam (%lld, %lld, %lld): k_cb_peak %.4f ms (%.1f GB/s), k_cb_fit %.4f ms\n", (long long)nband,
-                (long long)nx, (long long)ny, t_peak, double(nband) * double(n) * 8.0 / (double(t_peak) * 1e6), t_fit);
-    }
+                (long long)nx, (long long)ny, t_peak.ms(), double(nband) * double(n) * 8.0 / (t_peak.ms() * 1e6), t_fit.ms());
     if (info)
         for (int64_t b = 0; b < nband; ++b) info[b] = h_info[size_t(b)];
     for (int64_t b = 0; b < nband; ++b) {

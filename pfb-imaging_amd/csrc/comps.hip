@@ -15,8 +15,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "comps_api.hpp"
 
@@ -175,8 +177,6 @@ __global__ void __launch_bounds__(CP_THREADS) k_comps_regrid(const double *__res
     out[o] = v * area_ratio;
 }
 
-static dim3 cp_blocks(int64_t n) { return dim3(uint32_t(std::max<int64_t>(ceil_div(n, CP_THREADS), 1))); }
-
 // one axis of the reference's padding arithmetic (modelspec.py:281-319), in the same order of operations
 static RegridAxis regrid_axis(int64_t ni, double celli, double x0i, int64_t no, double cello, double x0o)
 {
@@ -218,7 +218,7 @@ static void regrid_async(hipStream_t st, const double *in_dev, int64_t nxi, int6
         PFB_REQUIRE(!outside(ax, nxo) && !outside(ay, nyo), "one of the requested output points is out of bounds of the padded input grid");
     }
     const double area_ratio = (cellxo * cellyo) / (cellxi * cellyi);
-    hipLaunchKernelGGL(k_comps_regrid, cp_blocks(nxo * nyo), dim3(CP_THREADS), 0, st, in_dev, ax, ay, nxo, nyo, int(interp), area_ratio,
+    hipLaunchKernelGGL(k_comps_regrid, blocks1d(nxo * nyo, CP_THREADS), dim3(CP_THREADS), 0, st, in_dev, ax, ay, nxo, nyo, int(interp), area_ratio,
                        out_dev);
     PFB_HIP(hipGetLastError());
     if (interpolated) *interpolated = interp ? 1 : 0;
@@ -238,9 +238,21 @@ void render_async(pfbhip_comps *h, const double *basis_host, int use_region, dou
     PFB_HIP(hipMemcpyAsync(h->basis.p, basis_host, size_t(h->nparam) * sizeof(double), hipMemcpyHostToDevice, st));
     PFB_HIP(hipMemsetAsync(image_dev, 0, size_t(h->nx) * size_t(h->ny) * sizeof(double), st));
     if (h->ncomps)
-        hipLaunchKernelGGL(k_comps_scatter, cp_blocks(h->ncomps), dim3(CP_THREADS), 0, st, h->pix.p, h->ncomps, h->coeffs.p, h->basis.p,
+        hipLaunchKernelGGL(k_comps_scatter, blocks1d(h->ncomps, CP_THREADS), dim3(CP_THREADS), 0, st, h->pix.p, h->ncomps, h->coeffs.p, h->basis.p,
                            h->nparam, use_region ? h->region.p : nullptr, image_dev);
     PFB_HIP(hipGetLastError());
+}
+
+// a handle with its arrays allocated (one element where there are no components) and nothing in them
+std::unique_ptr<pfbhip_comps> make_comps(int64_t nx, int64_t ny, int64_t ncomps, int32_t nparam)
+{
+    auto h = std::make_unique<pfbhip_comps>();
+    h->nx = nx, h->ny = ny, h->ncomps = ncomps, h->nparam = nparam;
+    const size_t n = size_t(std::max<int64_t>(ncomps, 1));
+    h->xi.alloc(n), h->yi.alloc(n), h->pix.alloc(n);
+    h->coeffs.alloc(n * size_t(nparam));
+    h->basis.alloc(size_t(nparam));
+    return h;
 }
 
 }  // namespace
@@ -269,26 +281,16 @@ int pfbhip_comps_create(int64_t nx, int64_t ny, int64_t ncomps, int32_t nparam, 
             PFB_REQUIRE(dup == sorted.end(), "two components share the pixel (%lld, %lld): locations must be distinct",
                         dup == sorted.end() ? 0LL : (long long)(*dup / ny), dup == sorted.end() ? 0LL : (long long)(*dup % ny));
         }
-        auto h = new pfbhip_comps;
-        try {
-            h->nx = nx, h->ny = ny, h->ncomps = ncomps, h->nparam = nparam;
-            const size_t n = size_t(std::max<int64_t>(ncomps, 1));
-            h->xi.alloc(n), h->yi.alloc(n), h->pix.alloc(n);
-            h->coeffs.alloc(n * size_t(nparam));
-            h->basis.alloc(size_t(nparam));
-            const hipStream_t st = h->stream();
-            if (ncomps) {
-                PFB_HIP(hipMemcpyAsync(h->xi.p, x_index_host, size_t(ncomps) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                PFB_HIP(hipMemcpyAsync(h->yi.p, y_index_host, size_t(ncomps) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                PFB_HIP(hipMemcpyAsync(h->pix.p, flat.data(), size_t(ncomps) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                PFB_HIP(hipMemcpyAsync(h->coeffs.p, coeffs_host, size_t(ncomps) * size_t(nparam) * sizeof(double), hipMemcpyHostToDevice, st));
-            }
-            PFB_HIP(hipStreamSynchronize(st));
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
+        auto h = make_comps(nx, ny, ncomps, nparam);
+        const hipStream_t st = h->stream();
+        synced(st, [&] {
+            const size_t n = size_t(ncomps);
+            upload(h->xi, x_index_host, n, st);
+            upload(h->yi, y_index_host, n, st);
+            upload(h->pix, flat.data(), n, st);
+            upload(h->coeffs, coeffs_host, n * size_t(nparam), st);
+        });
+        *out = h.release();
     });
 }
 
@@ -312,50 +314,36 @@ int pfbhip_comps_fit(const double *cube_host, const double *cube_dev, int64_t ns
         const int64_t npix = nx * ny, ntiles = ceil_div(npix, CP_TILE);
         PFB_REQUIRE(ntiles < (int64_t(1) << 31), "image too large");
         const hipStream_t st = hipStreamPerThread;
-        DevBuf<double> upload;
-        if (cube_host) {
-            upload.alloc(size_t(ns) * size_t(npix));
-            PFB_HIP(hipMemcpyAsync(upload.p, cube_host, upload.bytes(), hipMemcpyHostToDevice, st));
-            cube_dev = upload.p;
-        }
+        DevBuf<double> cube, A;
         DevBuf<uint8_t> mask{size_t(npix)};
         DevBuf<int32_t> counts{size_t(ntiles)};
         DevBuf<int64_t> offsets{size_t(ntiles)};
-        DevBuf<double> A{size_t(nparam) * size_t(ns)};
-        PFB_HIP(hipMemcpyAsync(A.p, A_host, A.bytes(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_comps_mask, dim3(uint32_t(ntiles)), dim3(CP_THREADS), 0, st, cube_dev, int(ns), npix, mask.p, counts.p);
-        PFB_HIP(hipGetLastError());
         std::vector<int32_t> hc(static_cast<size_t>(ntiles));
-        PFB_HIP(hipMemcpyAsync(hc.data(), counts.p, counts.bytes(), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
         std::vector<int64_t> ho(static_cast<size_t>(ntiles));
+        std::unique_ptr<pfbhip_comps> h;
         int64_t ncomps = 0;
-        for (int64_t w = 0; w < ntiles; ++w) {  // the scan, in workgroup order
-            ho[size_t(w)] = ncomps;
-            ncomps += hc[size_t(w)];
-        }
-        auto h = new pfbhip_comps;
-        try {
-            h->nx = nx, h->ny = ny, h->ncomps = ncomps, h->nparam = nparam;
-            const size_t n = size_t(std::max<int64_t>(ncomps, 1));
-            h->xi.alloc(n), h->yi.alloc(n), h->pix.alloc(n);
-            h->coeffs.alloc(n * size_t(nparam));
-            h->basis.alloc(size_t(nparam));
+        synced(st, [&] {  // (the temporaries above die after the kernels that use them)
+            if (cube_host) cube_dev = upload(cube, cube_host, size_t(ns) * size_t(npix), st);
+            upload(A, A_host, size_t(nparam) * size_t(ns), st);
+            hipLaunchKernelGGL(k_comps_mask, dim3(uint32_t(ntiles)), dim3(CP_THREADS), 0, st, cube_dev, int(ns), npix, mask.p, counts.p);
+            PFB_HIP(hipGetLastError());
+            PFB_HIP(hipMemcpyAsync(hc.data(), counts.p, counts.bytes(), hipMemcpyDeviceToHost, st));
+            PFB_HIP(hipStreamSynchronize(st));
+            for (int64_t w = 0; w < ntiles; ++w) {  // the scan, in workgroup order
+                ho[size_t(w)] = ncomps;
+                ncomps += hc[size_t(w)];
+            }
+            h = make_comps(nx, ny, ncomps, nparam);
             if (ncomps) {
                 PFB_HIP(hipMemcpyAsync(offsets.p, ho.data(), offsets.bytes(), hipMemcpyHostToDevice, st));
                 hipLaunchKernelGGL(k_comps_compact, dim3(uint32_t(ntiles)), dim3(CP_THREADS), 0, st, mask.p, npix, ny, offsets.p, ncomps,
                                    h->xi.p, h->yi.p, h->pix.p);
-                hipLaunchKernelGGL(k_comps_fit, cp_blocks(ncomps), dim3(CP_THREADS), 0, st, cube_dev, int(ns), npix, h->pix.p, ncomps, A.p,
+                hipLaunchKernelGGL(k_comps_fit, blocks1d(ncomps, CP_THREADS), dim3(CP_THREADS), 0, st, cube_dev, int(ns), npix, h->pix.p, ncomps, A.p,
                                    int(nparam), h->coeffs.p);
                 PFB_HIP(hipGetLastError());
             }
-            PFB_HIP(hipStreamSynchronize(st));  // (the temporaries above die after the kernels that use them)
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            delete h;
-            throw;
-        }
-        *out = h;
+        });
+        *out = h.release();
         *ncomps_out = ncomps;
     });
 }
@@ -377,11 +365,12 @@ int pfbhip_comps_get(pfbhip_comps *h, int64_t *x_index_host, int64_t *y_index_ho
         PFB_REQUIRE(h, "NULL handle");
         const hipStream_t st = h->stream();
         const size_t n = size_t(h->ncomps);
-        if (n && x_index_host) PFB_HIP(hipMemcpyAsync(x_index_host, h->xi.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (n && y_index_host) PFB_HIP(hipMemcpyAsync(y_index_host, h->yi.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (n && coeffs_host)
-            PFB_HIP(hipMemcpyAsync(coeffs_host, h->coeffs.p, n * size_t(h->nparam) * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            if (n && x_index_host) PFB_HIP(hipMemcpyAsync(x_index_host, h->xi.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            if (n && y_index_host) PFB_HIP(hipMemcpyAsync(y_index_host, h->yi.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            if (n && coeffs_host)
+                PFB_HIP(hipMemcpyAsync(coeffs_host, h->coeffs.p, n * size_t(h->nparam) * sizeof(double), hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
@@ -392,9 +381,7 @@ int pfbhip_comps_set_region(pfbhip_comps *h, const uint8_t *region_host)
         h->has_region = false;
         if (!region_host) return;
         const size_t npix = size_t(h->nx) * size_t(h->ny);
-        h->region.ensure(npix);
-        PFB_HIP(hipMemcpyAsync(h->region.p, region_host, npix, hipMemcpyHostToDevice, h->stream()));
-        PFB_HIP(hipStreamSynchronize(h->stream()));
+        synced(h->stream(), [&] { upload(h->region, region_host, npix, h->stream()); });
         h->has_region = true;
     });
 }
@@ -403,8 +390,7 @@ int pfbhip_comps_render_dev(pfbhip_comps *h, const double *basis_host, int use_r
 {
     return guarded([&] {
         PFB_REQUIRE(h && basis_host && image_dev, "NULL argument");
-        render_async(h, basis_host, use_region, image_dev);
-        PFB_HIP(hipStreamSynchronize(h->stream()));
+        synced(h->stream(), [&] { render_async(h, basis_host, use_region, image_dev); });
     });
 }
 
@@ -413,10 +399,11 @@ int pfbhip_comps_render(pfbhip_comps *h, const double *basis_host, int use_regio
     return guarded([&] {
         PFB_REQUIRE(h && basis_host && image_host, "NULL argument");
         const size_t npix = size_t(h->nx) * size_t(h->ny);
-        h->image.ensure(npix);
-        render_async(h, basis_host, use_region, h->image.p);
-        PFB_HIP(hipMemcpyAsync(image_host, h->image.p, npix * sizeof(double), hipMemcpyDeviceToHost, h->stream()));
-        PFB_HIP(hipStreamSynchronize(h->stream()));
+        synced(h->stream(), [&] {
+            h->image.ensure(npix);
+            render_async(h, basis_host, use_region, h->image.p);
+            PFB_HIP(hipMemcpyAsync(image_host, h->image.p, npix * sizeof(double), hipMemcpyDeviceToHost, h->stream()));
+        });
     });
 }
 
@@ -426,9 +413,10 @@ int pfbhip_comps_regrid_dev(const double *in_dev, int64_t nxi, int64_t nyi, doub
 {
     return guarded([&] {
         PFB_REQUIRE(in_dev && out_dev && in_dev != out_dev, "NULL or aliased argument");
-        regrid_async(hipStreamPerThread, in_dev, nxi, nyi, cellxi, cellyi, x0i, y0i, nxo, nyo, cellxo, cellyo, x0o, y0o, out_dev,
-                     interpolated);
-        PFB_HIP(hipStreamSynchronize(hipStreamPerThread));
+        synced(hipStreamPerThread, [&] {
+            regrid_async(hipStreamPerThread, in_dev, nxi, nyi, cellxi, cellyi, x0i, y0i, nxo, nyo, cellxo, cellyo, x0o, y0o, out_dev,
+                         interpolated);
+        });
     });
 }
 
@@ -441,15 +429,11 @@ int pfbhip_comps_regrid(const double *in_host, int64_t nxi, int64_t nyi, double 
         PFB_REQUIRE(nxi >= 1 && nyi >= 1 && nxo >= 1 && nyo >= 1, "image sizes must be positive");
         const hipStream_t st = hipStreamPerThread;
         DevBuf<double> in{size_t(nxi) * size_t(nyi)}, out{size_t(nxo) * size_t(nyo)};
-        PFB_HIP(hipMemcpyAsync(in.p, in_host, in.bytes(), hipMemcpyHostToDevice, st));
-        try {
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(in.p, in_host, in.bytes(), hipMemcpyHostToDevice, st));
             regrid_async(st, in.p, nxi, nyi, cellxi, cellyi, x0i, y0i, nxo, nyo, cellxo, cellyo, x0o, y0o, out.p, interpolated);
             PFB_HIP(hipMemcpyAsync(out_host, out.p, out.bytes(), hipMemcpyDeviceToHost, st));
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            throw;
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        });
     });
 }
 

@@ -1,5 +1,5 @@
 // devloop.hpp -- the host-side scaffold of the device-resident backward solvers (pd.hip, fb.hip): the PSF-Hessian band
-// description, the stream scope, the stage clock, the stopping measure and the resume protocol of a handle.  Host code
+// description, the stream scope, the stopping measure and the resume protocol of a handle.  Host code
 // only, apart from k_diff (a pure subtraction): kernels with a multiply-add stay in their .hip file, whose
 // floating-point contraction they were built under.
 #pragma once
@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "devcg.hpp"
 #include "pipeline_api.hpp"
@@ -22,8 +23,6 @@ namespace pfbhip {
 
 constexpr int LOOP_MAXB = 16;  // bands held in registers by the one-pass kernels of the solvers
 
-static dim3 blocks256(size_t n) { return dim3(uint32_t(ceil_div(int64_t(n), 256))); }
-
 // d = a - b
 static __global__ void __launch_bounds__(256) k_diff(const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ d,
                                                      int64_t n)
@@ -34,47 +33,6 @@ static __global__ void __launch_bounds__(256) k_diff(const double *__restrict__ 
 
 // _nb_norm_diff / _nb_any_nonzero of the reference: ||x - xp|| / max(||x||^2, 1e-12)^1/2, 1 when x is all zero
 inline double rel_change_eps(double num, double den, double nnz) { return nnz > 0.0 ? std::sqrt(num / std::max(den, 1e-12)) : 1.0; }
-
-// HIP events around the stages of a short run, on the loop's stream, read back after the loop.  `on` only for a bounded
-// number of events (the callers: maxit <= 64, benchmark-style runs); off, nothing is created or recorded.
-struct StageClock {
-    hipStream_t st;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> stage;
-    StageClock(hipStream_t st_, bool on_) : st(st_), on(on_) {}
-    StageClock(const StageClock &) = delete;
-    StageClock &operator=(const StageClock &) = delete;
-    void begin(int s)
-    {
-        if (!on) return;
-        hipEvent_t a, b;
-        PFB_HIP(hipEventCreate(&a));
-        PFB_HIP(hipEventCreate(&b));
-        PFB_HIP(hipEventRecord(a, st));
-        ev.push_back(a);
-        ev.push_back(b);
-        stage.push_back(s);
-    }
-    void end()
-    {
-        if (on) PFB_HIP(hipEventRecord(ev.back(), st));
-    }
-    // adds the bracketed times to ms / calls (after the stream was synchronised)
-    void read(double *ms, int64_t *calls) const
-    {
-        for (size_t i = 0; i < stage.size(); ++i) {
-            float e = 0.f;
-            PFB_HIP(hipEventElapsedTime(&e, ev[2 * i], ev[2 * i + 1]));
-            ms[stage[i]] += double(e);
-            calls[stage[i]] += 1;
-        }
-    }
-    ~StageClock()
-    {
-        for (auto e : ev) (void)hipEventDestroy(e);
-    }
-};
 
 // The PSF-approximate Hessian of a cube, band by band (an owned copy of the C-ABI description): H_b = scale_b * sum over
 // the band's partitions q in [off[b], off[b + 1]) of beam_q PSF_q beam_q, + eta_b.
@@ -115,7 +73,7 @@ struct PsfHessBands {
     // Enqueues out (+)= (mul / div) H_b in for band b, one apply per partition, eta with the first; the first apply
     // accumulates into out only if `accumulate_first`.  The plan is handed mul * scale_b / div and mul * eta_b / div (so
     // -1, gamma gives the -scale_b / gamma of the primal-dual gradient to the bit).  clk brackets every apply as `stage`.
-    void apply(int64_t b, const double *in, double *out, double mul, double div, bool accumulate_first, StageClock *clk = nullptr,
+    void apply(int64_t b, const double *in, double *out, double mul, double div, bool accumulate_first, StageTimer *clk = nullptr,
                int stage = 0) const
     {
         const size_t ub = size_t(b);
@@ -191,8 +149,7 @@ struct Resume {
     // w_dev <- src (n doubles, from the host or the device), synchronised
     void set_weight(double *w_dev, const double *src, size_t n, hipMemcpyKind kind, hipStream_t st)
     {
-        PFB_HIP(hipMemcpyAsync(w_dev, src, n * sizeof(double), kind, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] { PFB_HIP(hipMemcpyAsync(w_dev, src, n * sizeof(double), kind, st)); });
         has_weight = true;
     }
     void stages_to(double *ms, int64_t *calls) const

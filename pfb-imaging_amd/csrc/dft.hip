@@ -24,8 +24,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "comps_api.hpp"
 
@@ -240,15 +242,6 @@ DftGeom geometry(const pfbhip_dft *h, const pfbhip_dft_conv *cv)
     return g;
 }
 
-template <class T>
-const T *upload(DevBuf<T> &buf, const T *host, size_t n, hipStream_t st)
-{
-    if (!host) return nullptr;
-    buf.ensure(std::max<size_t>(n, 1));
-    if (n) PFB_HIP(hipMemcpyAsync(buf.p, host, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return buf.p;
-}
-
 // (l, m, nm1, amp / N) of a host list; amp == NULL: (l, m, nm1, N) as the image kernels want it.  `keep` owns the staging
 // array until the caller has synchronised.
 void sources_from_host(pfbhip_dft *h, const pfbhip_dft_conv *cv, int64_t nsrc, const double *lm, const double *amp,
@@ -344,19 +337,6 @@ void image_async(pfbhip_dft *h, const DftGeom &g, int64_t nsrc, const double *of
     PFB_HIP(hipMemcpyAsync(out_host, h->out.p, size_t(nsrc) * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
-// runs body(), then waits for the stream -- also when body() throws: the host staging arrays must outlive the copies
-template <class F>
-void synced(pfbhip_dft *h, F &&body)
-{
-    try {
-        body();
-    } catch (...) {
-        (void)hipStreamSynchronize(h->stream());
-        throw;
-    }
-    PFB_HIP(hipStreamSynchronize(h->stream()));
-}
-
 }  // namespace
 
 extern "C" {
@@ -369,10 +349,10 @@ int pfbhip_dft_create(int64_t nrow, int64_t nchan, const double *uvw_host, const
         *out = nullptr;
         PFB_REQUIRE(uvw_host && freq_host, "NULL argument");
         PFB_REQUIRE(nrow >= 1 && nchan >= 1 && nrow < (int64_t(1) << 40) && nchan < (int64_t(1) << 31), "bad sizes");
-        auto h = new pfbhip_dft;
-        try {
-            h->nrow = nrow, h->nchan = nchan;
-            const hipStream_t st = h->stream();
+        auto h = std::make_unique<pfbhip_dft>();
+        h->nrow = nrow, h->nchan = nchan;
+        const hipStream_t st = h->stream();
+        synced(st, [&] {
             h->uvw.alloc(size_t(nrow) * 3);
             h->freq.alloc(size_t(nchan));
             PFB_HIP(hipMemcpyAsync(h->uvw.p, uvw_host, h->uvw.bytes(), hipMemcpyHostToDevice, st));
@@ -382,13 +362,8 @@ int pfbhip_dft_create(int64_t nrow, int64_t nchan, const double *uvw_host, const
                 PFB_HIP(hipMemcpyAsync(h->mask.p, mask_host, h->mask.bytes(), hipMemcpyHostToDevice, st));
                 h->has_mask = true;
             }
-            PFB_HIP(hipStreamSynchronize(st));
-        } catch (...) {
-            (void)hipStreamSynchronize(h->stream());
-            delete h;
-            throw;
-        }
-        *out = h;
+        });
+        *out = h.release();
     });
 }
 
@@ -407,7 +382,7 @@ int pfbhip_dft_predict(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc,
         const DftGeom g = geometry(h, conv);
         PFB_REQUIRE(amp || nsrc == 0, "NULL argument");
         std::vector<double> keep;
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             sources_from_host(h, conv, nsrc, lm, amp, keep);
             predict_host(h, g, nsrc, rowf, chanf, off, wgt_host, vis_host);
         });
@@ -421,7 +396,7 @@ int pfbhip_dft_predict_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t n
         const DftGeom g = geometry(h, conv);
         PFB_REQUIRE(amp || nsrc == 0, "NULL argument");
         std::vector<double> keep;
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             sources_from_host(h, conv, nsrc, lm, amp, keep);
             predict_async(h, g, nsrc, rowf, chanf, off, wgt_dev, vis_dev);
         });
@@ -434,7 +409,7 @@ int pfbhip_dft_predict_comps(pfbhip_dft *h, const pfbhip_dft_conv *conv, pfbhip_
 {
     return guarded([&] {
         const DftGeom g = geometry(h, conv);
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             sources_from_comps(h, conv, comps, basis_host, use_region, cellx, celly, lshift, mshift);
             predict_host(h, g, comps->ncomps, nullptr, nullptr, off, wgt_host, vis_host);
         });
@@ -447,7 +422,7 @@ int pfbhip_dft_predict_comps_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, pfb
 {
     return guarded([&] {
         const DftGeom g = geometry(h, conv);
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             sources_from_comps(h, conv, comps, basis_host, use_region, cellx, celly, lshift, mshift);
             predict_async(h, g, comps->ncomps, nullptr, nullptr, off, wgt_dev, vis_dev);
         });
@@ -461,7 +436,7 @@ int pfbhip_dft_image(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsrc, c
         const DftGeom g = geometry(h, conv);
         PFB_REQUIRE(vis_host, "NULL argument");
         std::vector<double> keep;
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             const hipStream_t st = h->stream();
             const size_t nvis = size_t(g.nrow) * size_t(g.nsel);
             sources_from_host(h, conv, nsrc, lm, nullptr, keep);
@@ -478,7 +453,7 @@ int pfbhip_dft_image_dev(pfbhip_dft *h, const pfbhip_dft_conv *conv, int64_t nsr
     return guarded([&] {
         const DftGeom g = geometry(h, conv);
         std::vector<double> keep;
-        synced(h, [&] {
+        synced(h->stream(), [&] {
             sources_from_host(h, conv, nsrc, lm, nullptr, keep);
             image_async(h, g, nsrc, off, wgt_dev, vis_dev, out_host);
         });

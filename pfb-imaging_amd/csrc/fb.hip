@@ -313,14 +313,15 @@ int pfbhip_fb_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
         h->xp = h->xa.p;
         h->x = h->xb.p;
         const hipStream_t st = h->st;
-        PFB_HIP(hipMemcpyAsync(h->xt.p, xtilde_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipMemcpyAsync(h->xp, x0_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipMemcpyAsync(h->y.p, h->xp, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
         h->run.has_weight = weight_host != nullptr;  // (NULL: the caller sets the weight before the first run)
-        if (weight_host) PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_diff, blocks256(h->nimg), dim3(256), 0, st, h->xt.p, h->y.p, h->d.p, int64_t(h->nimg));
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(h->xt.p, xtilde_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
+            PFB_HIP(hipMemcpyAsync(h->xp, x0_host, h->nimg * sizeof(double), hipMemcpyHostToDevice, st));
+            PFB_HIP(hipMemcpyAsync(h->y.p, h->xp, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (weight_host) PFB_HIP(hipMemcpyAsync(h->w.p, weight_host, h->cube * sizeof(double), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_diff, blocks1d(int64_t(h->nimg)), dim3(256), 0, st, h->xt.p, h->y.p, h->d.p, int64_t(h->nimg));
+            PFB_HIP(hipGetLastError());
+        });
         *out = h.release();
     });
 }
@@ -362,84 +363,85 @@ int pfbhip_fb_run(pfbhip_fb *h, double lam, double tol, int maxit, double *x_hos
         const int l1 = h->reg_kind;
         const bool fast = nband <= LOOP_MAXB && npix % 2 == 0;
         const bool fused_id = !h->psi && fast;
-        StageClock clk(st, info != nullptr && maxit <= 64);
+        StageTimer clk(st, info != nullptr && maxit <= 64);
         int status = 1;
-        PFB_HIP(hipStreamSynchronize(st));
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            (void)h->run.complete(h->x, h->xp);  // xp <- x (y and d were written by the previous step kernel)
-            double beta = 0.0;
-            if (h->acceleration) {  // FISTA momentum: data-independent, advanced once per iteration
-                const double tp = h->t;
-                h->t = (1.0 + std::sqrt(1.0 + 4.0 * tp * tp)) / 2.0;
-                beta = (tp - 1.0) / h->t;
-            }
-            // 1. forward step: y <- y + (step / g) H d, d = xtilde - y
-            for (int64_t b = 0; b < nband; ++b)
-                h->bands.apply(b, h->d.p + size_t(b) * npix, h->y.p + size_t(b) * npix, h->step / h->g, 1.0, true, &clk, 0);
-            const double *xo = h->xout.p;
-            if (!fused_id) {
-                // 2. analysis (a copy of xg for the identity)
-                clk.begin(1);
-                if (h->psi) {
-                    for (int64_t b = 0; b < nband; ++b) psi_dot_async(h->psi, h->y.p + size_t(b) * npix, h->alpha.p + size_t(b) * cube);
+        synced(st, [&] {
+            PFB_HIP(hipStreamSynchronize(st));
+            const auto t0 = std::chrono::steady_clock::now();
+            for (;;) {
+                (void)h->run.complete(h->x, h->xp);  // xp <- x (y and d were written by the previous step kernel)
+                double beta = 0.0;
+                if (h->acceleration) {  // FISTA momentum: data-independent, advanced once per iteration
+                    const double tp = h->t;
+                    h->t = (1.0 + std::sqrt(1.0 + 4.0 * tp * tp)) / 2.0;
+                    beta = (tp - 1.0) / h->t;
+                }
+                // 1. forward step: y <- y + (step / g) H d, d = xtilde - y
+                for (int64_t b = 0; b < nband; ++b)
+                    h->bands.apply(b, h->d.p + size_t(b) * npix, h->y.p + size_t(b) * npix, h->step / h->g, 1.0, true, &clk, 0);
+                const double *xo = h->xout.p;
+                if (!fused_id) {
+                    // 2. analysis (a copy of xg for the identity)
+                    clk.begin(1);
+                    if (h->psi) {
+                        for (int64_t b = 0; b < nband; ++b) psi_dot_async(h->psi, h->y.p + size_t(b) * npix, h->alpha.p + size_t(b) * cube);
+                    } else {
+                        PFB_HIP(hipMemcpyAsync(h->alpha.p, h->y.p, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
+                    }
+                    clk.end();
+                    // 3. alpha <- prox(alpha) - alpha
+                    clk.begin(2);
+                    if (nband <= LOOP_MAXB && cube % 2 == 0) {
+                        dispatch_nb<ShrinkNB>(int(nband), st, h->alpha.p, int64_t(cube), tau, (const double *)h->w.p, l1);
+                    } else {
+                        if (!l1) hipLaunchKernelGGL(k_fb_bandsum, blocks1d(int64_t(cube)), dim3(256), 0, st, h->alpha.p, int(nband), int64_t(cube),
+                                                    h->scratch.p);
+                        hipLaunchKernelGGL(k_fb_shrink_gen, blocks1d(int64_t(h->ncoef)), dim3(256), 0, st, h->alpha.p, int64_t(cube),
+                                           int64_t(h->ncoef), tau, h->w.p, l1 ? nullptr : h->scratch.p);
+                    }
+                    clk.end();
+                    // 4. synthesis (the identity's alpha is the image-domain difference already)
+                    clk.begin(3);
+                    if (h->psi) {
+                        for (int64_t b = 0; b < nband; ++b) psi_hdot_async(h->psi, h->alpha.p + size_t(b) * cube, h->xout.p + size_t(b) * npix);
+                    } else {
+                        xo = h->alpha.p;
+                    }
+                    clk.end();
+                }
+                // 5. x, positivity, norms, y_next, d
+                clk.begin(4);
+                if (fused_id) {
+                    dispatch_nb<StepIdNB>(int(nband), st, int64_t(npix), h->y.p, (const double *)nullptr, (const double *)h->xp,
+                                          (const double *)h->xt.p, h->x, h->d.p, inv_nu, beta, h->positivity, tau,
+                                          (const double *)h->w.p, l1, h->partials.p);
+                } else if (fast) {
+                    dispatch_nb<StepNB>(int(nband), st, int64_t(npix), h->y.p, xo, (const double *)h->xp, (const double *)h->xt.p, h->x,
+                                        h->d.p, inv_nu, beta, h->positivity, tau, (const double *)h->w.p, l1, h->partials.p);
                 } else {
-                    PFB_HIP(hipMemcpyAsync(h->alpha.p, h->y.p, h->nimg * sizeof(double), hipMemcpyDeviceToDevice, st));
+                    if (h->positivity == 2)
+                        hipLaunchKernelGGL(k_fb_flag, blocks1d(int64_t(npix)), dim3(256), 0, st, int64_t(npix), int(nband), h->y.p, xo, inv_nu,
+                                           h->scratch.p);
+                    hipLaunchKernelGGL(k_fb_step_gen, dim3(CG_BLOCKS), dim3(CG_THREADS), 0, st, int64_t(npix), int(nband), h->y.p, xo, h->xp,
+                                       h->xt.p, h->x, h->d.p, inv_nu, beta, h->positivity, h->scratch.p, h->partials.p);
                 }
                 clk.end();
-                // 3. alpha <- prox(alpha) - alpha
-                clk.begin(2);
-                if (nband <= LOOP_MAXB && cube % 2 == 0) {
-                    dispatch_nb<ShrinkNB>(int(nband), st, h->alpha.p, int64_t(cube), tau, (const double *)h->w.p, l1);
-                } else {
-                    if (!l1) hipLaunchKernelGGL(k_fb_bandsum, blocks256(cube), dim3(256), 0, st, h->alpha.p, int(nband), int64_t(cube),
-                                                h->scratch.p);
-                    hipLaunchKernelGGL(k_fb_shrink_gen, blocks256(h->ncoef), dim3(256), 0, st, h->alpha.p, int64_t(cube),
-                                       int64_t(h->ncoef), tau, h->w.p, l1 ? nullptr : h->scratch.p);
+                PFB_HIP(hipGetLastError());
+                double s[3];  // |x - xp|^2, |x|^2, #nonzero(x)
+                fetch_partials<3>(h->partials.p, h->hpart, st, s);
+                h->run.eps = rel_change_eps(s[0], s[1], s[2]);
+                h->run.pending = true;
+                if (h->run.eps < tol) {
+                    status = 0;
+                    ++h->events;
+                    break;
                 }
-                clk.end();
-                // 4. synthesis (the identity's alpha is the image-domain difference already)
-                clk.begin(3);
-                if (h->psi) {
-                    for (int64_t b = 0; b < nband; ++b) psi_hdot_async(h->psi, h->alpha.p + size_t(b) * cube, h->xout.p + size_t(b) * npix);
-                } else {
-                    xo = h->alpha.p;
-                }
-                clk.end();
+                if (h->run.k + 1 >= maxit) break;
             }
-            // 5. x, positivity, norms, y_next, d
-            clk.begin(4);
-            if (fused_id) {
-                dispatch_nb<StepIdNB>(int(nband), st, int64_t(npix), h->y.p, (const double *)nullptr, (const double *)h->xp,
-                                      (const double *)h->xt.p, h->x, h->d.p, inv_nu, beta, h->positivity, tau,
-                                      (const double *)h->w.p, l1, h->partials.p);
-            } else if (fast) {
-                dispatch_nb<StepNB>(int(nband), st, int64_t(npix), h->y.p, xo, (const double *)h->xp, (const double *)h->xt.p, h->x,
-                                    h->d.p, inv_nu, beta, h->positivity, tau, (const double *)h->w.p, l1, h->partials.p);
-            } else {
-                if (h->positivity == 2)
-                    hipLaunchKernelGGL(k_fb_flag, blocks256(npix), dim3(256), 0, st, int64_t(npix), int(nband), h->y.p, xo, inv_nu,
-                                       h->scratch.p);
-                hipLaunchKernelGGL(k_fb_step_gen, dim3(CG_BLOCKS), dim3(CG_THREADS), 0, st, int64_t(npix), int(nband), h->y.p, xo, h->xp,
-                                   h->xt.p, h->x, h->d.p, inv_nu, beta, h->positivity, h->scratch.p, h->partials.p);
-            }
-            clk.end();
-            PFB_HIP(hipGetLastError());
-            double s[3];  // |x - xp|^2, |x|^2, #nonzero(x)
-            fetch_partials<3>(h->partials.p, h->hpart, st, s);
-            h->run.eps = rel_change_eps(s[0], s[1], s[2]);
-            h->run.pending = true;
-            if (h->run.eps < tol) {
-                status = 0;
-                ++h->events;
-                break;
-            }
-            if (h->run.k + 1 >= maxit) break;
-        }
-        h->run.loop_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        PFB_HIP(hipMemcpyAsync(x_host, h->x, h->nimg * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
-        clk.read(h->run.stage_ms, h->run.stage_calls);
+            h->run.loop_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            PFB_HIP(hipMemcpyAsync(x_host, h->x, h->nimg * sizeof(double), hipMemcpyDeviceToHost, st));
+        });
+        clk.collect(h->run.stage_ms, h->run.stage_calls);
         if (info) {
             info->iters = h->run.k;
             info->status = status;

@@ -106,7 +106,7 @@ struct pfbhip_pd {
     Resume run;
     pfbhip_pd_traffic traffic = {};
 
-    // uploads the start values (weight_host may be NULL: set before the first run); the caller synchronises
+    // uploads the start values (weight_host may be NULL: set before the first run)
     pfbhip_pd(pfbhip_psi *psi_, pfbhip_psfconv *const *pcs, int64_t nband, const int64_t *nparts, const int64_t *psf_slots,
               const int64_t *beam_slots, const double *scale, const double *eta, const double *xtilde_host, double gamma_,
               const double *x_host, const double *v_host, const double *weight_host, double sigma_, double tau_, int positivity_,
@@ -141,11 +141,13 @@ struct pfbhip_pd {
         x = xb.p;
         vp = va.p;
         v = vb.p;
-        PFB_HIP(hipMemcpyAsync(xp, x_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipMemcpyAsync(xt.p, xtilde_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
-        PFB_HIP(hipMemcpyAsync(vp, v_host, ncoef * sizeof(double), hipMemcpyHostToDevice, st));
         run.has_weight = weight_host != nullptr;
-        if (weight_host) PFB_HIP(hipMemcpyAsync(w.p, weight_host, cube * sizeof(double), hipMemcpyHostToDevice, st));
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(xp, x_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
+            PFB_HIP(hipMemcpyAsync(xt.p, xtilde_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
+            PFB_HIP(hipMemcpyAsync(vp, v_host, ncoef * sizeof(double), hipMemcpyHostToDevice, st));
+            if (weight_host) PFB_HIP(hipMemcpyAsync(w.p, weight_host, cube * sizeof(double), hipMemcpyHostToDevice, st));
+        });
     }
 };
 
@@ -154,7 +156,7 @@ namespace {
 // One iteration enqueued on h->st: v <- Psi^H xp ; dual update and extrapolation ; xout_b <- Psi vext_b + grad(xp)_b ;
 // primal step, positivity and the norm partials.  Stage clocks: Psi^H analysis, dual update, Psi synthesis, the
 // PSF-approximate Hessian applies, primal step + norms -- what bench.py's C4 roofline is computed from.
-void pd_iteration(pfbhip_pd *h, double lam, StageClock &clk)
+void pd_iteration(pfbhip_pd *h, double lam, StageTimer &clk)
 {
     const hipStream_t st = h->st;
     const int64_t nband = h->bands.nband();
@@ -177,7 +179,7 @@ void pd_iteration(pfbhip_pd *h, double lam, StageClock &clk)
         clk.begin(2);
         psi_hdot_async(h->psi, h->vext.p + size_t(b) * cube, xo);
         clk.end();
-        hipLaunchKernelGGL(k_diff, blocks256(npix), dim3(256), 0, st, h->xt.p + size_t(b) * npix, h->xp + size_t(b) * npix, h->d.p,
+        hipLaunchKernelGGL(k_diff, blocks1d(int64_t(npix)), dim3(256), 0, st, h->xt.p + size_t(b) * npix, h->xp + size_t(b) * npix, h->d.p,
                            int64_t(npix));
         h->bands.apply(b, h->d.p, xo, -1.0, h->gamma, true, &clk, 3);
     }
@@ -187,7 +189,7 @@ void pd_iteration(pfbhip_pd *h, double lam, StageClock &clk)
         hipLaunchKernelGGL(k_pd_step, dim3(CG_BLOCKS), dim3(CG_THREADS), 0, st, int64_t(npix), int(nband), h->x, h->xp, h->xout.p, h->tau,
                            h->positivity, h->partials.p);
     } else {
-        hipLaunchKernelGGL(k_pd_primal, blocks256(h->nimg), dim3(256), 0, st, h->x, h->xp, h->xout.p, h->tau, int64_t(h->nimg));
+        hipLaunchKernelGGL(k_pd_primal, blocks1d(int64_t(h->nimg)), dim3(256), 0, st, h->x, h->xp, h->xout.p, h->tau, int64_t(h->nimg));
         if (flag_spans_ranks) {
             positivity_flag_async(h->x, nband, int64_t(npix), h->d.p, st);
             PFB_HIP(hipStreamSynchronize(st));
@@ -204,7 +206,7 @@ void pd_iteration(pfbhip_pd *h, double lam, StageClock &clk)
 
 // Iterates from where the handle stands until eps < tol (returns 0) or iteration maxit - 1 ran (returns 1).  One host
 // round trip per iteration: the norm partials, summed over the ranks when there is a communicator.
-int pd_loop(pfbhip_pd *h, double lam, double tol, int maxit, StageClock &clk)
+int pd_loop(pfbhip_pd *h, double lam, double tol, int maxit, StageTimer &clk)
 {
     for (;;) {
         // complete the previous iteration: xp <- x, vp <- v (primal_dual.py:434-435)
@@ -234,12 +236,12 @@ int pd_loop(pfbhip_pd *h, double lam, double tol, int maxit, StageClock &clk)
 void pd_solve(pfbhip_pd *h, double lam, double tol, int maxit, bool clock_on, pfbhip_pd_info *info)
 {
     StreamScope scope(h->psi, h->bands, h->st);
-    StageClock clk(h->st, clock_on);
+    StageTimer clk(h->st, clock_on);
     PFB_HIP(hipStreamSynchronize(h->st));
     const auto t0 = std::chrono::steady_clock::now();
     const int status = pd_loop(h, lam, tol, maxit, clk);
     h->run.loop_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    clk.read(h->run.stage_ms, h->run.stage_calls);
+    clk.collect(h->run.stage_ms, h->run.stage_calls);
     if (info) {
         info->iters = h->run.k;  // the reference reports the loop index of the last iteration
         info->status = status;
@@ -262,10 +264,11 @@ int pfbhip_primal_dual(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nban
         PFB_REQUIRE(weight_host && maxit >= 1, "bad arguments");
         pfbhip_pd h(psi, pcs, nband, nparts, psf_slots, beam_slots, scale, eta, xtilde_host, gamma, x_host, v_host, weight_host, sigma,
                     tau, positivity, comm);
-        pd_solve(&h, lam, tol, maxit, info != nullptr && maxit <= 64, info);
-        PFB_HIP(hipMemcpyAsync(x_host, h.x, h.nimg * sizeof(double), hipMemcpyDeviceToHost, h.st));
-        PFB_HIP(hipMemcpyAsync(v_host, h.v, h.ncoef * sizeof(double), hipMemcpyDeviceToHost, h.st));
-        PFB_HIP(hipStreamSynchronize(h.st));
+        synced(h.st, [&] {
+            pd_solve(&h, lam, tol, maxit, info != nullptr && maxit <= 64, info);
+            PFB_HIP(hipMemcpyAsync(x_host, h.x, h.nimg * sizeof(double), hipMemcpyDeviceToHost, h.st));
+            PFB_HIP(hipMemcpyAsync(v_host, h.v, h.ncoef * sizeof(double), hipMemcpyDeviceToHost, h.st));
+        });
     });
 }
 
@@ -280,7 +283,6 @@ int pfbhip_pd_create(pfbhip_psi *psi, pfbhip_psfconv *const *pcs, int64_t nband,
         PFB_REQUIRE(out, "bad arguments");
         std::unique_ptr<pfbhip_pd> h(new pfbhip_pd(psi, pcs, nband, nparts, psf_slots, beam_slots, scale, eta, xtilde_host, gamma, x_host,
                                                    v_host, weight_host, sigma, tau, positivity, nullptr));
-        PFB_HIP(hipStreamSynchronize(h->st));
         *out = h.release();
     });
 }
@@ -315,9 +317,10 @@ int pfbhip_pd_run(pfbhip_pd *h, double lam, double tol, int maxit, double *x_hos
     return guarded([&] {
         PFB_REQUIRE(h && x_host && maxit >= 1, "bad arguments");
         h->run.require_runnable(maxit);
-        pd_solve(h, lam, tol, maxit, maxit <= 64, info);
-        PFB_HIP(hipMemcpyAsync(x_host, h->x, h->nimg * sizeof(double), hipMemcpyDeviceToHost, h->st));
-        PFB_HIP(hipStreamSynchronize(h->st));
+        synced(h->st, [&] {
+            pd_solve(h, lam, tol, maxit, maxit <= 64, info);
+            PFB_HIP(hipMemcpyAsync(x_host, h->x, h->nimg * sizeof(double), hipMemcpyDeviceToHost, h->st));
+        });
         h->traffic.d2h_bytes += int64_t(h->nimg * sizeof(double));
     });
 }
@@ -326,9 +329,9 @@ int pfbhip_pd_get_dual(pfbhip_pd *h, double *v_host)
 {
     return guarded([&] {
         PFB_REQUIRE(h && v_host, "NULL argument");
-        // the dual of the last iteration run (the start value before the first)
-        PFB_HIP(hipMemcpyAsync(v_host, h->run.iterate(h->v, h->vp), h->ncoef * sizeof(double), hipMemcpyDeviceToHost, h->st));
-        PFB_HIP(hipStreamSynchronize(h->st));
+        synced(h->st, [&] {  // the dual of the last iteration run (the start value before the first)
+            PFB_HIP(hipMemcpyAsync(v_host, h->run.iterate(h->v, h->vp), h->ncoef * sizeof(double), hipMemcpyDeviceToHost, h->st));
+        });
         h->traffic.d2h_bytes += int64_t(h->ncoef * sizeof(double));
     });
 }
@@ -357,7 +360,6 @@ int pfbhip_psfconv_power_method(pfbhip_psfconv *const *pcs, int64_t nband, const
         hipStream_t st = bands.stream();
         StreamScope scope(nullptr, bands, st);
         DevBuf<double> bp(nimg), red(comm != nullptr ? 3 : 0);
-        PFB_HIP(hipMemcpyAsync(bp.p, b_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
         DevPower pm(int64_t(nimg), st);
         auto aop = [&](const double *in, double *out) {
             for (int64_t b = 0; b < nband; ++b) bands.apply(b, in + size_t(b) * npix, out + size_t(b) * npix, 1.0, 1.0, false);
@@ -369,9 +371,11 @@ int pfbhip_psfconv_power_method(pfbhip_psfconv *const *pcs, int64_t nband, const
             PFB_CHECK_STATUS(pfbhip_comm_allreduce_sum(comm, red.p, red.p, 3));
             PFB_HIP(hipMemcpy(s, red.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
         };
-        pm.run(aop, allreduce, bp.p, tol, maxit, info);
-        PFB_HIP(hipMemcpyAsync(b_host, bp.p, nimg * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(bp.p, b_host, nimg * sizeof(double), hipMemcpyHostToDevice, st));
+            pm.run(aop, allreduce, bp.p, tol, maxit, info);
+            PFB_HIP(hipMemcpyAsync(b_host, bp.p, nimg * sizeof(double), hipMemcpyDeviceToHost, st));
+        });
     });
 }
 

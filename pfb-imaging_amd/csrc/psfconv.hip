@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "realfft2d.hpp"
 #include "psffft_api.hpp"
@@ -26,8 +27,6 @@
 #include "devcg.hpp"
 
 namespace pfbhip {
-
-static inline dim3 blocks1d(int64_t n, int t = 256) { return dim3(uint32_t(std::max<int64_t>(ceil_div(n, t), 1))); }
 
 // xpad (nxp, nyp): [0:nx, 0:ny] = x * beam, 0 elsewhere
 __global__ void k_psf_pad(const double *x, const double *beam, int nx, int ny, int nxp, int nyp, double *xpad)
@@ -206,16 +205,14 @@ int pfbhip_psfconv_set_psfhat(pfbhip_psfconv *p, int64_t slot, const double *psf
         PFB_REQUIRE(p && psfhat_host, "NULL argument");
         auto &s = p->slot(p->psf, slot);
         size_t n = size_t(p->nxp) * size_t(p->nyo2) * (is_complex ? 2 : 1);
-        s.data.ensure(n);
-        if (p->own.ok) {  // keep (nyo2, nxp): the layout the per-frequency pass reads contiguously
-            DevBuf<double> tmp(n);
-            PFB_HIP(hipMemcpyAsync(tmp.p, psfhat_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-            p->own.transpose_psf(tmp.p, is_complex != 0, s.data.p, p->stream);
-            PFB_HIP(hipStreamSynchronize(p->stream));
-        } else {
-            PFB_HIP(hipMemcpyAsync(s.data.p, psfhat_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-            PFB_HIP(hipStreamSynchronize(p->stream));
-        }
+        DevBuf<double> tmp;
+        synced(p->stream, [&] {
+            s.data.ensure(n);
+            if (p->own.ok)  // keep (nyo2, nxp): the layout the per-frequency pass reads contiguously
+                p->own.transpose_psf(upload(tmp, psfhat_host, n, p->stream), is_complex != 0, s.data.p, p->stream);
+            else
+                upload(s.data, psfhat_host, n, p->stream);
+        });
         s.is_complex = is_complex != 0;
         s.bound = true;
     });
@@ -231,9 +228,7 @@ int pfbhip_psfconv_set_beam(pfbhip_psfconv *p, int64_t slot, const double *beam_
             return;
         }
         size_t n = size_t(p->nx) * size_t(p->ny);
-        s.data.ensure(n);
-        PFB_HIP(hipMemcpyAsync(s.data.p, beam_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] { upload(s.data, beam_host, n, p->stream); });
         s.bound = true;
     });
 }
@@ -243,8 +238,7 @@ int pfbhip_psfconv_apply_dev(pfbhip_psfconv *p, const double *x_dev, int64_t psf
 {
     return guarded([&] {
         PFB_REQUIRE(p && x_dev && out_dev, "NULL argument");
-        p->apply(x_dev, psf_slot, beam_slot, mode, shift, scale, eta, accumulate, out_dev);
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] { p->apply(x_dev, psf_slot, beam_slot, mode, shift, scale, eta, accumulate, out_dev); });
     });
 }
 
@@ -254,14 +248,13 @@ int pfbhip_psfconv_apply(pfbhip_psfconv *p, const double *x_host, int64_t psf_sl
     return guarded([&] {
         PFB_REQUIRE(p && x_host && out_host, "NULL argument");
         size_t n = size_t(p->nx) * size_t(p->ny);
-        p->d_x.ensure(n);
-        p->d_out.ensure(n);
-        PFB_HIP(hipMemcpyAsync(p->d_x.p, x_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        if (accumulate)
-            PFB_HIP(hipMemcpyAsync(p->d_out.p, out_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        p->apply(p->d_x.p, psf_slot, beam_slot, mode, shift, scale, eta, accumulate, p->d_out.p);
-        PFB_HIP(hipMemcpyAsync(out_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] {
+            const double *x = upload(p->d_x, x_host, n, p->stream);
+            p->d_out.ensure(n);
+            if (accumulate) PFB_HIP(hipMemcpyAsync(p->d_out.p, out_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
+            p->apply(x, psf_slot, beam_slot, mode, shift, scale, eta, accumulate, p->d_out.p);
+            PFB_HIP(hipMemcpyAsync(out_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        });
     });
 }
 
@@ -283,20 +276,19 @@ int pfbhip_psfconv_direct(pfbhip_psfconv *p, const double *x_host, int64_t psf_s
     return guarded([&] {
         PFB_REQUIRE(p && x_host && out_host, "NULL argument");
         const size_t n = size_t(p->nx) * size_t(p->ny);
-        p->d_x.ensure(n);
-        p->d_out.ensure(n);
-        PFB_HIP(hipMemcpyAsync(p->d_x.p, x_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        p->apply(p->d_x.p, psf_slot, taper_slot, 2, shift, 1.0, 0.0, 0, p->d_out.p);
-        if (raw_host) PFB_HIP(hipMemcpyAsync(raw_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        if (beam_slot >= 0) {
-            PFB_REQUIRE(beam_slot < int64_t(p->beam.size()) && p->beam[size_t(beam_slot)]->bound, "beam slot %lld is not bound",
-                        (long long)beam_slot);
-            hipLaunchKernelGGL(k_beam_divide, dim3(uint32_t(ceil_div(int64_t(n), 256))), dim3(256), 0, p->stream, int64_t(n),
-                               p->beam[size_t(beam_slot)]->data.p, min_beam, p->d_out.p);
-            PFB_HIP(hipGetLastError());
-        }
-        PFB_HIP(hipMemcpyAsync(out_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] {
+            p->d_out.ensure(n);
+            p->apply(upload(p->d_x, x_host, n, p->stream), psf_slot, taper_slot, 2, shift, 1.0, 0.0, 0, p->d_out.p);
+            if (raw_host) PFB_HIP(hipMemcpyAsync(raw_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+            if (beam_slot >= 0) {
+                PFB_REQUIRE(beam_slot < int64_t(p->beam.size()) && p->beam[size_t(beam_slot)]->bound, "beam slot %lld is not bound",
+                            (long long)beam_slot);
+                hipLaunchKernelGGL(k_beam_divide, dim3(uint32_t(ceil_div(int64_t(n), 256))), dim3(256), 0, p->stream, int64_t(n),
+                                   p->beam[size_t(beam_slot)]->data.p, min_beam, p->d_out.p);
+                PFB_HIP(hipGetLastError());
+            }
+            PFB_HIP(hipMemcpyAsync(out_host, p->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        });
     });
 }
 
@@ -309,18 +301,19 @@ int pfbhip_psfconv_cg(pfbhip_psfconv *p, int64_t nparts, const int64_t *psf_slot
         hipStream_t st = p->stream;
         const size_t n = size_t(p->nx) * size_t(p->ny);
         DevBuf<double> b{n}, x{n};
-        PFB_HIP(hipMemcpyAsync(b.p, rhs_host, n * sizeof(double), hipMemcpyHostToDevice, st));
-        if (has_x0) PFB_HIP(hipMemcpyAsync(x.p, x_host, n * sizeof(double), hipMemcpyHostToDevice, st));
-        else PFB_HIP(hipMemsetAsync(x.p, 0, n * sizeof(double), st));
         DevCG cg(int64_t(n), st);
-        cg.solve(
-            [&](const double *in, double *out) {
-                for (int64_t k = 0; k < nparts; ++k)
-                    p->apply(in, psf_slots[k], beam_slots[k], 0, 0.0, scale, k == 0 ? eta : 0.0, k > 0, out);
-            },
-            b.p, x.p, tol, maxit, minit, info);
-        PFB_HIP(hipMemcpyAsync(x_host, x.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(b.p, rhs_host, n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (has_x0) PFB_HIP(hipMemcpyAsync(x.p, x_host, n * sizeof(double), hipMemcpyHostToDevice, st));
+            else PFB_HIP(hipMemsetAsync(x.p, 0, n * sizeof(double), st));
+            cg.solve(
+                [&](const double *in, double *out) {
+                    for (int64_t k = 0; k < nparts; ++k)
+                        p->apply(in, psf_slots[k], beam_slots[k], 0, 0.0, scale, k == 0 ? eta : 0.0, k > 0, out);
+                },
+                b.p, x.p, tol, maxit, minit, info);
+            PFB_HIP(hipMemcpyAsync(x_host, x.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
@@ -372,17 +365,18 @@ static int r2c_2d_impl(const double *in_host, int64_t nbatch, int64_t n0, int64_
         const size_t nr = size_t(n0) * size_t(n1), nc = size_t(n0) * size_t(n1 / 2 + 1);
         DevBuf<double> d_in(nr);
         DevBuf<double2> d_out(nc);
-        for (int64_t b = 0; b < nbatch; ++b) {
-            PFB_HIP(hipMemcpyAsync(d_in.p, in_host + size_t(b) * nr, nr * sizeof(double), hipMemcpyHostToDevice, st));
-            fft.r2c(d_in.p, d_out.p);
-            if (centred) {
-                hipLaunchKernelGGL(k_checker_sign, dim3(uint32_t(ceil_div(int64_t(nc), 256))), dim3(256), 0, st, d_out.p, n0, n1 / 2 + 1);
-                PFB_HIP(hipGetLastError());
+        synced(st, [&] {
+            for (int64_t b = 0; b < nbatch; ++b) {
+                PFB_HIP(hipMemcpyAsync(d_in.p, in_host + size_t(b) * nr, nr * sizeof(double), hipMemcpyHostToDevice, st));
+                fft.r2c(d_in.p, d_out.p);
+                if (centred) {
+                    hipLaunchKernelGGL(k_checker_sign, dim3(uint32_t(ceil_div(int64_t(nc), 256))), dim3(256), 0, st, d_out.p, n0, n1 / 2 + 1);
+                    PFB_HIP(hipGetLastError());
+                }
+                PFB_HIP(hipMemcpyAsync(out_host + size_t(b) * nc * 2, d_out.p, nc * sizeof(double2), hipMemcpyDeviceToHost,
+                                       st));
             }
-            PFB_HIP(hipMemcpyAsync(out_host + size_t(b) * nc * 2, d_out.p, nc * sizeof(double2), hipMemcpyDeviceToHost,
-                                   st));
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        });
     });
 }
 
@@ -407,15 +401,16 @@ int pfbhip_c2r_2d(const double *in_host, int64_t nbatch, int64_t n0, int64_t n1,
         const size_t nr = size_t(n0) * size_t(n1), nc = size_t(n0) * size_t(n1 / 2 + 1);
         DevBuf<double> d_out(nr);
         DevBuf<double2> d_in(nc);
-        for (int64_t b = 0; b < nbatch; ++b) {
-            PFB_HIP(hipMemcpyAsync(d_in.p, in_host + size_t(b) * nc * 2, nc * sizeof(double2), hipMemcpyHostToDevice,
-                                   st));
-            fft.c2r(d_in.p, d_out.p);
-            hipLaunchKernelGGL(k_scale, blocks1d(int64_t(nr)), dim3(256), 0, st, d_out.p, 1.0 / double(nr), int64_t(nr));
-            PFB_HIP(hipGetLastError());
-            PFB_HIP(hipMemcpyAsync(out_host + size_t(b) * nr, d_out.p, nr * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            for (int64_t b = 0; b < nbatch; ++b) {
+                PFB_HIP(hipMemcpyAsync(d_in.p, in_host + size_t(b) * nc * 2, nc * sizeof(double2), hipMemcpyHostToDevice,
+                                       st));
+                fft.c2r(d_in.p, d_out.p);
+                hipLaunchKernelGGL(k_scale, blocks1d(int64_t(nr)), dim3(256), 0, st, d_out.p, 1.0 / double(nr), int64_t(nr));
+                PFB_HIP(hipGetLastError());
+                PFB_HIP(hipMemcpyAsync(out_host + size_t(b) * nr, d_out.p, nr * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+        });
     });
 }
 

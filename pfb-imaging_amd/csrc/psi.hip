@@ -14,6 +14,7 @@
 #include <memory>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "pipeline_api.hpp"
 
@@ -627,8 +628,7 @@ int pfbhip_psi_dot_dev(pfbhip_psi *p, const double *x_dev, double *alpha_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(p && x_dev && alpha_dev, "NULL argument");
-        p->dot(x_dev, alpha_dev);
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] { p->dot(x_dev, alpha_dev); });
     });
 }
 
@@ -636,8 +636,7 @@ int pfbhip_psi_hdot_dev(pfbhip_psi *p, const double *alpha_dev, double *x_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(p && x_dev && alpha_dev, "NULL argument");
-        p->hdot(alpha_dev, x_dev);
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] { p->hdot(alpha_dev, x_dev); });
     });
 }
 
@@ -647,22 +646,21 @@ int pfbhip_psi_dot(pfbhip_psi *p, const double *x_host, double *alpha_host, int 
     return guarded([&] {
         PFB_REQUIRE(p && x_host && alpha_host, "NULL argument");
         const size_t n = size_t(p->nx) * size_t(p->ny), plane = size_t(p->nxmax) * size_t(p->nymax);
-        p->d_x.ensure(n);
-        p->d_alpha.ensure(p->cube());
-        PFB_HIP(hipMemcpyAsync(p->d_x.p, x_host, n * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        p->dot(p->d_x.p, p->d_alpha.p);
-        const double *src = p->d_alpha.p;
-        if (transposed) {
-            p->d_alphaT.ensure(p->cube());
-            for (int b = 0; b < p->nbasis; ++b)
-                hipLaunchKernelGGL(k_transpose_f64_any, dim3(uint32_t(ceil_div(p->nymax, 32)), uint32_t(ceil_div(p->nxmax, 32))),
-                                   dim3(32, 8), 0, p->stream, p->d_alpha.p + size_t(b) * plane, int(p->nxmax), int(p->nymax),
-                                   p->d_alphaT.p + size_t(b) * plane);
-            PFB_HIP(hipGetLastError());
-            src = p->d_alphaT.p;
-        }
-        PFB_HIP(hipMemcpyAsync(alpha_host, src, p->cube() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] {
+            p->d_alpha.ensure(p->cube());
+            p->dot(upload(p->d_x, x_host, n, p->stream), p->d_alpha.p);
+            const double *src = p->d_alpha.p;
+            if (transposed) {
+                p->d_alphaT.ensure(p->cube());
+                for (int b = 0; b < p->nbasis; ++b)
+                    hipLaunchKernelGGL(k_transpose_f64_any, dim3(uint32_t(ceil_div(p->nymax, 32)), uint32_t(ceil_div(p->nxmax, 32))),
+                                       dim3(32, 8), 0, p->stream, p->d_alpha.p + size_t(b) * plane, int(p->nxmax), int(p->nymax),
+                                       p->d_alphaT.p + size_t(b) * plane);
+                PFB_HIP(hipGetLastError());
+                src = p->d_alphaT.p;
+            }
+            PFB_HIP(hipMemcpyAsync(alpha_host, src, p->cube() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        });
     });
 }
 
@@ -671,23 +669,23 @@ int pfbhip_psi_hdot(pfbhip_psi *p, const double *alpha_host, double *x_host, int
     return guarded([&] {
         PFB_REQUIRE(p && x_host && alpha_host, "NULL argument");
         const size_t n = size_t(p->nx) * size_t(p->ny), plane = size_t(p->nxmax) * size_t(p->nymax);
-        p->d_x.ensure(n);
-        p->d_alpha.ensure(p->cube());
-        const double *src = p->d_alpha.p;
-        if (transposed) {
-            p->d_alphaT.ensure(p->cube());
-            PFB_HIP(hipMemcpyAsync(p->d_alphaT.p, alpha_host, p->cube() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-            for (int b = 0; b < p->nbasis; ++b)
-                hipLaunchKernelGGL(k_transpose_f64_any, dim3(uint32_t(ceil_div(p->nxmax, 32)), uint32_t(ceil_div(p->nymax, 32))),
-                                   dim3(32, 8), 0, p->stream, p->d_alphaT.p + size_t(b) * plane, int(p->nymax), int(p->nxmax),
-                                   p->d_alpha.p + size_t(b) * plane);
-            PFB_HIP(hipGetLastError());
-        } else {
-            PFB_HIP(hipMemcpyAsync(p->d_alpha.p, alpha_host, p->cube() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-        }
-        p->hdot(src, p->d_x.p);
-        PFB_HIP(hipMemcpyAsync(x_host, p->d_x.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        PFB_HIP(hipStreamSynchronize(p->stream));
+        synced(p->stream, [&] {
+            p->d_x.ensure(n);
+            p->d_alpha.ensure(p->cube());
+            const double *src = p->d_alpha.p;
+            if (transposed) {
+                upload(p->d_alphaT, alpha_host, p->cube(), p->stream);
+                for (int b = 0; b < p->nbasis; ++b)
+                    hipLaunchKernelGGL(k_transpose_f64_any, dim3(uint32_t(ceil_div(p->nxmax, 32)), uint32_t(ceil_div(p->nymax, 32))),
+                                       dim3(32, 8), 0, p->stream, p->d_alphaT.p + size_t(b) * plane, int(p->nymax), int(p->nxmax),
+                                       p->d_alpha.p + size_t(b) * plane);
+                PFB_HIP(hipGetLastError());
+            } else {
+                upload(p->d_alpha, alpha_host, p->cube(), p->stream);
+            }
+            p->hdot(src, p->d_x.p);
+            PFB_HIP(hipMemcpyAsync(x_host, p->d_x.p, n * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        });
     });
 }
 
@@ -698,10 +696,11 @@ int pfbhip_l21_vtilde_sum_dev(const double *vp_dev, double *v_dev, int64_t nband
     return guarded([&] {
         PFB_REQUIRE(vp_dev && v_dev && sum_dev && nband >= 1 && n >= 0, "bad arguments");
         if (n == 0) return;
-        hipLaunchKernelGGL(k_l21_vtilde, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, vp_dev, v_dev, int(nband), n,
-                           sigma, sum_dev);
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(nullptr));
+        synced(nullptr, [&] {
+            hipLaunchKernelGGL(k_l21_vtilde, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, vp_dev, v_dev, int(nband), n,
+                               sigma, sum_dev);
+            PFB_HIP(hipGetLastError());
+        });
     });
 }
 
@@ -710,10 +709,11 @@ int pfbhip_l21_scale_dev(double *v_dev, int64_t nband, int64_t n, double lam, co
     return guarded([&] {
         PFB_REQUIRE(v_dev && weight_dev && sum_dev && nband >= 1 && n >= 0, "bad arguments");
         if (n == 0) return;
-        hipLaunchKernelGGL(k_l21_scale, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, v_dev, int(nband), n, lam,
-                           weight_dev, sum_dev);
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(nullptr));
+        synced(nullptr, [&] {
+            hipLaunchKernelGGL(k_l21_scale, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, v_dev, int(nband), n, lam,
+                               weight_dev, sum_dev);
+            PFB_HIP(hipGetLastError());
+        });
     });
 }
 
@@ -774,9 +774,10 @@ int pfbhip_positivity_dev(double *x_dev, int64_t nband, int64_t n, int mode)
     return guarded([&] {
         PFB_REQUIRE(x_dev && nband >= 1 && n >= 0 && (mode == 1 || mode == 2), "bad arguments");
         if (n == 0) return;
-        hipLaunchKernelGGL(k_positivity, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, x_dev, int(nband), n, mode);
-        PFB_HIP(hipGetLastError());
-        PFB_HIP(hipStreamSynchronize(nullptr));
+        synced(nullptr, [&] {
+            hipLaunchKernelGGL(k_positivity, dim3(uint32_t(ceil_div(n, 256))), dim3(256), 0, nullptr, x_dev, int(nband), n, mode);
+            PFB_HIP(hipGetLastError());
+        });
     });
 }
 

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <memory>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "realfft2d.hpp"
 
@@ -382,8 +383,9 @@ int pfbhip_gaussconv_apply_dev(pfbhip_gaussconv *h, const double *image_dev, con
         check_scales(scale_x, scale_y);
         PFB_REQUIRE(!kerni_dev || gausspari, "kerni without gausspari");
         PFB_REQUIRE(!gausspari || (kernf_dev == nullptr) == (kerni_dev == nullptr), "kernf and kerni must be given together");
-        h->apply(image_dev, gaussparf, nparf, gausspari, norm_kernel, scale_x, scale_y, kernf_dev, kerni_dev, out_dev);
-        PFB_HIP(hipStreamSynchronize(h->stream));
+        synced(h->stream, [&] {
+            h->apply(image_dev, gaussparf, nparf, gausspari, norm_kernel, scale_x, scale_y, kernf_dev, kerni_dev, out_dev);
+        });
     });
 }
 
@@ -399,21 +401,14 @@ int pfbhip_gaussconv_apply(pfbhip_gaussconv *h, const double *image_host, const 
         PFB_REQUIRE(!gausspari || (kernf_host == nullptr) == (kerni_host == nullptr), "kernf and kerni must be given together");
         const size_t n = size_t(h->nband) * h->npix(), bytes = n * sizeof(double);
         hipStream_t st = h->stream;
-        h->d_a.ensure(n);
-        h->d_o.ensure(n);
-        PFB_HIP(hipMemcpyAsync(h->d_a.p, image_host, bytes, hipMemcpyHostToDevice, st));
-        if (kernf_host) {
-            h->d_kf.ensure(size_t(nparf) * h->npix());
-            PFB_HIP(hipMemcpyAsync(h->d_kf.p, kernf_host, size_t(nparf) * h->npix() * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        if (kerni_host) {
-            h->d_ki.ensure(n);
-            PFB_HIP(hipMemcpyAsync(h->d_ki.p, kerni_host, bytes, hipMemcpyHostToDevice, st));
-        }
-        h->apply(h->d_a.p, gaussparf, nparf, gausspari, norm_kernel, scale_x, scale_y, kernf_host ? h->d_kf.p : nullptr,
-                 kerni_host ? h->d_ki.p : nullptr, h->d_o.p);
-        PFB_HIP(hipMemcpyAsync(out_host, h->d_o.p, bytes, hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            const double *image = upload(h->d_a, image_host, n, st);
+            const double *kernf = upload(h->d_kf, kernf_host, size_t(nparf) * h->npix(), st);
+            const double *kerni = upload(h->d_ki, kerni_host, n, st);
+            h->d_o.ensure(n);
+            h->apply(image, gaussparf, nparf, gausspari, norm_kernel, scale_x, scale_y, kernf, kerni, h->d_o.p);
+            PFB_HIP(hipMemcpyAsync(out_host, h->d_o.p, bytes, hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
@@ -432,8 +427,7 @@ int pfbhip_gaussconv_restore_dev(pfbhip_gaussconv *h, const double *model_dev, c
         PFB_REQUIRE(h && model_dev && residual_dev && image_dev, "NULL argument");
         h->check_args(gaussparf, nparf, gausspari, npari, true);
         check_wsum(h, wsum);
-        h->restore(model_dev, residual_dev, wsum, gausspari, gaussparf, nparf, image_dev);
-        PFB_HIP(hipStreamSynchronize(h->stream));
+        synced(h->stream, [&] { h->restore(model_dev, residual_dev, wsum, gausspari, gaussparf, nparf, image_dev); });
     });
 }
 
@@ -446,14 +440,13 @@ int pfbhip_gaussconv_restore(pfbhip_gaussconv *h, const double *model_host, cons
         check_wsum(h, wsum);
         const size_t n = size_t(h->nband) * h->npix(), bytes = n * sizeof(double);
         hipStream_t st = h->stream;
-        h->d_a.ensure(n);
-        h->d_b.ensure(n);
-        h->d_o.ensure(n);
-        PFB_HIP(hipMemcpyAsync(h->d_a.p, model_host, bytes, hipMemcpyHostToDevice, st));
-        PFB_HIP(hipMemcpyAsync(h->d_b.p, residual_host, bytes, hipMemcpyHostToDevice, st));
-        h->restore(h->d_a.p, h->d_b.p, wsum, gausspari, gaussparf, nparf, h->d_o.p);
-        PFB_HIP(hipMemcpyAsync(image_host, h->d_o.p, bytes, hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            const double *model = upload(h->d_a, model_host, n, st);
+            const double *residual = upload(h->d_b, residual_host, n, st);
+            h->d_o.ensure(n);
+            h->restore(model, residual, wsum, gausspari, gaussparf, nparf, h->d_o.p);
+            PFB_HIP(hipMemcpyAsync(image_host, h->d_o.p, bytes, hipMemcpyDeviceToHost, st));
+        });
     });
 }
 

@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "pipeline_api.hpp"
 
@@ -166,26 +167,26 @@ static void rms_sync(hipStream_t st, double *coef, int64_t nband, int nbasis, in
 {
     const int64_t n = int64_t(nbasis) * m;
     DevBuf<double> partials(size_t(nbasis) * RW_BLOCKS * 2);
-    std::vector<double> host(size_t(nbasis) * RW_BLOCKS * 2);
-    hipLaunchKernelGGL(k_l21_rms_sum, dim3(RW_BLOCKS, uint32_t(nbasis)), dim3(256), 0, st, coef, int(nband), n, m, partials.p);
-    PFB_HIP(hipGetLastError());
-    PFB_HIP(hipMemcpyAsync(host.data(), partials.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFB_HIP(hipStreamSynchronize(st));
-    std::vector<double> cnt(size_t(nbasis), 0.0);
-    for (int b = 0; b < nbasis; ++b) {
-        double c = 0.0, t = 0.0;
-        for (int i = 0; i < RW_BLOCKS; ++i) {  // (fixed order: the result does not depend on the schedule)
-            c += host[(size_t(b) * RW_BLOCKS + size_t(i)) * 2];
-            t += host[(size_t(b) * RW_BLOCKS + size_t(i)) * 2 + 1];
+    std::vector<double> host(size_t(nbasis) * RW_BLOCKS * 2), cnt(size_t(nbasis), 0.0);
+    synced(st, [&] {  // (partials and host are declared outside: they outlive the wait on every path)
+        hipLaunchKernelGGL(k_l21_rms_sum, dim3(RW_BLOCKS, uint32_t(nbasis)), dim3(256), 0, st, coef, int(nband), n, m, partials.p);
+        PFB_HIP(hipGetLastError());
+        PFB_HIP(hipMemcpyAsync(host.data(), partials.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        PFB_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < nbasis; ++b) {
+            double c = 0.0, t = 0.0;
+            for (int i = 0; i < RW_BLOCKS; ++i) {  // (fixed order: the result does not depend on the schedule)
+                c += host[(size_t(b) * RW_BLOCKS + size_t(i)) * 2];
+                t += host[(size_t(b) * RW_BLOCKS + size_t(i)) * 2 + 1];
+            }
+            cnt[size_t(b)] = c;
+            if (c > 0.0)
+                hipLaunchKernelGGL(k_l21_rms_dev2, dim3(RW_BLOCKS), dim3(256), 0, st, coef + size_t(b) * size_t(m), m, t / c,
+                                   partials.p + size_t(b) * RW_BLOCKS);
         }
-        cnt[size_t(b)] = c;
-        if (c > 0.0)
-            hipLaunchKernelGGL(k_l21_rms_dev2, dim3(RW_BLOCKS), dim3(256), 0, st, coef + size_t(b) * size_t(m), m, t / c,
-                               partials.p + size_t(b) * RW_BLOCKS);
-    }
-    PFB_HIP(hipGetLastError());
-    PFB_HIP(hipMemcpyAsync(host.data(), partials.p, size_t(nbasis) * RW_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFB_HIP(hipStreamSynchronize(st));
+        PFB_HIP(hipGetLastError());
+        PFB_HIP(hipMemcpyAsync(host.data(), partials.p, size_t(nbasis) * RW_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+    });
     for (int b = 0; b < nbasis; ++b) {
         double q = 0.0;
         for (int i = 0; i < RW_BLOCKS; ++i) q += host[size_t(b) * RW_BLOCKS + size_t(i)];
@@ -237,9 +238,10 @@ int pfbhip_l21_reweight_dev(pfbhip_psi *psi, const double *x_dev, int64_t nband,
         const Geometry g = geometry(psi);
         check_rms(rms, g.nbasis, alpha);
         const hipStream_t st = psi_stream(psi);
-        analyse(psi, g, x_dev, nband, scratch_dev);
-        reweight_async(st, scratch_dev, nband, g.nbasis, g.m, rms, rmsfactor, alpha, weight_dev);
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            analyse(psi, g, x_dev, nband, scratch_dev);
+            reweight_async(st, scratch_dev, nband, g.nbasis, g.m, rms, rmsfactor, alpha, weight_dev);
+        });
     });
 }
 
@@ -249,7 +251,7 @@ int pfbhip_l21_rms_dev(pfbhip_psi *psi, const double *update_dev, int64_t nband,
     return guarded([&] {
         PFB_REQUIRE(psi && update_dev && scratch_dev && rms_out && count_out && nband >= 1, "bad arguments");
         const Geometry g = geometry(psi);
-        analyse(psi, g, update_dev, nband, scratch_dev);
+        synced(psi_stream(psi), [&] { analyse(psi, g, update_dev, nband, scratch_dev); });
         rms_sync(psi_stream(psi), scratch_dev, nband, g.nbasis, g.m, rms_out, count_out);
     });
 }
@@ -263,19 +265,19 @@ int pfbhip_l21_reweight(pfbhip_psi *psi, const double *x_host, int64_t nband, co
         check_rms(rms, g.nbasis, alpha);
         const hipStream_t st = psi_stream(psi);
         DevBuf<double> x(size_t(nband) * g.npix), coef(size_t(nband) * g.cube), w(g.cube);
-        PFB_HIP(hipMemcpyAsync(x.p, x_host, x.n * sizeof(double), hipMemcpyHostToDevice, st));
-        analyse(psi, g, x.p, nband, coef.p);
-        reweight_async(st, coef.p, nband, g.nbasis, g.m, rms, rmsfactor, alpha, w.p);
-        PFB_HIP(hipMemcpyAsync(weight_host, w.p, g.cube * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (bandsum_host) {  // the band sum itself, as the rms passes form it (tests: bit-identical to np.sum(axis=0))
-            DevBuf<double> partials(size_t(g.nbasis) * RW_BLOCKS * 2);
-            hipLaunchKernelGGL(k_l21_rms_sum, dim3(RW_BLOCKS, uint32_t(g.nbasis)), dim3(256), 0, st, coef.p, int(nband),
-                               int64_t(g.cube), g.m, partials.p);
-            PFB_HIP(hipGetLastError());
-            PFB_HIP(hipMemcpyAsync(bandsum_host, coef.p, g.cube * sizeof(double), hipMemcpyDeviceToHost, st));
-            PFB_HIP(hipStreamSynchronize(st));  // (partials dies here: after the kernel that writes it)
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        DevBuf<double> partials(bandsum_host ? size_t(g.nbasis) * RW_BLOCKS * 2 : 0);
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(x.p, x_host, x.n * sizeof(double), hipMemcpyHostToDevice, st));
+            analyse(psi, g, x.p, nband, coef.p);
+            reweight_async(st, coef.p, nband, g.nbasis, g.m, rms, rmsfactor, alpha, w.p);
+            PFB_HIP(hipMemcpyAsync(weight_host, w.p, g.cube * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (bandsum_host) {  // the band sum itself, as the rms passes form it (tests: bit-identical to np.sum(axis=0))
+                hipLaunchKernelGGL(k_l21_rms_sum, dim3(RW_BLOCKS, uint32_t(g.nbasis)), dim3(256), 0, st, coef.p, int(nband),
+                                   int64_t(g.cube), g.m, partials.p);
+                PFB_HIP(hipGetLastError());
+                PFB_HIP(hipMemcpyAsync(bandsum_host, coef.p, g.cube * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+        });
     });
 }
 
@@ -286,8 +288,10 @@ int pfbhip_l21_rms(pfbhip_psi *psi, const double *update_host, int64_t nband, do
         const Geometry g = geometry(psi);
         const hipStream_t st = psi_stream(psi);
         DevBuf<double> x(size_t(nband) * g.npix), coef(size_t(nband) * g.cube);
-        PFB_HIP(hipMemcpyAsync(x.p, update_host, x.n * sizeof(double), hipMemcpyHostToDevice, st));
-        analyse(psi, g, x.p, nband, coef.p);
+        synced(st, [&] {
+            PFB_HIP(hipMemcpyAsync(x.p, update_host, x.n * sizeof(double), hipMemcpyHostToDevice, st));
+            analyse(psi, g, x.p, nband, coef.p);
+        });
         rms_sync(st, coef.p, nband, g.nbasis, g.m, rms_out, count_out);
     });
 }

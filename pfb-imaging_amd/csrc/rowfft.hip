@@ -11,6 +11,7 @@
 #include <mutex>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "rowfft.hpp"
 #include "rowfft_api.hpp"
@@ -1370,28 +1371,21 @@ int pfbhip_debug_rowfft(double *data_host, int64_t n, int64_t nrows, int inverse
         PFB_REQUIRE(plan.init(n), "row length %lld is not supported by the hand-written FFT", (long long)n);
         const RowFFTPlan &pl = plan.pl;
         const size_t tot = size_t(n) * size_t(nrows);
-        DevBuf<double2> d(tot);
-        PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
-        hipEvent_t a, b;
-        PFB_HIP(hipEventCreate(&a));
-        PFB_HIP(hipEventCreate(&b));
-        if (reps > 1) {  // warm-up on a scratch copy so that the result stays a single transform
-            DevBuf<double2> s(tot);
-            PFB_HIP(hipMemcpy(s.p, d.p, tot * sizeof(double2), hipMemcpyDeviceToDevice));
-            rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
-            PFB_HIP(hipEventRecord(a, nullptr));
-            for (int r = 0; r < reps; ++r) rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
-            PFB_HIP(hipEventRecord(b, nullptr));
-            PFB_HIP(hipEventSynchronize(b));
-            float ms = 0;
-            PFB_HIP(hipEventElapsedTime(&ms, a, b));
-            if (ms_out) *ms_out = ms / reps;
-        }
-        rowfft_plain(pl, d.p, int(nrows), inverse != 0, nullptr);
-        PFB_HIP(hipDeviceSynchronize());
-        PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
+        DevBuf<double2> d(tot), s(reps > 1 ? tot : 0);
+        EventTimer timer(reps > 1);
+        synced(nullptr, [&] {
+            PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
+            if (reps > 1) {  // warm-up on a scratch copy so that the result stays a single transform
+                PFB_HIP(hipMemcpy(s.p, d.p, tot * sizeof(double2), hipMemcpyDeviceToDevice));
+                rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
+                timer.start(nullptr);
+                for (int r = 0; r < reps; ++r) rowfft_plain(pl, s.p, int(nrows), inverse != 0, nullptr);
+                timer.stop(nullptr);
+            }
+            rowfft_plain(pl, d.p, int(nrows), inverse != 0, nullptr);
+            PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
+        });
+        if (reps > 1 && ms_out) *ms_out = timer.ms() / reps;
     });
 }
 
@@ -1406,22 +1400,16 @@ int pfbhip_debug_rowfft_shape(double *data_host, int64_t n, int64_t nrows, int i
         PFB_REQUIRE(plan.init(n), "row length %lld is not supported by the hand-written FFT", (long long)n);
         const size_t tot = size_t(n) * size_t(nrows);
         DevBuf<double2> d(tot);
-        PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
-        hipEvent_t a, b;
-        PFB_HIP(hipEventCreate(&a));
-        PFB_HIP(hipEventCreate(&b));
-        PFB_HIP(hipEventRecord(a, nullptr));
-        if (family == 0) rowfft_plain(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
-        else rowfft_plain_nodual(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
-        PFB_HIP(hipEventRecord(b, nullptr));
-        PFB_HIP(hipEventSynchronize(b));
-        float ms = 0;
-        PFB_HIP(hipEventElapsedTime(&ms, a, b));
-        if (ms_out) *ms_out = ms;
-        PFB_HIP(hipDeviceSynchronize());
-        PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
+        EventTimer timer(true);
+        synced(nullptr, [&] {
+            PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
+            timer.start(nullptr);
+            if (family == 0) rowfft_plain(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
+            else rowfft_plain_nodual(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
+            timer.stop(nullptr);
+            PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
+        });
+        if (ms_out) *ms_out = timer.ms();
     });
 }
 

@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 
 namespace pfbhip {
@@ -214,32 +215,6 @@ __global__ void __launch_bounds__(SK_THREADS) k_copy16(const float4 *__restrict_
     for (int64_t i = int64_t(blockIdx.x) * SK_THREADS + threadIdx.x; i < n; i += step) dst[i] = src[i];
 }
 
-struct Timer {  // device time between start() and stop() on one stream
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit Timer(bool on)
-    {
-        if (!on) return;
-        PFB_HIP(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) {
-            (void)hipEventDestroy(e0);
-            throw std::runtime_error("hipEventCreate failed");
-        }
-    }
-    ~Timer()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    void start(hipStream_t st) { if (e0) PFB_HIP(hipEventRecord(e0, st)); }
-    void stop(hipStream_t st) { if (e0) PFB_HIP(hipEventRecord(e1, st)); }
-    double ms()  // after the stream has been synchronised
-    {
-        float t = 0.f;
-        if (e0) PFB_HIP(hipEventElapsedTime(&t, e0, e1));
-        return double(t);
-    }
-};
-
 struct Shape {
     int64_t nrow, nchan, nant, ntime, nbin;
 };
@@ -350,8 +325,8 @@ void weight_data_impl(const pfbhip_stokes_spec *spec, const Shape &sh, const voi
     uint8_t *o_mask = out_dev ? mask : d_mask.p;
     const int64_t se = spec->corr_first ? 1 : ns, sk = spec->corr_first ? nsamp : 1;
     const auto run = spec->full_jones ? launch<R, 4, true> : nc == 4 ? launch<R, 4, false> : launch<R, 2, false>;
-    Timer timer(device_ms != nullptr);
-    try {
+    EventTimer timer(device_ms != nullptr);
+    synced(st, [&] {  // the inputs are read from the caller's memory until it returns
         PFB_HIP(hipMemcpyAsync(d_data.p, data, d_data.bytes(), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(d_wgt_in.p, weight, d_wgt_in.bytes(), hipMemcpyHostToDevice, st));
         PFB_HIP(hipMemcpyAsync(d_flag.p, flag, d_flag.bytes(), hipMemcpyHostToDevice, st));
@@ -371,11 +346,7 @@ void weight_data_impl(const pfbhip_stokes_spec *spec, const Shape &sh, const voi
             PFB_HIP(hipMemcpyAsync(wgt, d_wgt.p, d_wgt.bytes(), hipMemcpyDeviceToHost, st));
             if (mask) PFB_HIP(hipMemcpyAsync(mask, d_mask.p, d_mask.bytes(), hipMemcpyDeviceToHost, st));
         }
-    } catch (...) {
-        (void)hipStreamSynchronize(st);
-        throw;
-    }
-    PFB_HIP(hipStreamSynchronize(st));  // the inputs are read from the caller's memory until here
+    });
     if (device_ms) *device_ms = timer.ms();
 }
 
@@ -428,19 +399,15 @@ int pfbhip_debug_copy16(int64_t nbytes, int32_t reps, double *ms)
         DevBuf<float4> src{size_t(nbytes / 16)}, dst{size_t(nbytes / 16)};
         const int64_t n = nbytes / 16;
         const uint32_t grid = uint32_t(std::min<int64_t>(ceil_div(n, SK_THREADS), SK_MAX_WORKGROUPS));
-        Timer timer(true);
-        try {
+        EventTimer timer(true);
+        synced(st, [&] {
             PFB_HIP(hipMemsetAsync(src.p, 0, src.bytes(), st));
             hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(SK_THREADS), 0, st, src.p, dst.p, n);  // warm-up
             timer.start(st);
             for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(SK_THREADS), 0, st, src.p, dst.p, n);
             PFB_HIP(hipGetLastError());
             timer.stop(st);
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            throw;
-        }
-        PFB_HIP(hipStreamSynchronize(st));
+        });
         *ms = timer.ms() / double(reps);
     });
 }
