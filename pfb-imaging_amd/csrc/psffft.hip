@@ -15,14 +15,13 @@ namespace pfbhip {
 // y axis (passes 1 and 3): every plain shape of the row FFT.  x axis (pass 2: forward, multiply, inverse on the same
 // row): powers of two chain the two transforms in registers; lengths with a leading radix-3/5 pass hand the row
 // over through LDS (both components: N * 16 bytes <= 160 KiB, i.e. N <= 10240).
-#define PSF_FOR_SHAPES_Y(X) RF_FOR_SHAPES(X)
 #define PSF_FOR_SHAPES_X(X)                                                                                     \
     X(1, 10) X(1, 11) X(1, 12) X(1, 13) X(1, 14) X(3, 9) X(3, 10) X(3, 11) X(5, 8) X(5, 9) X(5, 10) X(5, 11) X(7, 8) \
     X(7, 9) X(7, 10) X(9, 7) X(9, 8) X(9, 9) X(9, 10) X(15, 7) X(15, 8) X(15, 9)
 // (32 complex per thread at 16384 points -- 512 threads, 256 VGPRs -- was tried against the 1024-thread /
 // 128-VGPR layout and its 35-120 spilled registers in these fused kernels: it spills more.)
 template <int L, int K>
-using PsfShape = RfShape<L, K, true, 0, false>;  // (both components in LDS: see the hand-over below)
+using PsfShape = RfShape<L, K, true, false>;  // (both components in LDS: see the hand-over below)
 
 // out (cols, rows) = in (rows, cols)^T, 32 x 32 tiles through LDS
 template <class T>
@@ -272,10 +271,34 @@ __global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_psf_rows_inv(const 
 
 // ---- host side -------------------------------------------------------------------------------------
 
-template <class Kern>
-static void psf_allow_lds(Kern kern, bool *)
+// f(PsfShape<L, K>{}) at the padded size n of an axis, then the launch's error.  y: every plain length of the row FFT (doubled
+// ones are refused); x: the lengths of PSF_FOR_SHAPES_X.
+template <class F>
+static void psf_launch_y(int64_t n, F &&f)
 {
-    allow_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024);  // per (device, kernel)
+    bool plain = false;
+    rf_with_length(n, [&](auto len) {
+        if constexpr (!len.doubled) {
+            plain = true;
+            f(PsfShape<len.LEAD, len.K>{});
+        }
+    });
+    PFB_REQUIRE(plain, "unsupported padded size %lld", (long long)n);
+    PFB_HIP(hipGetLastError());
+}
+template <class F>
+static void psf_launch_x(int64_t n, F &&f)
+{
+    bool found = false;
+#define PSF_X(L, K)                         \
+    if (n == (int64_t(L) << K)) {           \
+        found = true;                       \
+        f(PsfShape<L, K>{});                \
+    }
+    PSF_FOR_SHAPES_X(PSF_X)
+#undef PSF_X
+    PFB_REQUIRE(found, "unsupported padded size %lld", (long long)n);
+    PFB_HIP(hipGetLastError());
 }
 
 bool PsfFFT::init(int64_t nx_, int64_t ny_, int64_t nxp_, int64_t nyp_)
@@ -313,16 +336,14 @@ void PsfFFT::transpose_psf(const double *src_dev, bool is_complex, double *dst_d
 template <class S>
 static void launch_rows_fwd(const PsfFFT &p, const double *x, const double *beam, hipStream_t st)
 {
-    static bool attr = false;
-    psf_allow_lds(&k_psf_rows_fwd<S>, &attr);
+    allow_dynamic_lds(reinterpret_cast<const void *>(&k_psf_rows_fwd<S>), 160 * 1024);  // per (device, kernel)
     hipLaunchKernelGGL(k_psf_rows_fwd<S>, dim3(uint32_t((p.nx + 1) / 2)), dim3(S::T), size_t(S::LDS_BYTES), st, p.fy.pl.twiddle,
                        x, beam, int(p.nx), int(p.ny), p.t2.p, p.ld2);
 }
 template <class S>
 static void launch_cols(const PsfFFT &p, const double *psfT, bool is_complex, int mode, double shift, hipStream_t st)
 {
-    static bool attr = false;
-    psf_allow_lds(&k_psf_cols<S>, &attr);
+    allow_dynamic_lds(reinterpret_cast<const void *>(&k_psf_cols<S>), 160 * 1024);  // per (device, kernel)
     hipLaunchKernelGGL(k_psf_cols<S>, dim3(uint32_t(p.nyo2)), dim3(S::T), size_t(S::LDS_BYTES), st, p.fx.pl.twiddle, p.t2.p, p.ld2,
                        int(p.nx), int(p.nyo2), psfT, is_complex ? 1 : 0, mode, shift, 1.0 / (double(p.nxp) * double(p.nyp)), p.t1.p,
                        p.ld1);
@@ -331,8 +352,7 @@ template <class S>
 static void launch_rows_inv(const PsfFFT &p, const double *beam, const double *x, double scale, double eta, int accumulate,
                             double *out, hipStream_t st)
 {
-    static bool attr = false;
-    psf_allow_lds(&k_psf_rows_inv<S>, &attr);
+    allow_dynamic_lds(reinterpret_cast<const void *>(&k_psf_rows_inv<S>), 160 * 1024);  // per (device, kernel)
     hipLaunchKernelGGL(k_psf_rows_inv<S>, dim3(uint32_t((p.nx + 1) / 2)), dim3(S::T), size_t(S::LDS_BYTES), st, p.fy.pl.twiddle,
                        p.t1.p, p.ld1, beam, x, int(p.nx), int(p.ny), scale, eta, accumulate, out);
 }
@@ -341,30 +361,9 @@ void PsfFFT::apply(const double *x_dev, const double *beam_dev, const double *ps
                    double scale, double eta, int accumulate, double *out_dev, hipStream_t st)
 {
     PFB_REQUIRE(ok, "PSF row-FFT plan is not initialised");
-    switch (nyp) {
-#define RF_X(L, K) \
-    case (L << K): launch_rows_fwd<PsfShape<L, K>>(*this, x_dev, beam_dev, st); break;
-        PSF_FOR_SHAPES_Y(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "unsupported padded size %lld", (long long)nyp);
-    }
-    PFB_HIP(hipGetLastError());
-    switch (nxp) {
-#define RF_X(L, K) \
-    case (L << K): launch_cols<PsfShape<L, K>>(*this, psfT_dev, is_complex, mode, shift, st); break;
-        PSF_FOR_SHAPES_X(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "unsupported padded size %lld", (long long)nxp);
-    }
-    PFB_HIP(hipGetLastError());
-    switch (nyp) {
-#define RF_X(L, K) \
-    case (L << K): launch_rows_inv<PsfShape<L, K>>(*this, beam_dev, x_dev, scale, eta, accumulate, out_dev, st); break;
-        PSF_FOR_SHAPES_Y(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "unsupported padded size %lld", (long long)nyp);
-    }
-    PFB_HIP(hipGetLastError());
+    psf_launch_y(nyp, [&](auto s) { launch_rows_fwd<decltype(s)>(*this, x_dev, beam_dev, st); });
+    psf_launch_x(nxp, [&](auto s) { launch_cols<decltype(s)>(*this, psfT_dev, is_complex, mode, shift, st); });
+    psf_launch_y(nyp, [&](auto s) { launch_rows_inv<decltype(s)>(*this, beam_dev, x_dev, scale, eta, accumulate, out_dev, st); });
 }
 
 }  // namespace pfbhip

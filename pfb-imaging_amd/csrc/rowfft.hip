@@ -66,9 +66,17 @@ __global__ void __launch_bounds__(S::T, S::WAVES_PER_SIMD) k_rowfft_plain(const 
 
 // LDS beyond 64 KiB needs the opt-in attribute, per (device, kernel): see allow_dynamic_lds()
 template <class Kern>
-static void rf_allow_lds(Kern kern, bool *)
+static void rf_allow_lds(Kern kern)
 {
     allow_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024);
+}
+
+// Runs f(RfLength) at the supported length N (f picks its shape type and launches) and collects the launch's error
+template <class F>
+static void rf_launch_at(int N, F &&f)
+{
+    PFB_REQUIRE(rf_with_length(N, f), "row length %d is not supported by the hand-written FFT", N);
+    PFB_HIP(hipGetLastError());
 }
 
 bool RowFFT::init(int64_t N)
@@ -121,58 +129,29 @@ void RowFFT::release()
 template <class S, bool INV>
 static void launch_plain(const RowFFTPlan &pl, double2 *data_dev, int nrows, size_t pitch, hipStream_t stream)
 {
-    static bool attr = false;
-    rf_allow_lds(&k_rowfft_plain<S, INV>, &attr);
+    rf_allow_lds(&k_rowfft_plain<S, INV>);
     hipLaunchKernelGGL((k_rowfft_plain<S, INV>), dim3(uint32_t(nrows)), dim3(S::T), size_t(S::LDS_BYTES), stream,
                        pl.twiddle, data_dev, nrows, pitch);
 }
 
-void rowfft_plain(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inverse, hipStream_t stream, size_t pitch)
+// The plain kernel on a shape family.  ALLOW_DUAL = true: RfShape<L, K>, what rowfft_plain runs.  false: RfShape<L, K, false>,
+// the family of the fused second-axis kernels (one component at a time in LDS, XPAD, one workgroup per CU) -- tests reach its
+// exchanges at a chosen length without a plan.  Doubled lengths: RfShape2 over the family's half-length shape.
+template <bool ALLOW_DUAL>
+static void rowfft_plain_family(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inverse, hipStream_t stream, size_t pitch)
 {
     if (pitch == 0) pitch = size_t(pl.N);
-    switch (pl.N) {
-#define RF_X(L, K)                                                                  \
-    case (L << K):                                                                  \
-        if (inverse) launch_plain<RfShape<L, K>, true>(pl, data_dev, nrows, pitch, stream); \
-        else launch_plain<RfShape<L, K>, false>(pl, data_dev, nrows, pitch, stream);        \
-        break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                                 \
-    case 2 * (L << K):                                                                             \
-        if (inverse) launch_plain<RfShape2<RfShape<L, K>>, true>(pl, data_dev, nrows, pitch, stream);     \
-        else launch_plain<RfShape2<RfShape<L, K>>, false>(pl, data_dev, nrows, pitch, stream);            \
-        break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rf_launch_at(pl.N, [&](auto len) {
+        using S1 = RfShape<len.LEAD, len.K, ALLOW_DUAL>;
+        using S = std::conditional_t<len.doubled, RfShape2<S1>, S1>;  // (names RfShape2<S1>, instantiates only the chosen one)
+        if (inverse) launch_plain<S, true>(pl, data_dev, nrows, pitch, stream);
+        else launch_plain<S, false>(pl, data_dev, nrows, pitch, stream);
+    });
 }
 
-// The plain kernel on the shape family of the fused second-axis kernels, RfShape<L, K, false> (one component at a time in LDS,
-// XPAD, one workgroup per CU; the doubled lengths over that S1): tests reach its exchanges at a chosen length without a plan.
-static void rowfft_plain_nodual(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inverse, hipStream_t stream)
+void rowfft_plain(const RowFFTPlan &pl, double2 *data_dev, int nrows, bool inverse, hipStream_t stream, size_t pitch)
 {
-    const size_t pitch = size_t(pl.N);
-    switch (pl.N) {
-#define RF_X(L, K)                                                                         \
-    case (L << K):                                                                         \
-        if (inverse) launch_plain<RfShape<L, K, false>, true>(pl, data_dev, nrows, pitch, stream); \
-        else launch_plain<RfShape<L, K, false>, false>(pl, data_dev, nrows, pitch, stream);        \
-        break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                                        \
-    case 2 * (L << K):                                                                                    \
-        if (inverse) launch_plain<RfShape2<RfShape<L, K, false>>, true>(pl, data_dev, nrows, pitch, stream);     \
-        else launch_plain<RfShape2<RfShape<L, K, false>>, false>(pl, data_dev, nrows, pitch, stream);            \
-        break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rowfft_plain_family<true>(pl, data_dev, nrows, inverse, stream, pitch);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -322,9 +301,8 @@ template <class S1>
 static void launch_a2b2(const RowFFTPlan &pl, const double2 *A, double2 *B, const int *rowmap, int nrows, int nu, int ny,
                         size_t apitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false;
     constexpr bool STASH = rf_stash_slots<S1>() > 0;
-    rf_allow_lds(&k_rowfft_a2b2<S1, STASH>, &attr);
+    rf_allow_lds(&k_rowfft_a2b2<S1, STASH>);
     hipLaunchKernelGGL((k_rowfft_a2b2<S1, STASH>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S1::T),
                        size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double), stream, pl.twiddle, A, B, rowmap,
                        nrows, nu, ny, apitch, astride, bstride, colruns);
@@ -333,9 +311,8 @@ template <class S1>
 static void launch_b2a2(const RowFFTPlan &pl, const double2 *B, double2 *A, const int *rowmap, int nrows, int nu, int ny,
                         size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false;
     constexpr bool STASH = rf_stash_slots<S1>() > 0;
-    rf_allow_lds(&k_rowfft_b2a2<S1, STASH>, &attr);
+    rf_allow_lds(&k_rowfft_b2a2<S1, STASH>);
     hipLaunchKernelGGL((k_rowfft_b2a2<S1, STASH>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S1::T),
                        size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double), stream, pl.twiddle, B, A, rowmap,
                        nrows, nu, ny, apitch, tpitch, astride, bstride, colruns);
@@ -345,8 +322,7 @@ template <class S>
 static void launch_a2b(const RowFFTPlan &pl, const double2 *A, double2 *B, const int *rowmap, int nrows, int nu, int ny,
                        size_t apitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false;
-    rf_allow_lds(&k_rowfft_a2b<S>, &attr);
+    rf_allow_lds(&k_rowfft_a2b<S>);
     // (grid.x a multiple of 8: a plane's workgroups then start on XCD 0 like the first plane's -- rowmap relies on it)
     hipLaunchKernelGGL((k_rowfft_a2b<S>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S::T), size_t(S::LDS_BYTES),
                        stream, pl.twiddle, A, B, rowmap, nrows, nu, ny, apitch, astride, bstride, colruns);
@@ -355,8 +331,7 @@ template <class S>
 static void launch_b2a(const RowFFTPlan &pl, const double2 *B, double2 *A, const int *rowmap, int nrows, int nu, int ny,
                        size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    static bool attr = false;
-    rf_allow_lds(&k_rowfft_b2a<S>, &attr);
+    rf_allow_lds(&k_rowfft_b2a<S>);
     hipLaunchKernelGGL((k_rowfft_b2a<S>), dim3(uint32_t((nrows + 7) / 8 * 8), uint32_t(nplanes)), dim3(S::T), size_t(S::LDS_BYTES),
                        stream, pl.twiddle, B, A, rowmap, nrows, nu, ny, apitch, tpitch, astride, bstride, colruns);
 }
@@ -364,36 +339,28 @@ static void launch_b2a(const RowFFTPlan &pl, const double2 *B, double2 *A, const
 void rowfft_a2b(const RowFFTPlan &pl, const double2 *A_dev, double2 *B_dev, const int *rowmap_dev, int nrows, int nu, int ny,
                 size_t apitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
-    switch (pl.N) {
-#define RF_X(L, K)                                                                       \
-    case (L << K): launch_a2b<RfShape<L, K>>(pl, A_dev, B_dev, rowmap_dev, nrows, nu, ny, apitch, nplanes, astride, bstride, colruns, stream); break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                       \
-    case 2 * (L << K): launch_a2b2<RfShape<L, K, false>>(pl, A_dev, B_dev, rowmap_dev, nrows, nu, ny, apitch, nplanes, astride, bstride, colruns, stream); break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rf_launch_at(pl.N, [&](auto len) {
+        if constexpr (len.doubled)
+            launch_a2b2<RfShape<len.LEAD, len.K, false>>(pl, A_dev, B_dev, rowmap_dev, nrows, nu, ny, apitch, nplanes, astride, bstride,
+                                                         colruns, stream);
+        else
+            launch_a2b<RfShape<len.LEAD, len.K>>(pl, A_dev, B_dev, rowmap_dev, nrows, nu, ny, apitch, nplanes, astride, bstride, colruns,
+                                                 stream);
+    });
 }
 
 void rowfft_b2a(const RowFFTPlan &pl, const double2 *B_dev, double2 *A_dev, const int *rowmap_dev, int nrows, int nu, int ny,
                 size_t apitch, int tpitch, int nplanes, size_t astride, size_t bstride, const int4 *colruns, hipStream_t stream)
 {
     PFB_REQUIRE(tpitch > 0, "rowfft_b2a reads the transposed plane Bt (tpitch %d): the fused pad kernel must store it", tpitch);
-    switch (pl.N) {
-#define RF_X(L, K)                                                                       \
-    case (L << K): launch_b2a<RfShape<L, K>>(pl, B_dev, A_dev, rowmap_dev, nrows, nu, ny, apitch, tpitch, nplanes, astride, bstride, colruns, stream); break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                       \
-    case 2 * (L << K): launch_b2a2<RfShape<L, K, false>>(pl, B_dev, A_dev, rowmap_dev, nrows, nu, ny, apitch, tpitch, nplanes, astride, bstride, colruns, stream); break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rf_launch_at(pl.N, [&](auto len) {
+        if constexpr (len.doubled)
+            launch_b2a2<RfShape<len.LEAD, len.K, false>>(pl, B_dev, A_dev, rowmap_dev, nrows, nu, ny, apitch, tpitch, nplanes, astride,
+                                                         bstride, colruns, stream);
+        else
+            launch_b2a<RfShape<len.LEAD, len.K>>(pl, B_dev, A_dev, rowmap_dev, nrows, nu, ny, apitch, tpitch, nplanes, astride, bstride,
+                                                 colruns, stream);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1192,16 +1159,15 @@ static void launch_crop2(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t
                          const FusedPlanes &planes, int do_w, bool first, double *accT_dev, const FusedFinal &fin,
                          hipStream_t stream)
 {
-    static bool attr = false, attr_sep = false;
     constexpr bool STASH = rf_stash_slots<S1>() > 0;
     const size_t lds = size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double);
     if (planes.sep && planes.nsc > 0 && do_w) {
-        rf_allow_lds(&k_fused_fft_crop2<S1, STASH, 2>, &attr_sep);
+        rf_allow_lds(&k_fused_fft_crop2<S1, STASH, 2>);
         hipLaunchKernelGGL((k_fused_fft_crop2<S1, STASH, 2>), dim3(uint32_t(g.ny)), dim3(S1::T), lds, stream, pl.twiddle, g, occ_dev,
                            B_dev, bstride, planes, do_w, first ? 1 : 0, accT_dev, fin);
         return;
     }
-    rf_allow_lds(&k_fused_fft_crop2<S1, STASH, 0>, &attr);
+    rf_allow_lds(&k_fused_fft_crop2<S1, STASH, 0>);
     hipLaunchKernelGGL((k_fused_fft_crop2<S1, STASH, 0>), dim3(uint32_t(g.ny)), dim3(S1::T), lds, stream, pl.twiddle, g, occ_dev,
                        B_dev, bstride, planes, do_w, first ? 1 : 0, accT_dev, fin);
 }
@@ -1210,10 +1176,9 @@ static void launch_pad2(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t 
                         const FusedPrep &prep, const FusedPlanes &planes, int do_w, double2 *B_dev, size_t bstride,
                         hipStream_t stream)
 {
-    static bool attr = false;
     PFB_REQUIRE(prep.x == nullptr, "fused pad kernel of the doubled shapes needs a prepared image (fused_pad_takes_prep)");
     constexpr bool STASH = rf_stash_slots<S1>() > 0;
-    rf_allow_lds(&k_fused_pad_fft2<S1, STASH>, &attr);
+    rf_allow_lds(&k_fused_pad_fft2<S1, STASH>);
     hipLaunchKernelGGL((k_fused_pad_fft2<S1, STASH>), dim3(uint32_t(g.ny)), dim3(S1::T),
                        size_t(S1::LDS_BYTES) + size_t(rf_stash_slots<S1>()) * S1::T * sizeof(double), stream,
                        pl.twiddle, g, occ_dev, dcT_dev, prep, planes, do_w, B_dev, bstride);
@@ -1234,16 +1199,15 @@ static void launch_crop(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t 
                         size_t bstride, const FusedPlanes &planes, int do_w, bool first, double *accT_dev,
                         const FusedFinal &fin, hipStream_t stream)
 {
-    static bool attr = false, attr_sc = false;
     const bool row = fused_row_fits(S::LDS_BYTES, g.nx) && planes.kp > 1;
     const size_t lds = size_t(S::LDS_BYTES) + (row ? size_t(g.nx) * sizeof(double) : 0);
     if (planes.nsc > 0 && !planes.sep && do_w) {
-        rf_allow_lds(&k_fused_fft_crop<S, true>, &attr_sc);
+        rf_allow_lds(&k_fused_fft_crop<S, true>);
         hipLaunchKernelGGL((k_fused_fft_crop<S, true>), dim3(uint32_t(g.ny)), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, B_dev,
                            bstride, planes, do_w, first ? 1 : 0, row ? 1 : 0, accT_dev, fin);
         return;
     }
-    rf_allow_lds(&k_fused_fft_crop<S, false>, &attr);
+    rf_allow_lds(&k_fused_fft_crop<S, false>);
     hipLaunchKernelGGL((k_fused_fft_crop<S, false>), dim3(uint32_t(g.ny)), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, B_dev,
                        bstride, planes, do_w, first ? 1 : 0, row ? 1 : 0, accT_dev, fin);
 }
@@ -1253,7 +1217,6 @@ static void launch_pad(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t *
                        const FusedPrep &prep, const FusedPlanes &planes, int do_w, double2 *B_dev, size_t bstride,
                        hipStream_t stream)
 {
-    static bool attr = false, attr_sc = false;
     const bool row = fused_row_fits(S::LDS_BYTES, g.nx);
     PFB_REQUIRE(row || prep.x == nullptr, "fused pad kernel without an LDS row needs a prepared image (fused_pad_takes_prep)");
     const size_t lds = size_t(S::LDS_BYTES) + (row ? size_t(g.nx) * sizeof(double) : 0);
@@ -1264,27 +1227,25 @@ static void launch_pad(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t *
         // one workgroup per CU, a multiple of 64 of them (the row -> block map groups blocks in 64s)
         const uint32_t nwg = uint32_t(std::min<int>(g.ny, std::max(64, (ncu / 64) * 64)));
         const bool sc = planes.nsc > 0 && !planes.sep && do_w, beam = prep.beam != nullptr;
-        static bool ap[4] = {false, false, false, false};
-#define PFB_PADP(SCV, BV)                                                                                                        \
-    do {                                                                                                                         \
-        rf_allow_lds(&k_fused_pad_fft_p<S, SCV, BV>, &ap[(SCV ? 2 : 0) + (BV ? 1 : 0)]);                                          \
-        hipLaunchKernelGGL((k_fused_pad_fft_p<S, SCV, BV>), dim3(nwg), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, prep, planes, \
-                           do_w, B_dev);                                                                                         \
-    } while (0)
-        if (sc && beam) PFB_PADP(true, true);
-        else if (sc) PFB_PADP(true, false);
-        else if (beam) PFB_PADP(false, true);
-        else PFB_PADP(false, false);
-#undef PFB_PADP
+        auto launch = [&](auto scv, auto bv) {
+            constexpr bool SCV = decltype(scv)::value, BV = decltype(bv)::value;
+            rf_allow_lds(&k_fused_pad_fft_p<S, SCV, BV>);
+            hipLaunchKernelGGL((k_fused_pad_fft_p<S, SCV, BV>), dim3(nwg), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, prep, planes,
+                               do_w, B_dev);
+        };
+        if (sc && beam) launch(std::true_type{}, std::true_type{});
+        else if (sc) launch(std::true_type{}, std::false_type{});
+        else if (beam) launch(std::false_type{}, std::true_type{});
+        else launch(std::false_type{}, std::false_type{});
         return;
     }
     if (planes.nsc > 0 && !planes.sep && do_w) {
-        rf_allow_lds(&k_fused_pad_fft<S, true>, &attr_sc);
+        rf_allow_lds(&k_fused_pad_fft<S, true>);
         hipLaunchKernelGGL((k_fused_pad_fft<S, true>), dim3(uint32_t(g.ny)), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, dcT_dev,
                            prep, planes, do_w, row ? 1 : 0, B_dev, bstride);
         return;
     }
-    rf_allow_lds(&k_fused_pad_fft<S, false>, &attr);
+    rf_allow_lds(&k_fused_pad_fft<S, false>);
     hipLaunchKernelGGL((k_fused_pad_fft<S, false>), dim3(uint32_t(g.ny)), dim3(S::T), lds, stream, pl.twiddle, g, occ_dev, dcT_dev,
                        prep, planes, do_w, row ? 1 : 0, B_dev, bstride);
 }
@@ -1292,67 +1253,37 @@ static void launch_pad(const RowFFTPlan &pl, const FusedGeom &g, const uint8_t *
 void fused_fft_crop(const RowFFT &f, const FusedGeom &g, const uint8_t *occ_dev, const double2 *B_dev, size_t bstride,
                     const FusedPlanes &planes, int do_w, bool first, double *accT_dev, const FusedFinal &fin, hipStream_t stream)
 {
-    switch (f.pl.N) {
-#define RF_X(L, K)                                                                                                   \
-    case (L << K):                                                                                                   \
-        launch_crop<RfShape<L, K, false>>(f.pl, g, occ_dev, B_dev, bstride, planes, do_w, first, accT_dev, fin, stream); \
-        break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                                                        \
-    case 2 * (L << K):                                                                                                    \
-        launch_crop2<RfShape<L, K, false>>(f.pl, g, occ_dev, B_dev, bstride, planes, do_w, first, accT_dev, fin, stream);    \
-        break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", f.pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rf_launch_at(f.pl.N, [&](auto len) {
+        using S = RfShape<len.LEAD, len.K, false>;  // (doubled lengths: the half-length shape)
+        if constexpr (len.doubled) launch_crop2<S>(f.pl, g, occ_dev, B_dev, bstride, planes, do_w, first, accT_dev, fin, stream);
+        else launch_crop<S>(f.pl, g, occ_dev, B_dev, bstride, planes, do_w, first, accT_dev, fin, stream);
+    });
 }
 
 bool fused_doubled_stashes(const RowFFT &f)
 {
-    if (!f.ok || !f.pl.doubled) return false;
-    switch (f.pl.N) {
-#define RF_X(L, K) \
-    case 2 * (L << K): return rf_stash_slots<RfShape<L, K, false>>() > 0;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: return false;
-    }
+    bool stashes = false;
+    if (f.ok && f.pl.doubled)
+        rf_with_length(f.pl.N, [&](auto len) { stashes = rf_stash_slots<RfShape<len.LEAD, len.K, false>>() > 0; });
+    return stashes;
 }
 
 bool fused_pad_takes_prep(const RowFFT &f, const FusedGeom &g)
 {
-    if (!f.ok || f.pl.doubled) return false;
-    switch (f.pl.N) {
-#define RF_X(L, K) \
-    case (L << K): return fused_row_fits(RfShape<L, K, false>::LDS_BYTES, g.nx);
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-        default: return false;
-    }
+    bool fits = false;
+    if (f.ok && !f.pl.doubled)
+        rf_with_length(f.pl.N, [&](auto len) { fits = fused_row_fits(RfShape<len.LEAD, len.K, false>::LDS_BYTES, g.nx); });
+    return fits;
 }
 
 void fused_pad_fft(const RowFFT &f, const FusedGeom &g, const uint8_t *occ_dev, const double *dcT_dev, const FusedPrep &prep,
                    const FusedPlanes &planes, int do_w, double2 *B_dev, size_t bstride, hipStream_t stream)
 {
-    switch (f.pl.N) {
-#define RF_X(L, K)                                                                                           \
-    case (L << K):                                                                                           \
-        launch_pad<RfShape<L, K, false>>(f.pl, g, occ_dev, dcT_dev, prep, planes, do_w, B_dev, bstride, stream); \
-        break;
-        RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, K)                                                                                                      \
-    case 2 * (L << K):                                                                                                  \
-        launch_pad2<RfShape<L, K, false>>(f.pl, g, occ_dev, dcT_dev, prep, planes, do_w, B_dev, bstride, stream);          \
-        break;
-        RF_FOR_SHAPES2(RF_X)
-#undef RF_X
-        default: PFB_REQUIRE(false, "row length %d is not supported by the hand-written FFT", f.pl.N);
-    }
-    PFB_HIP(hipGetLastError());
+    rf_launch_at(f.pl.N, [&](auto len) {
+        using S = RfShape<len.LEAD, len.K, false>;  // (doubled lengths: the half-length shape)
+        if constexpr (len.doubled) launch_pad2<S>(f.pl, g, occ_dev, dcT_dev, prep, planes, do_w, B_dev, bstride, stream);
+        else launch_pad<S>(f.pl, g, occ_dev, dcT_dev, prep, planes, do_w, B_dev, bstride, stream);
+    });
 }
 
 }  // namespace pfbhip
@@ -1404,8 +1335,8 @@ int pfbhip_debug_rowfft_shape(double *data_host, int64_t n, int64_t nrows, int i
         synced(nullptr, [&] {
             PFB_HIP(hipMemcpy(d.p, data_host, tot * sizeof(double2), hipMemcpyHostToDevice));
             timer.start(nullptr);
-            if (family == 0) rowfft_plain(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
-            else rowfft_plain_nodual(plan.pl, d.p, int(nrows), inverse != 0, nullptr);
+            if (family == 0) rowfft_plain_family<true>(plan.pl, d.p, int(nrows), inverse != 0, nullptr, 0);
+            else rowfft_plain_family<false>(plan.pl, d.p, int(nrows), inverse != 0, nullptr, 0);
             timer.stop(nullptr);
             PFB_HIP(hipMemcpy(data_host, d.p, tot * sizeof(double2), hipMemcpyDeviceToHost));
         });

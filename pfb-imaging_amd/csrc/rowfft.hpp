@@ -31,22 +31,13 @@ namespace pfbhip {
     X(1, 10) X(1, 11) X(1, 12) X(1, 13) X(1, 14) X(3, 9) X(3, 10) X(3, 11) X(3, 12) X(5, 8) X(5, 9) X(5, 10) X(5, 11) \
     X(7, 8) X(7, 9) X(7, 10) X(7, 11) X(9, 7) X(9, 8) X(9, 9) X(9, 10) X(15, 7) X(15, 8) X(15, 9) X(15, 10)
 
-// complex elements per thread: 32 (T = N/32 threads per row) where that leaves room for TWO rows per
-// CU (registers: 10 waves of <= 168 VGPRs; LDS: 2 x N doubles), so that one row's butterflies overlap
-// the other row's LDS transposes; 16 otherwise.
-#ifndef RF_E32_MAXN
-#define RF_E32_MAXN 0
-#endif
-#ifndef RF_E32_MINN
-#define RF_E32_MINN 4096
-#endif
-#ifndef RF_XPAD
+// complex elements per thread of a plain shape (T = N/16 threads per row).  32 per thread (512 threads at 16384 points) was
+// measured and lost everywhere: > 220 VGPRs in the plain transform, more spills in the fused kernels.
+constexpr int RF_ELEMS = 16;
+// unused doubles behind every 16 LEAD positions of one exchange (RfShape::XPAD; why: rf_transpose)
 #define RF_XPAD 2
-#endif
-#ifndef RF_TWO_WG_MAXT
+// most threads of two workgroups that share a CU (RfShape::TWO_WG_SPLIT, with the measurements)
 #define RF_TWO_WG_MAXT 1024
-#endif
-constexpr int rf_elems(int N) { return (N >= RF_E32_MINN && N <= RF_E32_MAXN) ? 32 : 16; }
 
 // Doubled shapes N = 2 N1 (N1 = LEAD * 2^K from this list): one workgroup runs the N1-point transforms of the
 // even and the odd samples one after the other and combines them (X[k] = E[k] + w^k O[k], X[k + N1] = E[k] -
@@ -73,45 +64,59 @@ constexpr int rf_radix(int K, int p)
                   : 4;
 }
 
-inline bool rowfft_make_plan(int64_t N, RowFFTPlan *p)
+// One supported row length as a type (the idiom of dispatch.hpp: a generic lambda reads the constants off its argument).
+// doubled: n = 2 N1 with N1 = LEAD * 2^K, else n = LEAD * 2^K.
+template <int LEAD_, int K_, bool DOUBLED_>
+struct RfLength {
+    static constexpr int LEAD = LEAD_, K = K_;
+    static constexpr bool doubled = DOUBLED_;
+    static constexpr int n = (DOUBLED_ ? 2 : 1) * (LEAD_ << K_);
+};
+
+// f(RfLength) for every supported length: the ONE expansion of the two lists
+template <class F>
+void rf_for_each_length(F &&f)
 {
-#define RF_X(L, KK)                      \
-    if (N == (int64_t(L) << KK)) {       \
-        p->N = int(N);                   \
-        p->T = int(N) / rf_elems(int(N)); \
-        p->lead = L;                     \
-        p->K = KK;                       \
-        return true;                     \
-    }
+#define RF_X(L, KK) f(RfLength<L, KK, false>{});
     RF_FOR_SHAPES(RF_X)
 #undef RF_X
-#define RF_X(L, KK)                          \
-    if (N == 2 * (int64_t(L) << KK)) {       \
-        p->N = int(N);                       \
-        p->T = int(N / 2) / rf_elems(int(N / 2)); \
-        p->lead = L;                         \
-        p->K = KK + 1;                       \
-        p->doubled = 1;                      \
-        return true;                         \
-    }
+#define RF_X(L, KK) f(RfLength<L, KK, true>{});
     RF_FOR_SHAPES2(RF_X)
 #undef RF_X
-    return false;
+}
+
+// f(RfLength) for the length equal to N; false (and no call) if N is not supported
+template <class F>
+bool rf_with_length(int64_t N, F &&f)
+{
+    bool found = false;
+    rf_for_each_length([&](auto len) {
+        if (!found && N == len.n) {
+            found = true;
+            f(len);
+        }
+    });
+    return found;
+}
+
+inline bool rowfft_make_plan(int64_t N, RowFFTPlan *p)
+{
+    return rf_with_length(N, [&](auto len) {
+        p->N = len.n;
+        p->T = (len.LEAD << len.K) / RF_ELEMS;
+        p->lead = len.LEAD;
+        p->K = len.K + (len.doubled ? 1 : 0);
+        if (len.doubled) p->doubled = 1;
+    });
 }
 
 // smallest supported row length >= x (0 if none)
 inline int64_t rowfft_size_at_least(double x)
 {
     int64_t best = 0;
-#define RF_X(L, KK)                                                       \
-    if (double(int64_t(L) << KK) >= x - 1e-9 && (best == 0 || (int64_t(L) << KK) < best)) best = int64_t(L) << KK;
-    RF_FOR_SHAPES(RF_X)
-#undef RF_X
-#define RF_X(L, KK)                                                               \
-    if (double(2 * (int64_t(L) << KK)) >= x - 1e-9 && (best == 0 || 2 * (int64_t(L) << KK) < best)) \
-        best = 2 * (int64_t(L) << KK);
-    RF_FOR_SHAPES2(RF_X)
-#undef RF_X
+    rf_for_each_length([&](auto len) {
+        if (double(len.n) >= x - 1e-9 && (best == 0 || len.n < best)) best = len.n;
+    });
     return best;
 }
 
@@ -562,10 +567,10 @@ __device__ __forceinline__ void rf_first_odd(double (&re)[E], double (&im)[E], i
 }
 
 // Compile-time description of one supported row length.
-template <int LEAD_, int K_, bool ALLOW_DUAL = true, int E_ = 0, bool ALLOW_SPLIT = true>
+template <int LEAD_, int K_, bool ALLOW_DUAL = true, bool ALLOW_SPLIT = true>
 struct RfShape {
     static constexpr int LEAD = LEAD_, K = K_;
-    static constexpr int N = LEAD_ << K_, E = E_ > 0 ? E_ : rf_elems(N), T = N / E;
+    static constexpr int N = LEAD_ << K_, E = RF_ELEMS, T = N / E;
     static constexpr bool DOUBLED = false;
     static constexpr int NSLOT = LEAD_ > 1 ? ((E + LEAD_ - 1) / LEAD_) * LEAD_ : E;  // load-functor slots per row
     static constexpr int NP = rf_npass(K_);
@@ -573,7 +578,7 @@ struct RfShape {
     // too, PADDED per exchange: one spare double per 16 positions in the first exchange (writes of stride 16 -> 17) and 16 per
     // 256 in the second (the 16-lane groups of a write land 256 apart -> 272); both need N / 16 spare doubles per component.
     // Smaller ones (T not a multiple of 256) keep the xor swizzle.
-    static constexpr bool SWZ = LEAD_ == 1 && (N < 4096 || E_ > 16);
+    static constexpr bool SWZ = LEAD_ == 1 && N < 4096;
     static constexpr int RLAST = rf_radix(K_, NP - 1);
     // Two workgroups per CU where they fit (LDS: 2 x N doubles when the row moves one component at a time; threads: 2 T <=
     // RF_TWO_WG_MAXT = 1024, i.e. 4 waves per SIMD and 128 VGPRs): the exchanges are barrier-separated phases in which the whole
@@ -582,15 +587,11 @@ struct RfShape {
     // the second workgroup means 5 waves per SIMD and 96 VGPRs: the plain transform fits without spills but gains nothing
     // (0.343 -> 0.350 ms, it is HBM-bound at 4.7 TB/s), the transposing store spills (0.43 -> 0.65 ms) and the fused pad kernel
     // loses its LDS image row (1.90 -> 2.34 ms) -- RF_TWO_WG_MAXT stays at 1024.
-    static constexpr int NLX = N + ((LEAD_ == 1 && N >= 4096 && E == 16) ? N / 16 : 0);  // (component length before XPAD is known)
-    static constexpr bool TWO_WG_SPLIT = ALLOW_DUAL && ALLOW_SPLIT && E == 16 && 2 * NLX * int(sizeof(double)) <= 160 * 1024 && 2 * T <= RF_TWO_WG_MAXT;
-#ifdef RF_NO_DUAL
-    static constexpr bool DUAL = false;
-#else
-    static constexpr bool DUAL = ALLOW_DUAL && E == 16 && NLX * 16 <= 160 * 1024 && !(TWO_WG_SPLIT && 2 * NLX * 16 > 160 * 1024);
-#endif
+    static constexpr int NLX = N + ((LEAD_ == 1 && N >= 4096) ? N / 16 : 0);  // (component length before XPAD is known)
+    static constexpr bool TWO_WG_SPLIT = ALLOW_DUAL && ALLOW_SPLIT && 2 * NLX * int(sizeof(double)) <= 160 * 1024 && 2 * T <= RF_TWO_WG_MAXT;
+    static constexpr bool DUAL = ALLOW_DUAL && NLX * 16 <= 160 * 1024 && !(TWO_WG_SPLIT && 2 * NLX * 16 > 160 * 1024);
     // unused doubles behind every 16 LEAD positions of the exchange after the first radix-16 pass (see rf_transpose)
-    static constexpr int XPAD = (!DUAL && LEAD_ > 1 && K_ >= 8 && E == 16) ? RF_XPAD : 0;
+    static constexpr int XPAD = (!DUAL && LEAD_ > 1 && K_ >= 8) ? RF_XPAD : 0;
     // padding (doubles per block of R Ns positions) of the exchange behind a radix-R pass at sub-length Ns
     static constexpr int xpad(int R, int Ns)
     {

@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev helper: compile rowfft.hip and list kernels with their VGPR count / spills
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -I/opt/rocm/include $RF_DEFS -c rowfft.hip -o build/rowfft.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -I/opt/rocm/include -c rowfft.hip -o build/rowfft.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re
 name=None
 for l in sys.stdin:
