@@ -206,6 +206,25 @@ int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, dou
 int pfbhip_gridder_dirty2vis_dev(pfbhip_gridder *g, const double *dirty_dev, const double *wgt_host /* or NULL */,
                                  double *vis_host /* (nrow,nchan,2) */);
 
+/* ---- one correlation of a device-resident chunk: row-ordered (nrow, nchan) DEVICE arrays in the caller's row order, e.g. a
+ * contiguous slice of the correlation-first cube pfbhip_weight_data_dev leaves in HBM.  Nothing is uploaded; every call
+ * returns with the plan's stream idle. */
+/* vis2dirty (src/pfb_imaging/operators/gridder.py:587-614): pfbhip_gridder_vis2dirty_dev without the upload.  vis_dev complex128,
+ * wgt_dev float64 or NULL (unit weights), dirty_dev (nx, ny). */
+int pfbhip_gridder_vis2dirty_rows_dev(pfbhip_gridder *g, const double *vis_dev, const double *wgt_dev /* or NULL */,
+                                      double *dirty_dev);
+/* The PSF (operators/gridder.py:616-655; grid_partition :878-906): vis2dirty of the PSF visibilities for the plan's own centre --
+ * ones at the phase centre, else the phase ramp of :617-622 -- formed inside the sort kernel: no (nrow, nchan) complex
+ * array exists anywhere.  psf_dev has the plan's image shape. */
+int pfbhip_gridder_psf_rows_dev(pfbhip_gridder *g, const double *wgt_dev /* or NULL */, double *psf_dev);
+/* pfbhip_gridder_set_weights (operators/hessian.py:50-89) from a resident array. */
+int pfbhip_gridder_set_weights_dev(pfbhip_gridder *g, const double *wgt_dev /* or NULL */);
+/* Un-weighted model visibilities and the residual visibilities (operators/gridder.py:480-507).  minuend_dev NULL: vis = R dirty,
+ * 0 on masked samples.  Else vis = minuend - R dirty on unmasked samples and vis = minuend on masked ones, in the one pass
+ * that un-sorts; vis_dev may be minuend_dev. */
+int pfbhip_gridder_dirty2vis_rows_dev(pfbhip_gridder *g, const double *dirty_dev, const double *minuend_dev /* or NULL */,
+                                      double *vis_dev);
+
 /* Per-stage device timing (HIP events on the handle's stream).  Stages:
  * 0 grid (scatter kernel)  1 degrid (gather kernel)  2 fft_rows (plain row-FFT passes: first axis, and the
  * second axis on the rocFFT fallback)  3 pad (B -> A transpose; + pad/w-screen kernel on the fallback)
@@ -360,6 +379,24 @@ int pfbhip_imaging_weights(const double *uvw_host, const double *freq_host, cons
                            int64_t ncorr, int64_t nrow, int64_t nchan, int64_t nx, int64_t ny, double cell_x, double cell_y,
                            double usign, double vsign, double robust, double filter_level, int64_t npix_super,
                            double *counts_out_host);
+
+/* ---- a device-resident visibility chunk (csrc/vischunk.hip): wgt_dev (ncorr, nvis) float64, mask_dev (nvis) uint8, nvis = nrow *
+ * nchan.  Reductions are two-stage (block partials, one final block, fixed trees, no float atomics): bit-reproducible. */
+/* WSUM of operators/gridder.py:584: wsum_host[c] = wgt[c, mask != 0].sum(). */
+int pfbhip_chunk_wsum_dev(const double *wgt_dev, const uint8_t *mask_dev, int64_t ncorr, int64_t nvis, double *wsum_host);
+/* The l2 reweighting of operators/gridder.py:509-532 on resident residual visibilities resvis_dev (ncorr, nvis) complex128: per
+ * correlation ressq = wgtp |r|^2 (wgtp_dev (ncorr, nvis), or the scalar when it is NULL), ovar_c = sum_{mask > 0} ressq /
+ * sum(mask), wgt *= (dof + 2) / (dof + ressq / ovar_c) on every sample.  ovar_host (ncorr, may be NULL) receives ovar.  When
+ * any ovar_c is zero (or the mask is empty) the call fails with PFBHIP_ERR_INVALID and the weights are untouched. */
+int pfbhip_chunk_l2_reweight_dev(const double *resvis_dev, const double *wgtp_dev /* or NULL */, double wgtp_scalar,
+                                 const uint8_t *mask_dev, double *wgt_dev, int64_t ncorr, int64_t nvis, double dof,
+                                 double *ovar_host);
+/* pfbhip_imaging_weights (operators/gridder.py:534-576) with the mask and the weights already resident: the same pipeline,
+ * wgt_dev updated in place (untouched when every count is zero); uvw and freq come from the host. */
+int pfbhip_imaging_weights_dev(const double *uvw_host, const double *freq_host, const uint8_t *mask_dev, double *wgt_dev,
+                               int64_t ncorr, int64_t nrow, int64_t nchan, int64_t nx, int64_t ny, double cell_x, double cell_y,
+                               double usign, double vsign, double robust, double filter_level, int64_t npix_super,
+                               double *counts_out_host /* or NULL */);
 
 /* ---- wavelet dictionary Psi and the l21 / positivity proxes ---------------- */
 /*

@@ -142,6 +142,8 @@ SYMBOLS = (
     "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
     "pfbhip_beam_regrid", "pfbhip_beam_rotate_mean",
     "pfbhip_weight_data", "pfbhip_weight_data_sp", "pfbhip_weight_data_dev", "pfbhip_debug_copy16",
+    "pfbhip_gridder_vis2dirty_rows_dev", "pfbhip_gridder_psf_rows_dev", "pfbhip_gridder_set_weights_dev",
+    "pfbhip_gridder_dirty2vis_rows_dev", "pfbhip_chunk_wsum_dev", "pfbhip_chunk_l2_reweight_dev", "pfbhip_imaging_weights_dev",
 )
 
 _lib = None
@@ -363,6 +365,20 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+def dev_ptr(a, offset=0, count=None):
+    """void* of element ``offset`` of the DeviceArray ``a`` (None -> NULL): how a contiguous slice of a resident cube -- one
+    correlation of a correlation-first chunk -- is handed to the library.  ``count`` elements from there must lie inside."""
+    if a is None:
+        return None
+    offset = int(offset)
+    size = a.nbytes // a.dtype.itemsize
+    if offset < 0 or offset + (0 if count is None else int(count)) > size:
+        raise ValueError(f"elements [{offset}, {offset + (count or 0)}) are outside a DeviceArray of {size}")
+    if not a.ptr.value and size:
+        raise ValueError("the DeviceArray has been freed")
+    return vp((a.ptr.value or 0) + offset * a.dtype.itemsize)
 
 
 _ro_memo = {}  # (address, shape, dtype) -> (array kept alive, key, sample): read-only inputs only

@@ -228,6 +228,70 @@ __global__ void k_permute_out(MapArgs m, const uint32_t *src, int64_t nactive, c
     vis[i] = v;
 }
 
+// k_permute_in whose visibilities are the PSF's, generated here: sval[j] = wgt[src] * exp(2 pi i (+-ramp + shift phase)), where
+// ramp = (u x0 + v y0 - w (n0 - 1)) freq / c in the caller's unflipped uvw (operators/gridder.py::psf_visibilities; `ramp` is 0
+// at the phase centre, where they are ones) and the sign is that of the Hermitian fold.  The ramp does NOT cancel against
+// shift_phase: flip_u / flip_v enter shift_phase twice (u and lshift both carry the sign), so its u and v terms are
+// +(u x0 + v y0) as well and the two add; the w terms, -w (n0 - 1) and +w nshift, have the same sign too.  Both phases
+// go through one reduction and one sincospi.
+__global__ void k_permute_in_psf(MapArgs m, const uint32_t *src, int64_t nactive, const double *wgt, int ramp, double x0, double y0,
+                                 double nm1, int shifting, double ls, double ms, double ns, double2 *sval)
+{
+    int64_t j = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (j >= nactive) return;
+    uint32_t s = src[j];
+    uint32_t i = s & 0x7FFFFFFFu;
+    double ph = 0.0;
+    if (ramp) {
+        int64_t row = i / uint32_t(m.nchan);
+        int chan = int(i - row * m.nchan);
+        ph = (m.uvw[3 * row] * x0 + m.uvw[3 * row + 1] * y0 - m.uvw[3 * row + 2] * nm1) * m.fc[chan];
+        if (s >> 31) ph = -ph;
+    }
+    if (shifting) {
+        VisPos p = vis_position(m, i);
+        ph += p.u * ls + p.v * ms + p.w * ns;
+    }
+    double2 v = make_double2(wgt ? wgt[i] : 1.0, 0.0);
+    if (ramp || shifting) {
+        double c, sn;
+        ph -= rint(ph);
+        sincospi(2.0 * ph, &sn, &c);
+        v.y = v.x * sn;
+        v.x = v.x * c;
+    }
+    sval[j] = v;
+}
+
+// k_permute_out into a row-ordered device array that is written exactly once per sample, in one pass over
+// max(nactive, nvis) threads: thread t < nactive un-sorts visibility t (vis[src] = R dirty, or minuend[src] - R dirty), thread
+// t < nvis settles sample t when the mask drops it (0, or minuend[t]).  The two sets of samples are disjoint -- the sort
+// keeps exactly the samples with mask != 0 -- and every sample is read and written by one thread, so vis may be minuend.
+__global__ void k_permute_out_rows(MapArgs m, const uint32_t *src, int64_t nactive, const double2 *sacc, const double2 *minuend,
+                                   int shifting, double ls, double ms, double ns, double2 *vis)
+{
+    int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t < m.nvis && m.mask && !m.mask[t]) vis[t] = minuend ? minuend[t] : make_double2(0.0, 0.0);
+    if (t >= nactive) return;
+    uint32_t s = src[t];
+    uint32_t i = s & 0x7FFFFFFFu;
+    double2 v = sacc[t];
+    if (shifting) {
+        double c, sn;
+        shift_phase(m, i, ls, ms, ns, &c, &sn);
+        double re = v.x * c + v.y * sn, im = -v.x * sn + v.y * c;
+        v.x = re;
+        v.y = im;
+    }
+    if (s >> 31) v.y = -v.y;
+    if (minuend) {
+        double2 a = minuend[i];
+        v.x = a.x - v.x;
+        v.y = a.y - v.y;
+    }
+    vis[i] = v;
+}
+
 __global__ void k_gather_f64(const uint32_t *src, int64_t nactive, const double *in, double *out)
 {
     int64_t j = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
@@ -2215,14 +2279,34 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 // pfbhip_gridder::upload / download differ
 // ---------------------------------------------------------------------------------------
 
-// sval = the uploaded visibilities (d_vis) in tile-sorted order, weighted with d_wgt if `weighted`, phase-shifted
-static void permute_in(pfbhip_gridder *g, bool weighted)
+// sval = the caller's row-ordered (nrow, nchan) device arrays in tile-sorted order, weighted with wgt_dev unless it is NULL,
+// phase-shifted
+static void permute_in_rows(pfbhip_gridder *g, const double2 *vis_dev, const double *wgt_dev)
 {
     if (g->info.nactive)
         hipLaunchKernelGGL(k_permute_in, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->map, g->d_src.p, g->info.nactive,
-                           g->d_vis.p, weighted ? g->d_wgt.p : nullptr, int(g->shifting), g->info.lshift, g->info.mshift,
-                           g->info.nshift, g->d_sval.p);
+                           vis_dev, wgt_dev, int(g->shifting), g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
     PFB_HIP(hipGetLastError());
+}
+
+// the same of the uploaded visibilities (d_vis), weighted with d_wgt if `weighted`
+static void permute_in(pfbhip_gridder *g, bool weighted)
+{
+    permute_in_rows(g, g->d_vis.p, weighted ? g->d_wgt.p : nullptr);
+}
+
+// body(), then a wait for st -- also when body() throws: synced() of abi_scope.hpp, which this file cannot include (it
+// defines its own StageTimer and blocks1d).  Argument checks stay in front of it.
+template <class F>
+static void stream_scope(hipStream_t st, F &&body)
+{
+    try {
+        body();
+    } catch (...) {
+        (void)hipStreamSynchronize(st);
+        throw;
+    }
+    PFB_HIP(hipStreamSynchronize(st));
 }
 
 // the uploaded visibilities -> dirty image (device)
@@ -2477,6 +2561,75 @@ int pfbhip_gridder_dirty2vis_dev(pfbhip_gridder *g, const double *dirty_dev, con
 int pfbhip_gridder_set_weights(pfbhip_gridder *g, const double *wgt_host)
 {
     return guarded([&] { set_weights_host(g, wgt_host); });
+}
+
+// ---- row-ordered DEVICE arrays: one correlation of a resident (ncorr, nrow, nchan) chunk (vischunk.hip).  Each entry checks
+// its arguments, then enqueues everything inside one stream_scope: it returns with the plan's stream idle. ----
+
+// vis2dirty of gridder.py:587-614 of the reference: vis2dirty_device without upload_vis_wgt
+int pfbhip_gridder_vis2dirty_rows_dev(pfbhip_gridder *g, const double *vis_dev, const double *wgt_dev, double *dirty_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(g && dirty_dev && (vis_dev || g->nvis == 0), "NULL argument");
+        stream_scope(g->stream, [&] {
+            permute_in_rows(g, reinterpret_cast<const double2 *>(vis_dev), wgt_dev);
+            g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, dirty_dev);
+        });
+    });
+}
+
+// The PSF of gridder.py:616-655 for the plan's own centre: the visibilities (ones, or the phase ramp of :617-622) are formed
+// inside the permute kernel, see k_permute_in_psf.
+int pfbhip_gridder_psf_rows_dev(pfbhip_gridder *g, const double *wgt_dev, double *psf_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(g && psf_dev, "NULL argument");
+        const double x0 = g->uprm.center_x, y0 = g->uprm.center_y;
+        PFB_REQUIRE(x0 * x0 + y0 * y0 < 1.0, "phase centre (%g, %g) is not on the sphere", x0, y0);
+        const double nm1 = std::sqrt(1.0 - x0 * x0 - y0 * y0) - 1.0;
+        stream_scope(g->stream, [&] {
+            if (g->info.nactive)
+                hipLaunchKernelGGL(k_permute_in_psf, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->map, g->d_src.p,
+                                   g->info.nactive, wgt_dev, int(x0 != 0.0 || y0 != 0.0), x0, y0, nm1, int(g->shifting), g->info.lshift,
+                                   g->info.mshift, g->info.nshift, g->d_sval.p);
+            PFB_HIP(hipGetLastError());
+            g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, psf_dev);
+        });
+    });
+}
+
+// set_weights (the weights of hessian.py:50-89) from a resident array
+int pfbhip_gridder_set_weights_dev(pfbhip_gridder *g, const double *wgt_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(g, "NULL handle");
+        g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
+        stream_scope(g->stream, [&] {
+            if (g->info.nactive)
+                hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->d_src.p, g->info.nactive, wgt_dev,
+                                   g->d_swgt.p);
+            PFB_HIP(hipGetLastError());
+        });
+        g->weights_bound = true;
+    });
+}
+
+// The un-weighted model visibilities of gridder.py:480-507 and their subtraction from the data (:506-507) in the un-sort:
+// vis = R dirty (0 on masked samples), or vis = minuend - R dirty (minuend on masked samples); vis may be minuend.
+int pfbhip_gridder_dirty2vis_rows_dev(pfbhip_gridder *g, const double *dirty_dev, const double *minuend_dev, double *vis_dev)
+{
+    return guarded([&] {
+        PFB_REQUIRE(g && dirty_dev && (vis_dev || g->nvis == 0), "NULL argument");
+        stream_scope(g->stream, [&] {
+            ApplyState a{g->d_grid.p};
+            g->prepare_and_degrid(a, dirty_dev, nullptr, g->d_sacc.p);
+            if (g->nvis)
+                hipLaunchKernelGGL(k_permute_out_rows, blocks1d(std::max(g->info.nactive, g->nvis)), dim3(256), 0, g->stream, g->map,
+                                   g->d_src.p, g->info.nactive, g->d_sacc.p, reinterpret_cast<const double2 *>(minuend_dev),
+                                   int(g->shifting), g->info.lshift, g->info.mshift, g->info.nshift, reinterpret_cast<double2 *>(vis_dev));
+            PFB_HIP(hipGetLastError());
+        });
+    });
 }
 
 // The exact residual of one partition (gridder.py:962-1016 of the reference: dirty2vis of beam * model, vis2dirty with the

@@ -78,20 +78,23 @@ struct CellSetup {
     DevBuf<double> uvw, freq;
     DevBuf<uint8_t> mask;
     CellArgs a;
+    // mask_resident: mask_h is a device pointer already (a resident chunk's mask) and is used where it lies
     CellSetup(const double *uvw_h, const double *freq_h, const uint8_t *mask_h, int64_t nrow, int64_t nchan, int64_t nx,
-              int64_t ny, double cell_x, double cell_y, double usign, double vsign)
+              int64_t ny, double cell_x, double cell_y, double usign, double vsign, bool mask_resident = false)
     {
         PFB_REQUIRE(uvw_h && freq_h && mask_h, "NULL argument");
         PFB_REQUIRE(nrow >= 0 && nchan >= 1 && nx >= 1 && ny >= 1, "bad shapes");
         uvw.alloc(size_t(std::max<int64_t>(nrow, 1)) * 3);
         freq.alloc(size_t(nchan));
-        mask.alloc(size_t(std::max<int64_t>(nrow * nchan, 1)));
         PFB_HIP(hipMemcpy(uvw.p, uvw_h, size_t(nrow) * 3 * sizeof(double), hipMemcpyHostToDevice));
         PFB_HIP(hipMemcpy(freq.p, freq_h, size_t(nchan) * sizeof(double), hipMemcpyHostToDevice));
-        PFB_HIP(hipMemcpy(mask.p, mask_h, size_t(nrow * nchan), hipMemcpyHostToDevice));
+        if (!mask_resident) {
+            mask.alloc(size_t(std::max<int64_t>(nrow * nchan, 1)));
+            PFB_HIP(hipMemcpy(mask.p, mask_h, size_t(nrow * nchan), hipMemcpyHostToDevice));
+        }
         a.uvw = uvw.p;
         a.freq = freq.p;
-        a.mask = mask.p;
+        a.mask = mask_resident ? mask_h : mask.p;
         a.nvis = nrow * nchan;
         a.nchan = int(nchan);
         a.nx = nx;
@@ -205,6 +208,58 @@ static double dev_filter_extreme(double *a, int64_t n, double level)
     return med;
 }
 
+// The body pfbhip_imaging_weights and pfbhip_imaging_weights_dev share: counts of wgt_dev (ncorr, nvis) on the (nx, ny) grid of
+// `s` -> filter -> box sum -> Briggs scaling -> wgt_dev /= counts[cell], every array resident (null stream).  Returns whether
+// the weights were changed: all-zero counts leave them alone.  The final counts go to counts_out_host when it is given.
+static bool imaging_weights_resident(const CellSetup &s, double *wgt_dev, int64_t ncorr, double robust, double filter_level,
+                                     int64_t npix_super, double *counts_out_host)
+{
+    const int64_t nx = s.a.nx, ny = s.a.ny, per = nx * ny;
+    const size_t ncnt = size_t(ncorr) * size_t(per);
+    DevBuf<double> counts(ncnt), tmp(npix_super > 0 ? ncnt : 0);
+    PFB_HIP(hipMemset(counts.p, 0, counts.bytes()));
+    if (!s.a.nvis) {
+        if (counts_out_host) PFB_HIP(hipMemcpy(counts_out_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
+        return false;
+    }
+    hipLaunchKernelGGL(k_counts, s.grid(), dim3(256), 0, 0, s.a, wgt_dev, int(ncorr), counts.p);
+    PFB_HIP(hipGetLastError());
+    if (filter_level > 0.0) (void)dev_filter_extreme(counts.p, int64_t(ncnt), filter_level);
+    if (npix_super > 0) {
+        dim3 grid(uint32_t(ceil_div(int64_t(ncnt), 256)));
+        hipLaunchKernelGGL(k_box_sum_axis, grid, dim3(256), 0, 0, counts.p, ncorr, int(nx), int(ny), int(npix_super), 1, tmp.p);
+        hipLaunchKernelGGL(k_box_sum_axis, grid, dim3(256), 0, 0, tmp.p, ncorr, int(nx), int(ny), int(npix_super), 0, counts.p);
+        PFB_HIP(hipGetLastError());
+    }
+    // Briggs: counts <- counts * (5 * 10^-R)^2 * sum(c) / sum(c^2) + 1 when R > -2; all-zero counts leave the weights alone
+    DevBuf<double> sums(size_t(2 * ncorr));
+    PFB_HIP(hipMemset(sums.p, 0, sums.bytes()));
+    hipLaunchKernelGGL(k_sum_sumsq, dim3(uint32_t(std::min<int64_t>(ceil_div(per, 256), 1024)), uint32_t(ncorr)), dim3(256), 0, 0,
+                       counts.p, per, sums.p);
+    PFB_HIP(hipGetLastError());
+    std::vector<double> hs(size_t(2 * ncorr));
+    PFB_HIP(hipMemcpy(hs.data(), sums.p, sums.bytes(), hipMemcpyDeviceToHost));
+    bool any = false;
+    for (int64_t k = 0; k < ncorr; ++k) any = any || hs[size_t(2 * k + 1)] > 0.0;
+    if (any) {
+        if (robust > -2.0) {
+            const double numsqrt = 5.0 * std::pow(10.0, -robust);
+            std::vector<double> ssq(static_cast<size_t>(ncorr), 0.0);
+            for (int64_t k = 0; k < ncorr; ++k)
+                ssq[size_t(k)] = hs[size_t(2 * k + 1)] > 0.0 ? numsqrt * numsqrt * hs[size_t(2 * k)] / hs[size_t(2 * k + 1)] : 0.0;
+            DevBuf<double> d_ssq{size_t(ncorr)};
+            PFB_HIP(hipMemcpy(d_ssq.p, ssq.data(), d_ssq.bytes(), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_scale_plus_one, dim3(uint32_t(ceil_div(per, 256)), uint32_t(ncorr)), dim3(256), 0, 0, counts.p,
+                               per, d_ssq.p);
+            PFB_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_counts_divide, s.grid(), dim3(256), 0, 0, s.a, counts.p, int(ncorr), wgt_dev);
+        PFB_HIP(hipGetLastError());
+    }
+    if (counts_out_host) PFB_HIP(hipMemcpy(counts_out_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
+    return any;
+}
+
 }  // namespace pfbhip
 
 using namespace pfbhip;
@@ -223,52 +278,30 @@ int pfbhip_imaging_weights(const double *uvw_host, const double *freq_host, cons
     return guarded([&] {
         PFB_REQUIRE(wgt_host && ncorr >= 1 && npix_super >= 0, "bad arguments");
         CellSetup s(uvw_host, freq_host, mask_host, nrow, nchan, nx, ny, cell_x, cell_y, usign, vsign);
-        const int64_t per = nx * ny;
-        const size_t ncnt = size_t(ncorr) * size_t(per);
-        DevBuf<double> counts(ncnt), tmp(npix_super > 0 ? ncnt : 0);
-        PFB_HIP(hipMemset(counts.p, 0, counts.bytes()));
-        if (!s.a.nvis) {
-            if (counts_out_host) PFB_HIP(hipMemcpy(counts_out_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
-            return;
-        }
         DevBuf<double> wgt(size_t(ncorr) * size_t(s.a.nvis));
-        PFB_HIP(hipMemcpy(wgt.p, wgt_host, wgt.bytes(), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_counts, s.grid(), dim3(256), 0, 0, s.a, wgt.p, int(ncorr), counts.p);
-        PFB_HIP(hipGetLastError());
-        if (filter_level > 0.0) (void)dev_filter_extreme(counts.p, int64_t(ncnt), filter_level);
-        if (npix_super > 0) {
-            dim3 grid(uint32_t(ceil_div(int64_t(ncnt), 256)));
-            hipLaunchKernelGGL(k_box_sum_axis, grid, dim3(256), 0, 0, counts.p, ncorr, int(nx), int(ny), int(npix_super), 1, tmp.p);
-            hipLaunchKernelGGL(k_box_sum_axis, grid, dim3(256), 0, 0, tmp.p, ncorr, int(nx), int(ny), int(npix_super), 0, counts.p);
-            PFB_HIP(hipGetLastError());
-        }
-        // Briggs: counts <- counts * (5 * 10^-R)^2 * sum(c) / sum(c^2) + 1 when R > -2; all-zero counts leave the weights alone
-        DevBuf<double> sums(size_t(2 * ncorr));
-        PFB_HIP(hipMemset(sums.p, 0, sums.bytes()));
-        hipLaunchKernelGGL(k_sum_sumsq, dim3(uint32_t(std::min<int64_t>(ceil_div(per, 256), 1024)), uint32_t(ncorr)), dim3(256), 0, 0,
-                           counts.p, per, sums.p);
-        PFB_HIP(hipGetLastError());
-        std::vector<double> hs(size_t(2 * ncorr));
-        PFB_HIP(hipMemcpy(hs.data(), sums.p, sums.bytes(), hipMemcpyDeviceToHost));
-        bool any = false;
-        for (int64_t k = 0; k < ncorr; ++k) any = any || hs[size_t(2 * k + 1)] > 0.0;
-        if (any) {
-            if (robust > -2.0) {
-                const double numsqrt = 5.0 * std::pow(10.0, -robust);
-                std::vector<double> ssq(static_cast<size_t>(ncorr), 0.0);
-                for (int64_t k = 0; k < ncorr; ++k)
-                    ssq[size_t(k)] = hs[size_t(2 * k + 1)] > 0.0 ? numsqrt * numsqrt * hs[size_t(2 * k)] / hs[size_t(2 * k + 1)] : 0.0;
-                DevBuf<double> d_ssq{size_t(ncorr)};
-                PFB_HIP(hipMemcpy(d_ssq.p, ssq.data(), d_ssq.bytes(), hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_scale_plus_one, dim3(uint32_t(ceil_div(per, 256)), uint32_t(ncorr)), dim3(256), 0, 0, counts.p,
-                                   per, d_ssq.p);
-                PFB_HIP(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_counts_divide, s.grid(), dim3(256), 0, 0, s.a, counts.p, int(ncorr), wgt.p);
-            PFB_HIP(hipGetLastError());
+        if (s.a.nvis) PFB_HIP(hipMemcpy(wgt.p, wgt_host, wgt.bytes(), hipMemcpyHostToDevice));
+        if (imaging_weights_resident(s, wgt.p, ncorr, robust, filter_level, npix_super, counts_out_host))
             PFB_HIP(hipMemcpy(wgt_host, wgt.p, wgt.bytes(), hipMemcpyDeviceToHost));
+    });
+}
+
+// The same with the mask and the weights of a resident chunk (vischunk.py): nothing but uvw and freq goes up, nothing but the
+// counts (when asked for) comes down.  The pipeline runs on the null stream; the call returns with it idle.
+int pfbhip_imaging_weights_dev(const double *uvw_host, const double *freq_host, const uint8_t *mask_dev, double *wgt_dev,
+                               int64_t ncorr, int64_t nrow, int64_t nchan, int64_t nx, int64_t ny, double cell_x, double cell_y,
+                               double usign, double vsign, double robust, double filter_level, int64_t npix_super,
+                               double *counts_out_host)
+{
+    return guarded([&] {
+        PFB_REQUIRE(wgt_dev && ncorr >= 1 && npix_super >= 0, "bad arguments");
+        CellSetup s(uvw_host, freq_host, mask_dev, nrow, nchan, nx, ny, cell_x, cell_y, usign, vsign, true);
+        try {
+            (void)imaging_weights_resident(s, wgt_dev, ncorr, robust, filter_level, npix_super, counts_out_host);
+        } catch (...) {
+            (void)hipStreamSynchronize(nullptr);
+            throw;
         }
-        if (counts_out_host) PFB_HIP(hipMemcpy(counts_out_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
+        PFB_HIP(hipStreamSynchronize(nullptr));
     });
 }
 

@@ -7,6 +7,7 @@ Mirrors /root/reference/src/pfb_imaging/operators/gridder.py:
     grid_partition            :760-923   (dirty, PSF, PSFHAT, beam, wsum, imaging weights per partition)
     residual_from_partitions  :926-1016  (dirty - sum_p R_p^H W_p R_p (beam_p model))
     compute_residual_arrays   the arithmetic of compute_residual :1060-1117 on in-memory arrays
+    image_data_products_arrays / _chunk   the arithmetic of image_data_products :375-757 on host arrays / on a resident VisChunk
 The zarr / xarray / dask / ray plumbing around these (reading ``.xds``/``.dds`` stores, writing
 results) is orchestration and stays with the reference; partitions are accepted either as
 xarray-like objects (``part.UVW.values``, ``part.attrs``) or as plain dicts of numpy arrays.
@@ -571,6 +572,124 @@ def image_data_products_arrays(uvw, freq, vis, wgt, mask, nx, ny, nx_psf, ny_psf
             products["PSFPARSN"] = fitcleanbeam(psf, level=0.5, pixsize=1.0)
     elif do_psfpars:
         raise ValueError("do_psfpars needs do_psf: PSFPARSN is fitted to the PSF")
+    if do_beam:
+        products["BEAM"] = np.ones((ncorr, nx, ny)) if beam is None else np.asarray(beam)
+    outputs = {"residual": products["RESIDUAL"] if (do_residual and model is not None) else products.get("DIRTY"),
+               "wsum": wsum}
+    if do_psf:
+        outputs["psf"] = products["PSF"]
+    return products, outputs
+
+
+def image_data_products_chunk(chunk, nx, ny, nx_psf, ny_psf, cellx, celly, model=None, beam=None, robustness=None, l0=0.0, m0=0.0,
+                              nthreads=1, epsilon=1e-7, do_wgridding=True, l2_reweight_dof=None, wgtp=1.0, do_dirty=True,
+                              do_psf=True, do_residual=True, do_weight=True, do_beam=False, min_padding=1.7,
+                              filter_counts_level=5.0, npix_super=0, do_psfpars=False):
+    """:func:`image_data_products_arrays` of a chunk that is resident in HBM (:class:`~pfb_imaging_amd.vischunk.VisChunk`): the
+    same order of operations (gridder.py:375-757 of the reference), the same ``(products, outputs)`` and keys, no
+    per-correlation, per-product upload of visibilities and weights.
+
+    Model visibilities are degridded from the uploaded model straight into the residual visibilities
+    (``Gridder.dirty2vis_rows_dev`` with the chunk's visibilities as the minuend), which stay in HBM; the l2 reweighting and
+    the imaging weights run in place on ``chunk.wgt`` (so the chunk's weights are the products' ``WEIGHT`` afterwards, as the
+    reference's ``wgt`` is); ``WSUM`` is reduced on the device; ``DIRTY``, ``RESIDUAL`` and ``PSF`` are gridded from the
+    chunk's rows, the PSF's visibilities being formed inside the sort kernel.  One plan per output grid serves every
+    correlation.  What crosses PCIe: the model, once per correlation, up; the images and ``WSUM`` down; ``WEIGHT`` down only
+    with ``do_weight``; the PSF up again for ``PSFHAT`` (``fft.r2c`` takes host arrays) and ``PSFPARSN``.
+
+    ``do_noise`` is not offered: its random draw is the host's (``rng.standard_normal`` per correlation), so its visibilities
+    would be uploaded like the array path's; use :func:`image_data_products_arrays` for it.  ``wgtp`` is a scalar, a host
+    array or a float64 ``DeviceArray`` of the chunk's shape.
+
+    Device memory held: the chunk's ``ncorr * 24 + 1`` bytes per sample, ``ncorr * 16`` more per sample while a model is
+    given, one image per grid and the plans."""
+    from ..vischunk import VisChunk
+
+    if not isinstance(chunk, VisChunk):
+        raise TypeError(f"chunk must be a VisChunk, not {type(chunk).__name__}")
+    if do_psfpars and not do_psf:
+        raise ValueError("do_psfpars needs do_psf: PSFPARSN is fitted to the PSF")
+    ncorr = chunk.ncorr
+    if model is None:
+        if l2_reweight_dof:
+            raise ValueError("Requested l2 reweight but no model passed in. Perhaps transfer model from somewhere?")
+    else:
+        model = np.asarray(model)
+        if model.shape != (ncorr, nx, ny):
+            raise ValueError(f"model shape {model.shape} != {(ncorr, nx, ny)}")
+        if model.dtype.kind not in "fiu":
+            raise TypeError(f"model must be real, not {model.dtype}")
+    if beam is not None and np.shape(beam) != (ncorr, nx, ny):
+        raise ValueError(f"beam shape {np.shape(beam)} != {(ncorr, nx, ny)}")
+    chunk._open()
+    resize_thread_pool(nthreads)
+    flip_u, flip_v, flip_w, x0, y0 = wgridder_conventions(l0, m0)
+    uvw, freq, mask = chunk.uvw, chunk.freq, chunk.mask_host
+    common = dict(pixsize_x=cellx, pixsize_y=celly, center_x=x0, center_y=y0, epsilon=epsilon, flip_u=flip_u, flip_v=flip_v,
+                  flip_w=flip_w, do_wgridding=do_wgridding, divide_by_n=False, sigma_min=1.1, sigma_max=3.0)
+    products, g, res_dev, img_dev = {}, None, None, None
+    try:
+        if do_dirty or model is not None:
+            g = Gridder(uvw, freq, mask, npix_x=nx, npix_y=ny, **common)
+            img_dev = _lib.DeviceArray((nx, ny), np.float64)
+        if model is not None:
+            # residual visibilities = vis - R model, un-weighted (gridder.py:480-507), formed by the un-sort of the degrid
+            res_dev = _lib.DeviceArray((ncorr, chunk.nrow, chunk.nchan), np.complex128)
+            for c in range(ncorr):
+                off = chunk.corr_offset(c)
+                img_dev.upload(model[c])
+                g.dirty2vis_rows_dev(img_dev, res_dev, minuend_dev=chunk.vis, vis_offset=off, minuend_offset=off)
+        if l2_reweight_dof:
+            chunk.l2_reweight(res_dev, l2_reweight_dof, wgtp)
+        if robustness is not None:
+            nx_pad = int(np.ceil(min_padding * nx))
+            nx_pad += nx_pad % 2
+            ny_pad = int(np.ceil(min_padding * ny))
+            ny_pad += ny_pad % 2
+            chunk.imaging_weights(nx_pad, ny_pad, cellx, celly, robustness, filter_level=filter_counts_level,
+                                  npix_super=npix_super, usign=1.0 if flip_u else -1.0, vsign=1.0 if flip_v else -1.0)
+        if do_weight:
+            products.update(WEIGHT=chunk.weights(), UVW=uvw, MASK=mask)
+        wsum = chunk.wsum()
+        products["WSUM"] = wsum
+        if do_dirty:
+            products["DIRTY"] = _lib.result_empty((ncorr, nx, ny), np.float64)
+            for c in range(ncorr):
+                off = chunk.corr_offset(c)
+                g.vis2dirty_rows_dev(chunk.vis, chunk.wgt, img_dev, vis_offset=off, wgt_offset=off)
+                img_dev.download(products["DIRTY"][c])
+        if do_residual and model is not None:
+            products["MODEL"] = model
+            products["RESIDUAL"] = _lib.result_empty((ncorr, nx, ny), np.float64)
+            for c in range(ncorr):
+                off = chunk.corr_offset(c)
+                g.vis2dirty_rows_dev(res_dev, chunk.wgt, img_dev, vis_offset=off, wgt_offset=off)
+                img_dev.download(products["RESIDUAL"][c])
+    finally:
+        if g is not None:
+            g.close()
+        for d in (res_dev, img_dev):
+            if d is not None:
+                d.free()
+    if do_psf:
+        gp, psf_dev = Gridder(uvw, freq, mask, npix_x=nx_psf, npix_y=ny_psf, **common), None
+        try:
+            psf_dev = _lib.DeviceArray((nx_psf, ny_psf), np.float64)
+            psf = _lib.result_empty((ncorr, nx_psf, ny_psf), np.float64)
+            for c in range(ncorr):
+                gp.psf_rows_dev(chunk.wgt, psf_dev, wgt_offset=chunk.corr_offset(c))
+                psf_dev.download(psf[c])
+        finally:
+            gp.close()
+            if psf_dev is not None:
+                psf_dev.free()
+        products["PSF"] = psf
+        if nx_psf % 2 == 0 and ny_psf % 2 == 0:
+            products["PSFHAT"] = _fft.r2c(psf, axes=(1, 2), nthreads=nthreads, forward=True, inorm=0, centred=True)
+        else:
+            products["PSFHAT"] = _fft.r2c(ifftshift(psf, axes=(1, 2)), axes=(1, 2), nthreads=nthreads, forward=True, inorm=0)
+        if do_psfpars:
+            products["PSFPARSN"] = fitcleanbeam(psf, level=0.5, pixsize=1.0)
     if do_beam:
         products["BEAM"] = np.ones((ncorr, nx, ny)) if beam is None else np.asarray(beam)
     outputs = {"residual": products["RESIDUAL"] if (do_residual and model is not None) else products.get("DIRTY"),

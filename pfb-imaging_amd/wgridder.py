@@ -164,6 +164,46 @@ class Gridder:
         check(lib().pfbhip_gridder_set_weights(self._h, ptr(wgt)))
         self._weights_token = object()
 
+    # -- operators on row-ordered device arrays (one correlation of a resident chunk, vischunk.py) ----------------
+    # ``vis`` / ``wgt`` are complex128 / float64 DeviceArrays in the caller's row order; ``*_offset`` is the ELEMENT offset of
+    # the (nrow, nchan) slice inside them (``c * nrow * nchan`` for correlation c of a correlation-first cube).
+    def _rows(self, a, offset, dtype, name, optional=False):
+        if a is None and optional:
+            return None
+        if not isinstance(a, _lib.DeviceArray):
+            raise TypeError(f"{name} must be a DeviceArray, not {type(a).__name__}")
+        if a.dtype != np.dtype(dtype):
+            raise TypeError(f"{name} must be {np.dtype(dtype)}, not {a.dtype}")
+        return _lib.dev_ptr(a, offset, self.nrow * self.nchan)
+
+    def _img_dev(self, a, name):
+        if not isinstance(a, _lib.DeviceArray) or a.dtype != np.float64 or tuple(a.shape) != (self.nx, self.ny):
+            raise ValueError(f"{name} must be a float64 DeviceArray of shape {(self.nx, self.ny)}")
+        return a.ptr
+
+    def vis2dirty_rows_dev(self, vis_dev, wgt_dev, dirty_dev, vis_offset=0, wgt_offset=0):
+        """:meth:`vis2dirty` of visibilities and weights (or None) that are already in HBM, into ``dirty_dev``."""
+        v = self._rows(vis_dev, vis_offset, np.complex128, "vis_dev")
+        w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
+        check(lib().pfbhip_gridder_vis2dirty_rows_dev(self._h, v, w, self._img_dev(dirty_dev, "dirty_dev")))
+
+    def psf_rows_dev(self, wgt_dev, psf_dev, wgt_offset=0):
+        """``vis2dirty(psf_visibilities(...), wgt)`` for this plan's centre; the visibilities are formed on the device."""
+        w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
+        check(lib().pfbhip_gridder_psf_rows_dev(self._h, w, self._img_dev(psf_dev, "psf_dev")))
+
+    def set_weights_dev(self, wgt_dev, wgt_offset=0):
+        w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
+        check(lib().pfbhip_gridder_set_weights_dev(self._h, w))
+        self._weights_token = object()
+
+    def dirty2vis_rows_dev(self, dirty_dev, vis_dev, minuend_dev=None, vis_offset=0, minuend_offset=0):
+        """Un-weighted ``vis = R dirty`` (0 on masked samples), or with ``minuend_dev``: ``vis = minuend - R dirty`` on unmasked
+        samples and ``minuend`` on masked ones.  ``vis_dev`` may be ``minuend_dev`` (same offset)."""
+        v = self._rows(vis_dev, vis_offset, np.complex128, "vis_dev")
+        m = self._rows(minuend_dev, minuend_offset, np.complex128, "minuend_dev", optional=True)
+        check(lib().pfbhip_gridder_dirty2vis_rows_dev(self._h, self._img_dev(dirty_dev, "dirty_dev"), m, v))
+
     def hessian(self, x, beam=None, eta=0.0, wsum=0.0, out=None):
         """beam * R^H W R (beam * x) / wsum + eta x with the weights bound by :meth:`set_weights`; ``out`` (C-contiguous
         float64, not ``x``) receives the result in place.  A float32 ``x`` (with a float32 or no beam) takes the
