@@ -149,6 +149,10 @@ typedef struct pfbhip_gridder_info {
      * for the one-plane scatter at W = 14, 15 (16 x 16-cell frame on 4 x 16 lanes; the sort key then carries the 2 x 2 block) */
     int32_t scatter_block;
     int32_t reserved0;
+    /* gather kernel: 0 = diagonal-walk form (k_degrid_mp), 1 = row-walk form (k_degrid_rw: single-pass plans without ES-kernel
+     * w-planes), 2 = one-plane form (k_degrid_wd; Hessian applies of fused plans run k_hess_wd and launch no gather) */
+    int32_t gather_mode;
+    int32_t reserved1;
 } pfbhip_gridder_info;
 
 int pfbhip_gridder_create(const pfbhip_gridder_params *params, const double *uvw_host /* (nrow,3) */,

@@ -582,7 +582,7 @@ struct StageTimer {
 // Which kernels and transforms a plan runs.  Decided in three steps of plan creation (sort_key_sub in sort_by_tile,
 // choose_kernels once build_work_lists has the work lists, choose_transforms in setup_transforms once the row-FFT plans
 // exist; PlanBuild::path until then), read-only afterwards, and reported as info.scatter_mode / scatter_launches /
-// scatter_block / fft_mode (report_path).
+// scatter_block / gather_mode / fft_mode (report_path).
 enum class Scatter { Walk, Block, Rec, OnePlane };   // k_grid_mp, k_grid_blk, k_grid_rec, k_grid_wd
 enum class Gather { Walk, RowWalk, OnePlane };       // k_degrid_mp, k_degrid_rw, k_degrid_wd
 enum class FirstAxis { RocFFT, Rows, Transposing };  // rocFFT rows of A; rowfft_plain + k_a2b / k_b2a; rowfft_a2b / rowfft_b2a
@@ -1393,6 +1393,7 @@ static void report_path(const PlanPath &p, pfbhip_gridder_info &info)
     info.scatter_mode = p.scatter == Scatter::Walk ? 0 : (p.scatter == Scatter::Block ? 1 : 2);
     info.scatter_launches = p.coloured ? 4 : 1;
     info.scatter_block = p.bc;
+    info.gather_mode = p.gather == Gather::Walk ? 0 : (p.gather == Gather::RowWalk ? 1 : 2);
     info.fft_mode = (p.axis1 != FirstAxis::RocFFT ? 1 : 0) | (p.axis2 == SecondAxis::Fused ? 2 : 0) |
                     (p.axis2 == SecondAxis::Rows ? 4 : 0) | (p.axis1 == FirstAxis::Transposing ? 8 : 0);
 }
@@ -2464,7 +2465,7 @@ int pfbhip_gridder_get_info(const pfbhip_gridder *g, pfbhip_gridder_info *info)
         std::swap(info->nu, info->nv);          // report the caller's orientation (the plan holds the transposed problem)
         std::swap(info->lshift, info->mshift);
         info->device_bytes = g->device_bytes();
-        info->reserved0 = 0;
+        info->reserved0 = info->reserved1 = 0;
     });
 }
 

@@ -76,7 +76,7 @@ def gpu_plan(c):
 
 def check_plan(c, info):
     """the case runs the instantiation it claims"""
-    assert info["wmode"] == 2 and info["nplanes"] == 1, info
+    assert info["wmode"] == 2 and info["nplanes"] == 1 and info["gather_mode"] == 2, info
     assert info["W"] == c.W and info["nderiv"] == c.K and abs(info["sigma"] - wc.SIGMA) < 1e-12, info
     assert info["scatter_launches"] == wc.SIZES[c.size][7], info
     assert info["scatter_block"] == wc.block_edge(c), info
