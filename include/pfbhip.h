@@ -221,6 +221,10 @@ int pfbhip_gridder_vis2dirty_rows_dev(pfbhip_gridder *g, const double *vis_dev, 
  * ones at the phase centre, else the phase ramp of :617-622 -- formed inside the sort kernel: no (nrow, nchan) complex
  * array exists anywhere.  psf_dev has the plan's image shape. */
 int pfbhip_gridder_psf_rows_dev(pfbhip_gridder *g, const double *wgt_dev /* or NULL */, double *psf_dev);
+/* The same with the ramp's sign chosen: ramp_sign = +1 is pfbhip_gridder_psf_rows_dev, -1 the conjugate ramp of the snapshot
+ * imager (src/pfb_imaging/utils/stokes2im.py:354, :483-486: freqfactor = -2 pi i f / c where operators/gridder.py:618 has
+ * +2 pi i).  At the phase centre both are ones. */
+int pfbhip_gridder_psf_rows_signed_dev(pfbhip_gridder *g, const double *wgt_dev /* or NULL */, double ramp_sign, double *psf_dev);
 /* pfbhip_gridder_set_weights (operators/hessian.py:50-89) from a resident array. */
 int pfbhip_gridder_set_weights_dev(pfbhip_gridder *g, const double *wgt_dev /* or NULL */);
 /* Un-weighted model visibilities and the residual visibilities (operators/gridder.py:480-507).  minuend_dev NULL: vis = R dirty,
@@ -401,6 +405,41 @@ int pfbhip_imaging_weights_dev(const double *uvw_host, const double *freq_host, 
                                int64_t ncorr, int64_t nrow, int64_t nchan, int64_t nx, int64_t ny, double cell_x, double cell_y,
                                double usign, double vsign, double robust, double filter_level, int64_t npix_super,
                                double *counts_out_host /* or NULL */);
+
+/* ---- one `pfb hci` snapshot on a resident chunk (csrc/snapshot.hip): the array steps of
+ * src/pfb_imaging/utils/stokes2im.py::stokes_image around its two vis2dirty calls per Stokes.  Every entry validates first and
+ * returns with its stream idle; the sums are two-stage like the chunk's (bit-identical from call to call). */
+/* Rephasing and model subtraction, stokes2im.py:364-373 and :466-468, one in-place pass over vis_dev (ncorr, nrow * nchan)
+ * complex128:  vis = (vis p - model p) * mask,  p = exp(-2 pi i freq[chan] / c * w_diff[row]).  w_diff_dev (nrow) may be NULL
+ * (p = 1), model_dev (ncorr, nrow * nchan) may be NULL; the mask (uint8) applies only with a model, as in the reference
+ * (:467-468), and masked samples are then written as exact zeros.  The phase is formed in cycles, reduced to a fraction of
+ * a turn, then sincospi.  The reference rephases the raw correlations before weight_data (:371, :447); weight_data's Jones
+ * correction and Stokes combination are linear in the data and p is one complex scalar per (row, channel), so it commutes
+ * with them and rephasing the Stokes chunk is the same operation. */
+int pfbhip_chunk_rephase_residual_dev(double *vis_dev, const double *model_dev /* or NULL */, const uint8_t *mask_dev,
+                                      const double *w_diff_dev /* or NULL */, const double *freq_host, int64_t ncorr, int64_t nrow,
+                                      int64_t nchan);
+/* The l2 reweighting in stokes_image's form, stokes2im.py:470-481: ressq = |r|^2 * mask (a 0 / 1 mask; the mask broadcast
+ * over the correlations, the evident intent of :472), ovar = sum over EVERY correlation and sample of ressq / sum(mask) -- one
+ * joint variance -- and wgt = (dof + 1) / (dof + ressq / ovar) / ovar on every sample: the weights are replaced, not
+ * multiplied; a masked sample gets (dof + 1) / dof / ovar, so dof must be positive (and finite).  ovar_host (may be NULL) receives ovar.  A zero variance (the
+ * reference's ValueError, :479) or an empty mask (:481 sets weight = None and fails later) is PFBHIP_ERR_INVALID before any
+ * weight is written. */
+int pfbhip_chunk_l2_reweight_joint_dev(const double *resvis_dev, const uint8_t *mask_dev, double *wgt_dev, int64_t ncorr, int64_t nvis,
+                                       double dof, double *ovar_host);
+/* The finish, stokes2im.py:684-692, :707-708, :731-737, :750-753, on the Stokes planes residual_dev (ns, nx, ny) and psf_dev
+ * (ns, nxp, nyp) float64 in HBM.  Per Stokes c with wsum_host[c] > 0: psf_max = max(psf[c]) (exact); psf[c] /= psf_max and
+ * residual[c] /= psf_max in place; rms[c] = np.std(residual[c]), two-pass; with pbeam_dev (ns, nx, ny; may be NULL)
+ * residual[c] *= pbeam / (pbeam^2 + eta) in place and beam_weight = pbeam^2 + eta.  A Stokes with wsum <= 0 gets zero residual,
+ * PSF, cube and psf planes (whatever its beam holds), psf_max 0 and rms 0; its beam_weight plane is pbeam^2 + eta all the
+ * same, as the reference forms beam_weight from the beam alone (:751).  Host outputs, TRANSPOSED, float32 (out_f64 = 0) or float64: cube_host (ns, ny, nx), psf_host (ns, nyp,
+ * nxp; may be NULL), beam_weight_host (ns, ny, nx; may be NULL, needs pbeam_dev); psf_max_host[ns], rms_host[ns].  Unlike the
+ * reference, whose normalisation loop is nested inside the per-Stokes loop (:686), each Stokes is normalised once.
+ * device_ms (may be NULL) receives the device time of the kernels alone, without the downloads. */
+int pfbhip_snapshot_finish_dev(double *residual_dev, double *psf_dev, const double *pbeam_dev /* or NULL */, const double *wsum_host,
+                               int64_t ns, int64_t nx, int64_t ny, int64_t nxp, int64_t nyp, double eta, int out_f64, void *cube_host,
+                               void *psf_host /* or NULL */, void *beam_weight_host /* or NULL */, double *psf_max_host,
+                               double *rms_host, double *device_ms /* or NULL */);
 
 /* ---- wavelet dictionary Psi and the l21 / positivity proxes ---------------- */
 /*

@@ -144,6 +144,8 @@ SYMBOLS = (
     "pfbhip_weight_data", "pfbhip_weight_data_sp", "pfbhip_weight_data_dev", "pfbhip_debug_copy16",
     "pfbhip_gridder_vis2dirty_rows_dev", "pfbhip_gridder_psf_rows_dev", "pfbhip_gridder_set_weights_dev",
     "pfbhip_gridder_dirty2vis_rows_dev", "pfbhip_chunk_wsum_dev", "pfbhip_chunk_l2_reweight_dev", "pfbhip_imaging_weights_dev",
+    "pfbhip_chunk_rephase_residual_dev", "pfbhip_chunk_l2_reweight_joint_dev", "pfbhip_gridder_psf_rows_signed_dev",
+    "pfbhip_snapshot_finish_dev",
 )
 
 _lib = None
@@ -379,6 +381,22 @@ def dev_ptr(a, offset=0, count=None):
     if not a.ptr.value and size:
         raise ValueError("the DeviceArray has been freed")
     return vp((a.ptr.value or 0) + offset * a.dtype.itemsize)
+
+
+class DeviceView(DeviceArray):
+    """``shape`` elements of the DeviceArray ``base`` from element ``offset`` on, as a DeviceArray that owns nothing (``free``
+    leaves the memory alone; the view keeps ``base`` referenced): one plane of a resident cube where a call takes a
+    DeviceArray of the plane's shape."""
+
+    def __init__(self, base, offset, shape):
+        self.shape = tuple(int(s) for s in shape)
+        self.dtype = base.dtype
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        self.ptr = dev_ptr(base, offset, self.nbytes // self.dtype.itemsize)
+        self.base = base
+
+    def free(self):
+        self.ptr = vp()
 
 
 _ro_memo = {}  # (address, shape, dtype) -> (array kept alive, key, sample): read-only inputs only

@@ -2580,23 +2580,30 @@ int pfbhip_gridder_vis2dirty_rows_dev(pfbhip_gridder *g, const double *vis_dev, 
 }
 
 // The PSF of gridder.py:616-655 for the plan's own centre: the visibilities (ones, or the phase ramp of :617-622) are formed
-// inside the permute kernel, see k_permute_in_psf.
-int pfbhip_gridder_psf_rows_dev(pfbhip_gridder *g, const double *wgt_dev, double *psf_dev)
+// inside the permute kernel, see k_permute_in_psf.  ramp_sign = -1 conjugates the ramp: the snapshot imager's PSF
+// visibilities (utils/stokes2im.py:354, :483-486 of the reference: freqfactor = -2 pi i f / c where grid has +2 pi i).
+int pfbhip_gridder_psf_rows_signed_dev(pfbhip_gridder *g, const double *wgt_dev, double ramp_sign, double *psf_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(g && psf_dev, "NULL argument");
+        PFB_REQUIRE(ramp_sign == 1.0 || ramp_sign == -1.0, "ramp_sign must be +1 or -1, not %g", ramp_sign);
         const double x0 = g->uprm.center_x, y0 = g->uprm.center_y;
         PFB_REQUIRE(x0 * x0 + y0 * y0 < 1.0, "phase centre (%g, %g) is not on the sphere", x0, y0);
         const double nm1 = std::sqrt(1.0 - x0 * x0 - y0 * y0) - 1.0;
         stream_scope(g->stream, [&] {
             if (g->info.nactive)
                 hipLaunchKernelGGL(k_permute_in_psf, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->map, g->d_src.p,
-                                   g->info.nactive, wgt_dev, int(x0 != 0.0 || y0 != 0.0), x0, y0, nm1, int(g->shifting), g->info.lshift,
-                                   g->info.mshift, g->info.nshift, g->d_sval.p);
+                                   g->info.nactive, wgt_dev, int(x0 != 0.0 || y0 != 0.0), ramp_sign * x0, ramp_sign * y0, ramp_sign * nm1,
+                                   int(g->shifting), g->info.lshift, g->info.mshift, g->info.nshift, g->d_sval.p);
             PFB_HIP(hipGetLastError());
             g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, psf_dev);
         });
     });
+}
+
+int pfbhip_gridder_psf_rows_dev(pfbhip_gridder *g, const double *wgt_dev, double *psf_dev)
+{
+    return pfbhip_gridder_psf_rows_signed_dev(g, wgt_dev, 1.0, psf_dev);
 }
 
 // set_weights (the weights of hessian.py:50-89) from a resident array

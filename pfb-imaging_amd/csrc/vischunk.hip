@@ -15,22 +15,9 @@
 
 #include "abi_scope.hpp"
 #include "common.hpp"
+#include "vischunk_api.hpp"
 
 namespace pfbhip {
-
-constexpr int CHUNK_THREADS = 256;
-constexpr int CHUNK_MAX_BLOCKS = 1024;  // first-stage blocks per correlation: one sweep covers 262 144 samples
-
-// sum of s[0, CHUNK_THREADS) into s[0] (every thread of the block calls it)
-template <class T>
-__device__ __forceinline__ void block_tree_sum(T *s)
-{
-    __syncthreads();
-    for (int h = CHUNK_THREADS / 2; h > 0; h >>= 1) {
-        if (int(threadIdx.x) < h) s[threadIdx.x] += s[threadIdx.x + h];
-        __syncthreads();
-    }
-}
 
 // part[c * gridDim.x + b] = sum over block b's samples of correlation c = blockIdx.y of wgt[c, i] where mask[i] != 0
 __global__ void __launch_bounds__(CHUNK_THREADS) k_wsum_partial(const double *__restrict__ wgt, const uint8_t *__restrict__ mask,
@@ -76,9 +63,10 @@ __global__ void __launch_bounds__(CHUNK_THREADS) k_ressq_partial(const double2 *
     }
 }
 
-// out[c] = sum of part[c * nb, (c + 1) * nb): one block per correlation; cnt_out = sum of cnt[0, nb) by block 0 (cnt may be NULL)
+// out[c] = sum of part[c * nb, (c + 1) * nb): one block per correlation; cnt_out = sum of cnt[0, ncnt) by block 0 (cnt may be NULL)
 __global__ void __launch_bounds__(CHUNK_THREADS) k_partial_final(const double *__restrict__ part, const unsigned long long *__restrict__ cnt,
-                                                                 int nb, double *__restrict__ out, unsigned long long *__restrict__ cnt_out)
+                                                                 int nb, int ncnt, double *__restrict__ out,
+                                                                 unsigned long long *__restrict__ cnt_out)
 {
     __shared__ double s[CHUNK_THREADS];
     __shared__ unsigned long long sc[CHUNK_THREADS];
@@ -90,7 +78,7 @@ __global__ void __launch_bounds__(CHUNK_THREADS) k_partial_final(const double *_
     if (threadIdx.x == 0) out[c] = s[0];
     if (c == 0 && cnt) {
         unsigned long long n = 0;
-        for (int b = threadIdx.x; b < nb; b += CHUNK_THREADS) n += cnt[b];
+        for (int b = threadIdx.x; b < ncnt; b += CHUNK_THREADS) n += cnt[b];
         sc[threadIdx.x] = n;
         block_tree_sum(sc);
         if (threadIdx.x == 0) *cnt_out = sc[0];
@@ -112,7 +100,20 @@ __global__ void __launch_bounds__(CHUNK_THREADS) k_l2_reweight(const double2 *__
     wgt[k] *= (dof + 2.0) / (dof + ressq / ovar[c]);
 }
 
-static int first_stage_blocks(int64_t nvis) { return int(std::min<int64_t>(std::max<int64_t>(ceil_div(nvis, CHUNK_THREADS), 1), CHUNK_MAX_BLOCKS)); }
+int chunk_first_stage_blocks(int64_t nvis) { return int(std::min<int64_t>(std::max<int64_t>(ceil_div(nvis, CHUNK_THREADS), 1), CHUNK_MAX_BLOCKS)); }
+
+void chunk_ressq_partial(hipStream_t st, const double2 *r, const double *wgtp_dev, double wgtp_scalar, const uint8_t *mask_dev,
+                         int64_t ncorr, int64_t nvis, int nb, double *part, unsigned long long *cnt)
+{
+    hipLaunchKernelGGL(k_ressq_partial, dim3(uint32_t(nb), uint32_t(ncorr)), dim3(CHUNK_THREADS), 0, st, r, wgtp_dev, wgtp_scalar, mask_dev,
+                       nvis, part, cnt);
+}
+
+void chunk_partial_final(hipStream_t st, const double *part, const unsigned long long *cnt, int nb, int ncnt, int nout, double *out,
+                         unsigned long long *cnt_out)
+{
+    hipLaunchKernelGGL(k_partial_final, dim3(uint32_t(nout)), dim3(CHUNK_THREADS), 0, st, part, cnt, nb, ncnt, out, cnt_out);
+}
 
 }  // namespace pfbhip
 
@@ -126,12 +127,12 @@ int pfbhip_chunk_wsum_dev(const double *wgt_dev, const uint8_t *mask_dev, int64_
         PFB_REQUIRE(wsum_host && ncorr >= 1 && ncorr <= 65535 && nvis >= 0, "bad arguments");
         PFB_REQUIRE((wgt_dev && mask_dev) || nvis == 0, "NULL argument");
         const hipStream_t st = hipStreamPerThread;
-        const int nb = first_stage_blocks(nvis);
+        const int nb = chunk_first_stage_blocks(nvis);
         DevBuf<double> part(size_t(ncorr) * size_t(nb)), out{size_t(ncorr)};
         synced(st, [&] {  // (wsum_host is written until the wait; part and out are declared outside)
             hipLaunchKernelGGL(k_wsum_partial, dim3(uint32_t(nb), uint32_t(ncorr)), dim3(CHUNK_THREADS), 0, st, wgt_dev, mask_dev, nvis,
                                part.p);
-            hipLaunchKernelGGL(k_partial_final, dim3(uint32_t(ncorr)), dim3(CHUNK_THREADS), 0, st, part.p, nullptr, nb, out.p, nullptr);
+            chunk_partial_final(st, part.p, nullptr, nb, 0, int(ncorr), out.p, nullptr);
             PFB_HIP(hipGetLastError());
             PFB_HIP(hipMemcpyAsync(wsum_host, out.p, size_t(ncorr) * sizeof(double), hipMemcpyDeviceToHost, st));
         });
@@ -145,16 +146,15 @@ int pfbhip_chunk_l2_reweight_dev(const double *resvis_dev, const double *wgtp_de
         PFB_REQUIRE(ncorr >= 1 && ncorr <= 65535 && nvis >= 0, "bad arguments");
         PFB_REQUIRE((resvis_dev && mask_dev && wgt_dev) || nvis == 0, "NULL argument");
         const hipStream_t st = hipStreamPerThread;
-        const int nb = first_stage_blocks(nvis);
+        const int nb = chunk_first_stage_blocks(nvis);
         DevBuf<double> part(size_t(ncorr) * size_t(nb)), ssq{size_t(ncorr)};
         DevBuf<unsigned long long> cnt(size_t(nb) + 1);
         std::vector<double> ovar(static_cast<size_t>(ncorr), 0.0);
         unsigned long long nmask = 0;
         const double2 *r = reinterpret_cast<const double2 *>(resvis_dev);
         synced(st, [&] {
-            hipLaunchKernelGGL(k_ressq_partial, dim3(uint32_t(nb), uint32_t(ncorr)), dim3(CHUNK_THREADS), 0, st, r, wgtp_dev, wgtp_scalar,
-                               mask_dev, nvis, part.p, cnt.p);
-            hipLaunchKernelGGL(k_partial_final, dim3(uint32_t(ncorr)), dim3(CHUNK_THREADS), 0, st, part.p, cnt.p, nb, ssq.p, cnt.p + nb);
+            chunk_ressq_partial(st, r, wgtp_dev, wgtp_scalar, mask_dev, ncorr, nvis, nb, part.p, cnt.p);
+            chunk_partial_final(st, part.p, cnt.p, nb, nb, int(ncorr), ssq.p, cnt.p + nb);
             PFB_HIP(hipGetLastError());
             PFB_HIP(hipMemcpyAsync(ovar.data(), ssq.p, size_t(ncorr) * sizeof(double), hipMemcpyDeviceToHost, st));
             PFB_HIP(hipMemcpyAsync(&nmask, cnt.p + nb, sizeof nmask, hipMemcpyDeviceToHost, st));

@@ -48,6 +48,21 @@ def generate_transient_spectra(times, freqs, transient_params):
     return profile, generate_frequency_profile(freqs, fp["peak_flux"], fp["reference_freq"], fp["spectral_index"])
 
 
+def accumulate_sources(dft, out, time, freq, sources, all_times, all_freqs, w_diff=None, beam=None):
+    """The per-source loop of stokes2im.py:501-558 on the device: each source's profiles are interpolated onto ``time`` / ``freq``,
+    scaled by its row of ``beam``, and ``tprofile[:, None] * fprofile[None, :] * exp(freqfactor * phase)`` is added into ``out``
+    (complex128 ``(nrow, nchan)``, a host array or a ``DeviceArray``) by one accumulating predict of ``dft`` (a
+    :class:`~pfb_imaging_amd.dft.DFT` over the coordinates the sources are simulated at).  Shared by :func:`inject_transients`
+    and ``VisChunk.inject_transients``; the arguments have been checked by the caller."""
+    for k, src in enumerate(sources):
+        tprofile = np.interp(time, all_times, src["time_profile"])
+        fprofile = np.interp(freq, all_freqs, src["freq_profile"])
+        if beam is not None:
+            fprofile = fprofile * beam[k]
+        dft.predict(np.array([[src["l"], src["m"]]]), np.ones(1), rowf=tprofile[None, :], chanf=fprofile[None, :], off=w_diff,
+                    signs=(1.0, 1.0, 1.0), sgn=-1.0, do_wgridding=True, divide_by_n=False, accumulate=True, out=out)
+
+
 def inject_transients(data, uvw, freq, time, sources, all_times, all_freqs, w_diff=None, beam=None):
     """Add point transients to ``data[:, :, 0]`` in place and return ``data`` (stokes2im.py:491-558, arrays only).
 
@@ -79,13 +94,7 @@ def inject_transients(data, uvw, freq, time, sources, all_times, all_freqs, w_di
     with DFT(uvw, freq) as d:
         acc = _lib.DeviceArray.from_host(np.ascontiguousarray(data[:, :, 0], dtype=np.complex128))
         try:
-            for k, src in enumerate(sources):
-                tprofile = np.interp(time, all_times, src["time_profile"])
-                fprofile = np.interp(freq, all_freqs, src["freq_profile"])
-                if beam is not None:
-                    fprofile = fprofile * beam[k]
-                d.predict(np.array([[src["l"], src["m"]]]), np.ones(1), rowf=tprofile[None, :], chanf=fprofile[None, :], off=w_diff,
-                          signs=(1.0, 1.0, 1.0), sgn=-1.0, do_wgridding=True, divide_by_n=False, accumulate=True, out=acc)
+            accumulate_sources(d, acc, time, freq, sources, all_times, all_freqs, w_diff, beam)
             data[:, :, 0] = acc.download()
         finally:
             acc.free()

@@ -11,6 +11,8 @@ Memory held: ``ncorr * 24 + 1`` bytes per sample (complex128 visibilities, float
 ``image_data_products_chunk`` holds ``ncorr * 16`` more per sample while a model is given (the residual visibilities).
 """
 
+import ctypes as ct
+
 import numpy as np
 
 from . import _lib
@@ -154,6 +156,84 @@ class VisChunk:
             if own is not None:
                 own.free()
         return ovar
+
+    # -- the snapshot imager's steps (utils/stokes2im.py; csrc/snapshot.hip) ---------------------------------------------
+    def _check_rephase(self, w_diff, model):
+        """``(w_diff (nrow) float64 or None, model)`` after the checks; no device call"""
+        if w_diff is not None:
+            w_diff = np.asarray(w_diff)
+            if w_diff.dtype.kind not in "fiu":
+                raise TypeError(f"w_diff must be real, not {w_diff.dtype}")
+            if w_diff.shape == (self.nrow, 1):
+                w_diff = w_diff.reshape(self.nrow)
+            if w_diff.shape != (self.nrow,):
+                raise ValueError(f"w_diff shape {w_diff.shape} != {(self.nrow,)}")
+            w_diff = as_c(w_diff, np.float64)
+        if model is not None:
+            model = _adopt(model, (self.ncorr, self.nrow, self.nchan), np.complex128, "model")
+        return w_diff, model
+
+    def rephase_residual(self, w_diff=None, model=None):
+        """stokes2im.py:364-373 and :466-468 of the reference in one in-place pass: ``vis = (vis p - model p) * mask`` with ``p =
+        exp(-2 pi i freq / c * w_diff[row])``.  ``w_diff (nrow)`` or ``(nrow, 1)`` [m] is a host array (``None``: ``p = 1``);
+        ``model``, Stokes model visibilities ``(ncorr, nrow, nchan)``, a host array (uploaded for the call) or a complex128
+        ``DeviceArray`` (left as it is).  The mask applies only with a model."""
+        w_diff, model = self._check_rephase(w_diff, model)
+        self._open()
+        wd = md = None
+        try:
+            if w_diff is not None:
+                wd = DeviceArray.from_host(w_diff)
+            if model is not None:
+                md = model if isinstance(model, DeviceArray) else DeviceArray.from_host(as_c(model, np.complex128))
+            check(lib().pfbhip_chunk_rephase_residual_dev(self.vis.ptr, None if md is None else md.ptr, self.mask.ptr,
+                                                          None if wd is None else wd.ptr, ptr(self.freq), i64(self.ncorr),
+                                                          i64(self.nrow), i64(self.nchan)))
+        finally:
+            if wd is not None:
+                wd.free()
+            if md is not None and md is not model:
+                md.free()
+
+    def l2_reweight_joint(self, dof):
+        """The l2 reweighting in ``stokes_image``'s form (stokes2im.py:470-481) with the chunk's visibilities as the residual:
+        ``ovar = sum over every correlation of |vis|^2 mask / mask.sum()`` and ``wgt = (dof + 1) / (dof + |vis|^2 mask / ovar)
+        / ovar`` -- the weights are replaced.  Returns ``ovar``; raises ``ValueError`` and leaves the weights as they are when
+        the residual is exactly zero or the mask is empty.  ``dof`` must be positive: a masked sample gets ``(dof + 1) / dof / ovar``."""
+        dof = float(dof)
+        if not (dof > 0 and np.isfinite(dof)):
+            raise ValueError(f"dof = {dof} must be positive and finite")
+        self._open()
+        ovar = f64(0.0)
+        check(lib().pfbhip_chunk_l2_reweight_joint_dev(self.vis.ptr, self.mask.ptr, self.wgt.ptr, i64(self.ncorr), i64(self.nvis),
+                                                       f64(dof), ct.byref(ovar)))
+        return ovar.value
+
+    def inject_transients(self, uvw, freq, time, sources, all_times, all_freqs, w_diff=None, beam=None):
+        """:func:`~pfb_imaging_amd.utils.transients.inject_transients` (stokes2im.py:491-558) into the chunk's first Stokes plane
+        where it lies: one accumulating direct-DFT predict per source, no download.  ``uvw`` are the coordinates the sources
+        are simulated at (the reference's ``uvw_old``); ``freq`` must be the chunk's."""
+        from .dft import DFT
+        from .utils.transients import accumulate_sources
+
+        uvw, freq, time = np.asarray(uvw, dtype=np.float64), np.asarray(freq, dtype=np.float64), np.asarray(time, dtype=np.float64)
+        if uvw.shape != (self.nrow, 3):
+            raise ValueError(f"uvw shape {uvw.shape} != {(self.nrow, 3)}")
+        if freq.shape != (self.nchan,) or not np.array_equal(freq, self.freq):
+            raise ValueError("freq must be the chunk's frequencies")
+        if time.shape != (self.nrow,):
+            raise ValueError(f"time {time.shape} != {(self.nrow,)}")
+        w_diff, _ = self._check_rephase(w_diff, None)
+        if beam is not None:
+            beam = np.asarray(beam, dtype=np.float64)
+            if beam.shape != (len(sources), self.nchan):
+                raise ValueError(f"beam {beam.shape} != {(len(sources), self.nchan)}")
+        self._open()
+        if not len(sources):
+            return
+        plane = _lib.DeviceView(self.vis, 0, (self.nrow, self.nchan))
+        with DFT(uvw, freq) as d:
+            accumulate_sources(d, plane, time, freq, sources, all_times, all_freqs, w_diff, beam)
 
     def imaging_weights(self, nx_pad, ny_pad, cellx, celly, robust, filter_level=5.0, npix_super=0, usign=1.0, vsign=-1.0,
                         return_counts=False):

@@ -187,10 +187,13 @@ class Gridder:
         w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
         check(lib().pfbhip_gridder_vis2dirty_rows_dev(self._h, v, w, self._img_dev(dirty_dev, "dirty_dev")))
 
-    def psf_rows_dev(self, wgt_dev, psf_dev, wgt_offset=0):
-        """``vis2dirty(psf_visibilities(...), wgt)`` for this plan's centre; the visibilities are formed on the device."""
+    def psf_rows_dev(self, wgt_dev, psf_dev, wgt_offset=0, ramp_sign=1.0):
+        """``vis2dirty(psf_visibilities(...), wgt)`` for this plan's centre; the visibilities are formed on the device.
+        ``ramp_sign=-1`` conjugates them: the snapshot imager's PSF (stokes2im.py:354, :483-486 of the reference)."""
+        if ramp_sign not in (1.0, -1.0):
+            raise ValueError(f"ramp_sign must be +1 or -1, not {ramp_sign}")
         w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
-        check(lib().pfbhip_gridder_psf_rows_dev(self._h, w, self._img_dev(psf_dev, "psf_dev")))
+        check(lib().pfbhip_gridder_psf_rows_signed_dev(self._h, w, f64(float(ramp_sign)), self._img_dev(psf_dev, "psf_dev")))
 
     def set_weights_dev(self, wgt_dev, wgt_offset=0):
         w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
