@@ -96,13 +96,16 @@ def taperf(shape, taper_width):
 
 def pcg(aop, b, x0=None, tol=1e-5, maxit=500, minit=100):
     """Restatement of pcg_numba without preconditioner (/root/reference/src/pfb_imaging/opt/pcg.py:88-199):
-    r = A x0 - b; stop on ||x - xp|| / ||x|| <= tol (and k >= minit), maxit, or 5 stalls."""
+    r = A x0 - b; stop on ||x - xp|| / ||x|| <= tol (and k >= minit), maxit, or 5 stalls.  ``pcg.last`` holds what the
+    reference only prints: iterations, status (0 converged, 1 maxit, 2 stalled, 3 zero start residual), eps, phi."""
     x = np.zeros_like(b) if x0 is None else x0
     r = aop(x) - b
     if not np.any(r):
+        pcg.last = dict(iters=0, status=3, eps=1.0, phi=0.0)
         return x
     p = -r
     rnorm = np.vdot(r, r).real
+    phi0 = rnorm
     k, eps, stall = 0, 1.0, 0
     while (eps > tol or k < minit) and k < maxit and stall < 5:
         xp = x.copy()
@@ -119,6 +122,7 @@ def pcg(aop, b, x0=None, tol=1e-5, maxit=500, minit=100):
         eps = np.linalg.norm(x - xp) / np.linalg.norm(x)
         if abs(epsp - eps) < 1e-3 * tol:
             stall += 1
+    pcg.last = dict(iters=k, status=1 if k >= maxit else (2 if stall >= 5 else 0), eps=float(eps), phi=float(rnorm / phi0))
     return x
 
 

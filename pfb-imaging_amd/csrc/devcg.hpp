@@ -5,8 +5,13 @@
 // x += alpha p, r += alpha Ap, beta = (r.r)_new/(r.r)_old, p = beta p - r; stop when
 // eps = ||x - xp|| / ||x|| <= tol (and k >= minit), or k == maxit, or 5 stalls
 // (|eps_prev - eps| < 1e-3 tol).  ||x - xp|| is alpha ||p|| analytically; ||x||^2 is floored
-// at 1e-12 like _nb_norm_diff.  Reductions are two-stage (per-block partials, summed on the
-// host in a fixed order), so results are run-to-run reproducible.
+// at 1e-12 like _nb_norm_diff.  Reductions are two-stage (per-block partials, summed in a
+// fixed order: by one block on the device inside the loop, on the host for the start residual
+// and the power method), so results are run-to-run reproducible
+// (tests/test_gpu_cg_pins.py::test_two_solves_are_bitwise_equal).  The same file holds both
+// loops to reference runs of pcg_numba / power_method_numba (iterations, status, x, eps, phi)
+// and walks the reductions' edges: n around one wave and one block, n equal to one grid stride
+// and just above it, a single non-zero element at each of those boundaries.
 #pragma once
 #include <hip/hip_runtime.h>
 
