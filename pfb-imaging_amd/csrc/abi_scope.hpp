@@ -1,6 +1,6 @@
 // abi_scope.hpp -- the host-side scaffold of a C-ABI entry point: the stream scope that keeps a call from returning while
 // the device still uses the caller's arrays, the upload that goes with it, the event timers and the 1-D launch shape.
-// Host code only.  (gridder.hip does not include it: it keeps its own StageTimer and blocks1d.)
+// Host code only.  (gridder.hip includes it too: its plan creation and all of its entries run under synced().)
 #pragma once
 #include <algorithm>
 #include <vector>

@@ -29,6 +29,7 @@
 #include <memory>
 #include <vector>
 
+#include "abi_scope.hpp"
 #include "common.hpp"
 #include "devcg.hpp"
 #include "dispatch.hpp"
@@ -522,63 +523,6 @@ __global__ void k_narrow_f64(int64_t n, const double *__restrict__ in, float *__
 enum Stage { ST_GRID, ST_DEGRID, ST_FFT_ROWS, ST_PAD, ST_CROP, ST_OTHER, ST_FFT_CROP, ST_PAD_FFT, ST_COUNT };
 static_assert(ST_COUNT == PFBHIP_NSTAGES, "stage list");
 
-struct StageTimer {
-    bool enabled = false;
-    hipStream_t stream = nullptr;
-    struct Rec {
-        int stage;
-        hipEvent_t a, b;
-    };
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
-    double ms[PFBHIP_NSTAGES] = {0};
-    int64_t calls[PFBHIP_NSTAGES] = {0};
-    hipEvent_t get()
-    {
-        if (!pool.empty()) {
-            hipEvent_t e = pool.back();
-            pool.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        PFB_HIP(hipEventCreate(&e));
-        return e;
-    }
-    void begin(int stage)
-    {
-        if (!enabled) return;
-        Rec r{stage, get(), get()};
-        PFB_HIP(hipEventRecord(r.a, stream));
-        recs.push_back(r);
-    }
-    void end()
-    {
-        if (!enabled) return;
-        PFB_HIP(hipEventRecord(recs.back().b, stream));
-    }
-    void collect()
-    {
-        for (auto &r : recs) {
-            PFB_HIP(hipEventSynchronize(r.b));
-            float t = 0;
-            PFB_HIP(hipEventElapsedTime(&t, r.a, r.b));
-            ms[r.stage] += t;
-            calls[r.stage] += 1;
-            pool.push_back(r.a);
-            pool.push_back(r.b);
-        }
-        recs.clear();
-    }
-    ~StageTimer()
-    {
-        for (auto &r : recs) {
-            (void)hipEventDestroy(r.a);
-            (void)hipEventDestroy(r.b);
-        }
-        for (auto e : pool) (void)hipEventDestroy(e);
-    }
-};
-
 // Which kernels and transforms a plan runs.  Decided in three steps of plan creation (sort_key_sub in sort_by_tile,
 // choose_kernels once build_work_lists has the work lists, choose_transforms in setup_transforms once the row-FFT plans
 // exist; PlanBuild::path until then), read-only afterwards, and reported as info.scatter_mode / scatter_launches /
@@ -635,6 +579,13 @@ struct pfbhip_gridder {
     DevBuf<WorkItem> d_work_col;
     std::vector<size_t> col_off, col_cnt;  // [group * 4 + colour]
     PlanPath path;
+    int kp_max = 1;                            // planes scattered / gathered per pass (LDS holds kp_max tiles)
+    size_t plane_stride = 0;                   // complex elements per plane of d_grid
+    std::vector<double> wplanes;               // w of every plane (wavelengths)
+    std::vector<double> nodes, lagr_coef;      // wmode 1: Chebyshev nodes and Lagrange denominators
+    float wshare[3] = {1.3f / 3, 1.f / 3, 0.7f / 3};  // see GroupArgs::wshare: measured optimum on C2 (equal shares: +7 % scatter time)
+    bool weights_bound = false;
+
     // scratch
     DevBuf<double2> d_grid, d_sval, d_sacc, d_vis;
     // Hessian applies clear the scatter's planes on a side stream while the degrid half runs: a second plane buffer
@@ -644,36 +595,67 @@ struct pfbhip_gridder {
     // work.  Clearing those -- per tile row the runs of touched tile columns, 8-row slices -- instead of every occupied row
     // moves a third of the bytes when the uv coverage is a disc (C2: 0.9 of 2.4 GB).
     DevBuf<int4> d_clear_rects;
-    DevBuf<int4> d_colruns;  // per tile row: the column runs in use (transposing first-axis FFT: RunLoad / RunStore)
     int n_clear_rects = 0;  // (> 0 only with the transposing first-axis transform)
     hipStream_t clear_stream = nullptr;
     hipEvent_t ev_clear = nullptr, ev_start = nullptr;
     DevBuf<double> d_wgt, d_swgt, d_img, d_img2, d_beam;
-    DevBuf<char> d_fftwork;
     DevBuf<double2> d_gridB;  // (ny, nu) transposed / cropped plane
     DevBuf<double> d_accT;    // (ny, nx) transposed image accumulator / transposed degrid input
-    DevBuf<uint8_t> d_occ;    // occupancy of 32-row blocks of the uv-plane
-    // first-axis row FFTs with the crop / pad + transpose folded in (rowfft_a2b / rowfft_b2a): row of every workgroup,
-    // ordered so that the 8 rows of a 128-byte line of B run on one XCD at about the same time (PFBHIP_TFFT=0: the
-    // separate k_a2b / k_b2a passes)
-    DevBuf<int> d_rowmap;
-    bool weights_bound = false;
+    // host <-> device transfers of single-precision I/O go through this staging buffer (upload / download below); it is
+    // reused by the next transfer: in-order on this stream
+    DevBuf<float> d_stage32;
+
+    // per-scheme tables
+    // record-driven register-footprint scatter (k_grid_rec) and one-plane scatter: d_rec, static per-visibility records; d_pval,
+    // the plane-weighted values of the current apply (kp_max, or wd.K, per visibility), written by the gather inside a Hessian
+    // apply (ApplyState::gather_values) or by k_plane_values* in front of the scatter
+    DevBuf<VisRec> d_rec;
+    DevBuf<double2> d_pval;
+    // row-walk gather (k_degrid_rw): d_kw, plane weights of every visibility (plan time)
+    DevBuf<double> d_kw;
+    // one-plane w-scheme (info.wmode == 2, gridder_wd_api.hpp): K kernel functions per axis, their derivative tables, the K
+    // complex coefficients of every sorted visibility
+    WdArgs wd{};
+    DevBuf<double> d_dtab;
+    DevBuf<double2> d_cw;
+
+    // transforms
+    DevBuf<uint8_t> d_occ;  // occupancy of 32-row blocks of the uv-plane
     struct RowSpan {
         int64_t row0, nrows;                      // occupied rows [row0, row0 + nrows) of A
         rocfft_plan fwd = nullptr, bwd = nullptr;  // batched length-nv row transforms
     };
     std::vector<RowSpan> spans;
     int64_t occ_rows = 0;
-    int kp_max = 1;              // planes scattered / gathered per pass (LDS holds kp_max tiles)
-    RowFFT rowfft_u;             // hand-written row FFT of length nu with fused pad / crop (if nu is supported)
-    RowFFT rowfft_v;             // hand-written row FFT of length nv for the occupied rows of A (if nv is supported)
-    size_t bstride = 0;          // complex elements per plane of d_gridB
-    size_t plane_stride = 0;     // complex elements per plane of d_grid
+    RowFFT rowfft_u;     // hand-written row FFT of length nu with fused pad / crop (if nu is supported)
+    RowFFT rowfft_v;     // hand-written row FFT of length nv for the occupied rows of A (if nv is supported)
+    size_t bstride = 0;  // complex elements per plane of d_gridB
+    // first-axis row FFTs with the crop / pad + transpose folded in (rowfft_a2b / rowfft_b2a): row of every workgroup,
+    // ordered so that the 8 rows of a 128-byte line of B run on one XCD at about the same time (PFBHIP_TFFT=0: the
+    // separate k_a2b / k_b2a passes)
+    DevBuf<int> d_rowmap;
+    DevBuf<int4> d_colruns;  // per tile row: the column runs in use (transposing first-axis FFT: RunLoad / RunStore)
+    FusedGeom fgeom;         // filled once by create_impl (fused path)
+    std::vector<FusedPlanes> plane_groups;  // per pass of kp_max planes: w and the composite screen polynomials (plan time)
+    DevBuf<double2> d_tau;                  // column tables of the separable screens (FusedPlanes::sep), nplanes x nx
     rocfft_plan fftB_fwd = nullptr, fftB_bwd = nullptr;  // ny rows of length nu
     rocfft_execution_info fft_info = nullptr;
+    DevBuf<char> d_fftwork;
+
+    // the profile: events around the stages (timer), what pfbhip_gridder_profile / _profile_get collected from them so far
     StageTimer timer;
-    std::vector<double> wplanes;  // w of every plane (wavelengths)
-    std::vector<double> nodes, lagr_coef;  // wmode 1: Chebyshev nodes and Lagrange denominators
+    double stage_ms[PFBHIP_NSTAGES] = {0};
+    int64_t stage_calls[PFBHIP_NSTAGES] = {0};
+
+    size_t device_bytes() const  // every DevBuf above, in the order of its declaration
+    {
+        return d_uvw.bytes() + d_fc.bytes() + d_pu.bytes() + d_pv.bytes() + d_pw.bytes() + d_corr.bytes() + d_cfu.bytes() +
+               d_cfv.bytes() + d_cheb.bytes() + d_ktab.bytes() + d_mask.bytes() + d_src.bytes() + d_work.bytes() + d_work_col.bytes() +
+               d_grid.bytes() + d_sval.bytes() + d_sacc.bytes() + d_vis.bytes() + d_grid2.bytes() + d_clear_rects.bytes() +
+               d_wgt.bytes() + d_swgt.bytes() + d_img.bytes() + d_img2.bytes() + d_beam.bytes() + d_gridB.bytes() + d_accT.bytes() +
+               d_stage32.bytes() + d_rec.bytes() + d_pval.bytes() + d_kw.bytes() + d_dtab.bytes() + d_cw.bytes() + d_occ.bytes() +
+               d_rowmap.bytes() + d_colruns.bytes() + d_tau.bytes() + d_fftwork.bytes();
+    }
 
     ~pfbhip_gridder()
     {
@@ -688,15 +670,6 @@ struct pfbhip_gridder {
         if (clear_stream) (void)hipStreamDestroy(clear_stream);
         if (ev_clear) (void)hipEventDestroy(ev_clear);
         if (ev_start) (void)hipEventDestroy(ev_start);
-    }
-
-    size_t device_bytes() const
-    {
-        return d_uvw.bytes() + d_fc.bytes() + d_pu.bytes() + d_pv.bytes() + d_pw.bytes() + d_corr.bytes() +
-               d_cfu.bytes() + d_cfv.bytes() + d_cheb.bytes() + d_ktab.bytes() + d_mask.bytes() + d_src.bytes() + d_work.bytes() + d_work_col.bytes() +
-               d_grid.bytes() + d_grid2.bytes() + d_sval.bytes() + d_sacc.bytes() + d_vis.bytes() + d_wgt.bytes() + d_swgt.bytes() +
-               d_img.bytes() + d_img2.bytes() + d_beam.bytes() + d_fftwork.bytes() + d_gridB.bytes() +
-               d_accT.bytes() + d_occ.bytes() + d_rowmap.bytes() + d_rec.bytes() + d_pval.bytes() + d_kw.bytes() + d_tau.bytes() + d_dtab.bytes() + d_cw.bytes() + d_stage32.bytes();
     }
 
     PlaneArgs plane_args(int plane) const
@@ -781,19 +754,6 @@ struct pfbhip_gridder {
     {
         return (size_t(2) * KP * blk_tile_rows(W) * blk_stride(W, KP) + blk_fixed_doubles(W, blk_threads(kp_max) / 64)) * sizeof(double);
     }
-    // record-driven register-footprint scatter (k_grid_rec) and one-plane scatter: d_rec, static per-visibility records; d_pval,
-    // the plane-weighted values of the current apply (kp_max, or wd.K, per visibility), written by the gather inside a Hessian
-    // apply (ApplyState::gather_values) or by k_plane_values* in front of the scatter
-    // one-plane w-scheme (info.wmode == 2, gridder_wd_api.hpp): K kernel functions per axis, their derivative tables, the K
-    // complex coefficients of every sorted visibility
-    WdArgs wd{};
-    DevBuf<double> d_dtab;
-    DevBuf<double2> d_cw;
-    DevBuf<VisRec> d_rec;
-    // row-walk gather (k_degrid_rw): d_kw, plane weights of every visibility (plan time)
-    DevBuf<double> d_kw;
-    float wshare[3] = {1.3f / 3, 1.f / 3, 0.7f / 3};  // see GroupArgs::wshare: measured optimum on C2 (equal shares: +7 % scatter time)
-    DevBuf<double2> d_pval;
 
     // the scatter of planes [plane0, plane0 + kp) of sval into a.out: one launch, or one per tile colour (see blk_tile_to_grid)
     void launch_grid(const ApplyState &a, int plane0, int kp, const double2 *sval)
@@ -983,10 +943,7 @@ struct pfbhip_gridder {
         if (!grid_all_planes(a, sval, path.axis2 == SecondAxis::Fused ? &f : nullptr)) finalize(beam, scale, eta, x, out);
     }
 
-    FusedGeom fgeom;  // filled once by create_impl (fused path)
     const FusedGeom &fused_geom() const { return fgeom; }
-    std::vector<FusedPlanes> plane_groups;  // per pass of kp_max planes: w and the composite screen polynomials (plan time)
-    DevBuf<double2> d_tau;                  // column tables of the separable screens (FusedPlanes::sep), nplanes x nx
     FusedPlanes fused_planes(int p0, int kp) const
     {
         const size_t grp = size_t(p0 / kp_max);
@@ -1089,9 +1046,8 @@ struct pfbhip_gridder {
         }
     }
 
-    // host <-> device transfers of n values: double as they are; float (single-precision I/O) through a staging buffer,
-    // widened / narrowed on the device (the staging buffer is reused by the next transfer: in-order on this stream)
-    DevBuf<float> d_stage32;
+    // host <-> device transfers of n values: double as they are; float (single-precision I/O) through the staging buffer
+    // d_stage32, widened / narrowed on the device
     void upload(const double *host, size_t n, double *dst)
     {
         PFB_HIP(hipMemcpyAsync(dst, host, n * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1126,11 +1082,19 @@ struct pfbhip_gridder {
             upload(wgt_host, size_t(nvis), d_wgt.p);
         }
     }
+    // the optional beam image of a Hessian apply: d_beam <- beam_host; NULL stays NULL
+    template <class T>
+    const double *bind_beam(const T *beam_host)
+    {
+        if (!beam_host) return nullptr;
+        const size_t npix = size_t(prm.nx * prm.ny);
+        d_beam.ensure(npix);
+        upload(beam_host, npix, d_beam.p);
+        return d_beam.p;
+    }
 };
 
 namespace pfbhip {
-
-static inline dim3 blocks1d(int64_t n, int t = 256) { return dim3(uint32_t(std::max<int64_t>(ceil_div(n, t), 1))); }
 
 // Measured rocFFT 2-D complex128 in-place times (ms) on MI355X, ROCm 7.2 (profiles/r01a_rocfft_sizes.txt):
 // lengths <= 10240 (160 KiB of LDS per row) run one kernel per axis; longer ones are decomposed.
@@ -1696,13 +1660,18 @@ static void validate_params(pfbhip_gridder *g, const double *uvw, const double *
     PFB_REQUIRE(freq != nullptr, "freq is NULL");
 }
 
-// device, stream, phase-centre geometry, the uploads of uvw / fc / mask and what of MapArgs does not depend on the kernel choice
-static void setup_geometry_and_upload(pfbhip_gridder *g, PlanBuild &pb, const double *uvw, const double *freq, const uint8_t *mask)
+// the device and the plan's stream: everything after this step is enqueued on it, inside create_impl's scope
+static void open_stream(pfbhip_gridder *g)
 {
-    const auto &prm = g->prm;
     PFB_HIP(hipGetDevice(&g->device));
     PFB_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     g->timer.stream = g->stream;
+}
+
+// phase-centre geometry, the uploads of uvw / fc / mask and what of MapArgs does not depend on the kernel choice
+static void setup_geometry_and_upload(pfbhip_gridder *g, PlanBuild &pb, const double *uvw, const double *freq, const uint8_t *mask)
+{
+    const auto &prm = g->prm;
     hipStream_t st = g->stream;
     auto &info = g->info;
 
@@ -2227,10 +2196,11 @@ static void finish_rocfft_and_clear(pfbhip_gridder *g, const PlanBuild &pb)
     }
     // rows of A outside the occupied spans are never written: clear the plane once
     PFB_HIP(hipMemsetAsync(g->d_grid.p, 0, g->d_grid.bytes(), st));
-    PFB_HIP(hipStreamSynchronize(st));  // every vector of pb that was uploaded without a synchronisation of its own
 }
 
-// Runs once per handle (pfbhip_gridder_create), on a freshly constructed one.
+// Runs once per handle (pfbhip_gridder_create), on a freshly constructed one that the caller owns.  Several steps upload
+// vectors of pb, or the caller's arrays, without a wait of their own: pb is declared in front of the scope, whose wait is
+// the one they rely on -- also when a later step throws.
 static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq, const uint8_t *mask)
 {
     const auto &prm = g->prm;
@@ -2238,37 +2208,40 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
     PlanBuild pb;
     pb.verbosity = prm.verbosity;
     validate_params(g, uvw, freq);
-    setup_geometry_and_upload(g, pb, uvw, freq, mask);
-    w_range(g, pb);
-    pb.lap("upload + w range");
-    const KernelChoice choice = choose_kernel(prm, pb.sw, g->nvis, info.lshift, info.mshift, info.nshift, pb.wlo, pb.whi, pb.tmax,
-                                              1.0 + pb.nm1min);
-    apply_choice(g, choice, pb.wlo, pb.whi);
-    PFB_REQUIRE(info.nplanes >= 1 && info.nplanes < 100000, "unreasonable number of w-planes (%lld)",
-                (long long)info.nplanes);
-    finish_map_args(g, pb);
-    sort_by_tile(g, pb);
-    build_work_lists(g, pb);
-    sorted_coordinates(g, pb);
-    {  // step 2 of the plan's path: the scatter and gather kernels
-        const size_t nwork = pb.lists.work.size(), npass = std::max<size_t>(g->work_cnt.size(), 1);
-        const WorkShape ws{g->map.key_sub, nwork, nwork / npass, pb.lists.coarse_items / npass,
-                           g->plane_stride * size_t(g->kp_max) * sizeof(double2)};
-        pb.path = choose_kernels(pb.sw, prm, info, g->kp_max, ws);
-    }
-    upload_colour_slices(g, pb);
-    build_records(g, pb);
-    pb.lap("records");
-    upload_kernel_tables(g, pb);
-    build_correction_image(g, pb);
-    pb.lap("kernel table + correction");
-    alloc_plane_buffers(g, pb);
-    setup_transforms(g, pb);
-    setup_occupancy(g, pb);
-    make_rocfft_plans(g, pb);
-    upload_row_map(g, pb);
-    pb.lap("occupancy, column runs, row map");
-    finish_rocfft_and_clear(g, pb);
+    open_stream(g);
+    synced(g->stream, [&] {
+        setup_geometry_and_upload(g, pb, uvw, freq, mask);
+        w_range(g, pb);
+        pb.lap("upload + w range");
+        const KernelChoice choice = choose_kernel(prm, pb.sw, g->nvis, info.lshift, info.mshift, info.nshift, pb.wlo, pb.whi, pb.tmax,
+                                                  1.0 + pb.nm1min);
+        apply_choice(g, choice, pb.wlo, pb.whi);
+        PFB_REQUIRE(info.nplanes >= 1 && info.nplanes < 100000, "unreasonable number of w-planes (%lld)",
+                    (long long)info.nplanes);
+        finish_map_args(g, pb);
+        sort_by_tile(g, pb);
+        build_work_lists(g, pb);
+        sorted_coordinates(g, pb);
+        {  // step 2 of the plan's path: the scatter and gather kernels
+            const size_t nwork = pb.lists.work.size(), npass = std::max<size_t>(g->work_cnt.size(), 1);
+            const WorkShape ws{g->map.key_sub, nwork, nwork / npass, pb.lists.coarse_items / npass,
+                               g->plane_stride * size_t(g->kp_max) * sizeof(double2)};
+            pb.path = choose_kernels(pb.sw, prm, info, g->kp_max, ws);
+        }
+        upload_colour_slices(g, pb);
+        build_records(g, pb);
+        pb.lap("records");
+        upload_kernel_tables(g, pb);
+        build_correction_image(g, pb);
+        pb.lap("kernel table + correction");
+        alloc_plane_buffers(g, pb);
+        setup_transforms(g, pb);
+        setup_occupancy(g, pb);
+        make_rocfft_plans(g, pb);
+        upload_row_map(g, pb);
+        pb.lap("occupancy, column runs, row map");
+        finish_rocfft_and_clear(g, pb);
+    });
     pb.lap("rocFFT plans + plane clear");
     info.device_bytes = g->device_bytes();
 }
@@ -2276,8 +2249,9 @@ static void create_impl(pfbhip_gridder *g, const double *uvw, const double *freq
 }  // namespace pfbhip
 
 // ---------------------------------------------------------------------------------------
-// bodies of the C-ABI entries, shared by the double and single-precision host entries (T = double, float): only
-// pfbhip_gridder::upload / download differ
+// bodies of the C-ABI entries.  The *_host templates are the double and single-precision host entries themselves (T = double,
+// float: only pfbhip_gridder::upload / download differ): they check their arguments, then run everything they enqueue inside
+// one synced().  The other functions here run inside an entry's scope and leave the final wait to it.
 // ---------------------------------------------------------------------------------------
 
 // sval = the caller's row-ordered (nrow, nchan) device arrays in tile-sorted order, weighted with wgt_dev unless it is NULL,
@@ -2296,24 +2270,12 @@ static void permute_in(pfbhip_gridder *g, bool weighted)
     permute_in_rows(g, g->d_vis.p, weighted ? g->d_wgt.p : nullptr);
 }
 
-// body(), then a wait for st -- also when body() throws: synced() of abi_scope.hpp, which this file cannot include (it
-// defines its own StageTimer and blocks1d).  Argument checks stay in front of it.
-template <class F>
-static void stream_scope(hipStream_t st, F &&body)
+// the caller's host visibilities (weighted with wgt_host unless it is NULL) -> the dirty image at dirty_dev, resident in HBM
+template <class T>
+static void vis2dirty_upload(pfbhip_gridder *g, const T *vis_host, const T *wgt_host, double *dirty_dev)
 {
-    try {
-        body();
-    } catch (...) {
-        (void)hipStreamSynchronize(st);
-        throw;
-    }
-    PFB_HIP(hipStreamSynchronize(st));
-}
-
-// the uploaded visibilities -> dirty image (device)
-static void vis2dirty_device(pfbhip_gridder *g, bool weighted, double *dirty_dev)
-{
-    permute_in(g, weighted);
+    g->upload_vis_wgt(vis_host, wgt_host);
+    permute_in(g, wgt_host != nullptr);
     g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, dirty_dev);
 }
 
@@ -2321,21 +2283,10 @@ template <class T>
 static void vis2dirty_host(pfbhip_gridder *g, const T *vis_host, const T *wgt_host, T *dirty_host)
 {
     PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-    g->upload_vis_wgt(vis_host, wgt_host);
-    vis2dirty_device(g, wgt_host != nullptr, g->d_img.p);
-    g->download(g->d_img.p, size_t(g->prm.nx * g->prm.ny), dirty_host);
-    PFB_HIP(hipStreamSynchronize(g->stream));
-}
-
-template <class T>
-static void degrid_to_host(pfbhip_gridder *g, const double *img_dev, const T *wgt_host, T *vis_host);
-
-template <class T>
-static void dirty2vis_host(pfbhip_gridder *g, const T *dirty_host, const T *wgt_host, T *vis_host)
-{
-    PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
-    g->upload(dirty_host, size_t(g->prm.nx * g->prm.ny), g->d_img.p);
-    degrid_to_host(g, g->d_img.p, wgt_host, vis_host);
+    synced(g->stream, [&] {
+        vis2dirty_upload(g, vis_host, wgt_host, g->d_img.p);
+        g->download(g->d_img.p, size_t(g->prm.nx * g->prm.ny), dirty_host);
+    });
 }
 
 // the degrid of an image resident in HBM and the un-sort of its visibilities into the caller's (nrow, nchan) order
@@ -2356,20 +2307,36 @@ static void degrid_to_host(pfbhip_gridder *g, const double *img_dev, const T *wg
         PFB_HIP(hipGetLastError());
         g->download(reinterpret_cast<const double *>(g->d_vis.p), size_t(g->nvis) * 2, vis_host);
     }
-    PFB_HIP(hipStreamSynchronize(st));
+}
+
+template <class T>
+static void dirty2vis_host(pfbhip_gridder *g, const T *dirty_host, const T *wgt_host, T *vis_host)
+{
+    PFB_REQUIRE(g && dirty_host && (vis_host || g->nvis == 0), "NULL argument");
+    synced(g->stream, [&] {
+        g->upload(dirty_host, size_t(g->prm.nx * g->prm.ny), g->d_img.p);
+        degrid_to_host(g, g->d_img.p, wgt_host, vis_host);
+    });
+}
+
+// d_swgt = the weights of the Hessian applies in tile-sorted order (ones where wgt_dev is NULL)
+static void bind_weights(pfbhip_gridder *g, const double *wgt_dev)
+{
+    g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
+    if (g->info.nactive)
+        hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->d_src.p, g->info.nactive, wgt_dev,
+                           g->d_swgt.p);
+    PFB_HIP(hipGetLastError());
 }
 
 template <class T>
 static void set_weights_host(pfbhip_gridder *g, const T *wgt_host)
 {
     PFB_REQUIRE(g, "NULL handle");
-    g->upload_vis_wgt<T>(nullptr, wgt_host);
-    g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
-    if (g->info.nactive)
-        hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->d_src.p, g->info.nactive,
-                           wgt_host ? g->d_wgt.p : nullptr, g->d_swgt.p);
-    PFB_HIP(hipGetLastError());
-    PFB_HIP(hipStreamSynchronize(g->stream));
+    synced(g->stream, [&] {
+        g->upload_vis_wgt<T>(nullptr, wgt_host);
+        bind_weights(g, wgt_host ? g->d_wgt.p : nullptr);
+    });
     g->weights_bound = true;
 }
 
@@ -2415,16 +2382,29 @@ static void hessian_host(pfbhip_gridder *g, const T *x_host, const T *beam_host,
 {
     PFB_REQUIRE(g && x_host && out_host, "NULL argument");
     const size_t npix = size_t(g->prm.nx * g->prm.ny);
-    g->d_img.ensure(npix);
-    g->d_img2.ensure(npix);
-    g->upload(x_host, npix, g->d_img.p);
-    if (beam_host) {
-        g->d_beam.ensure(npix);
-        g->upload(beam_host, npix, g->d_beam.p);
-    }
-    hessian_dev_impl(g, g->d_img.p, beam_host ? g->d_beam.p : nullptr, eta, wsum, g->d_img2.p);
-    g->download(g->d_img2.p, npix, out_host);
-    PFB_HIP(hipStreamSynchronize(g->stream));
+    synced(g->stream, [&] {
+        g->d_img.ensure(npix);
+        g->d_img2.ensure(npix);
+        g->upload(x_host, npix, g->d_img.p);
+        hessian_dev_impl(g, g->d_img.p, g->bind_beam(beam_host), eta, wsum, g->d_img2.p);
+        g->download(g->d_img2.p, npix, out_host);
+    });
+}
+
+// the operator of the device solvers: out = Hessian(in) with the beam (resident, or NULL), eta and wsum of the call
+static auto hessian_op(pfbhip_gridder *g, const double *beam_dev, double eta, double wsum)
+{
+    return [=](const double *in, double *out) { hessian_dev_impl(g, in, beam_dev, eta, wsum, out); };
+}
+
+// The CG solve on images resident in HBM: x_dev holds x0 on entry (zeros unless has_x0), the solution on exit.  cg comes from
+// the caller, which declares it in front of its scope.
+static void cg_solve(pfbhip_gridder *g, DevCG &cg, const double *beam_dev, double eta, double wsum, const double *rhs_dev,
+                     double *x_dev, int has_x0, double tol, int maxit, int minit, pfbhip_cg_info *info)
+{
+    PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the CG solve");
+    if (!has_x0) PFB_HIP(hipMemsetAsync(x_dev, 0, size_t(cg.n) * sizeof(double), g->stream));
+    cg.solve(hessian_op(g, beam_dev, eta, wsum), rhs_dev, x_dev, tol, maxit, minit, info);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2482,24 +2462,23 @@ int pfbhip_gridder_get_binmap(pfbhip_gridder *g, int32_t *iu0, int32_t *iv0, int
     return guarded([&] {
         PFB_REQUIRE(g, "NULL handle");
         hipStream_t st = g->stream;
-        const int64_t n = g->nvis;
-        if (n && (iu0 || iv0 || p0 || flip)) {
-            DevBuf<int32_t> a(n), b(n), c(n);
-            DevBuf<uint8_t> f(n);
-            hipLaunchKernelGGL(k_binmap, blocks1d(n), dim3(256), 0, st, g->map, a.p, b.p, c.p, f.p);
-            PFB_HIP(hipGetLastError());
-            // the plan's u is the caller's v
-            if (iu0) PFB_HIP(hipMemcpyAsync(iu0, b.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            if (iv0) PFB_HIP(hipMemcpyAsync(iv0, a.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            if (p0) PFB_HIP(hipMemcpyAsync(p0, c.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            if (flip) PFB_HIP(hipMemcpyAsync(flip, f.p, n, hipMemcpyDeviceToHost, st));
-            PFB_HIP(hipStreamSynchronize(st));
-        }
-        if (order && g->info.nactive) {
-            std::vector<uint32_t> src(size_t(g->info.nactive));
-            PFB_HIP(hipMemcpy(src.data(), g->d_src.p, src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (size_t j = 0; j < src.size(); ++j) order[j] = int64_t(src[j] & 0x7FFFFFFFu);
-        }
+        const int64_t n = (iu0 || iv0 || p0 || flip) ? g->nvis : 0;  // the index arrays are computed if one of them is asked for
+        DevBuf<int32_t> a(n), b(n), c(n);
+        DevBuf<uint8_t> f(n);
+        std::vector<uint32_t> src(order ? size_t(g->info.nactive) : 0);
+        synced(st, [&] {
+            if (n) {
+                hipLaunchKernelGGL(k_binmap, blocks1d(n), dim3(256), 0, st, g->map, a.p, b.p, c.p, f.p);
+                PFB_HIP(hipGetLastError());
+                // the plan's u is the caller's v
+                if (iu0) PFB_HIP(hipMemcpyAsync(iu0, b.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                if (iv0) PFB_HIP(hipMemcpyAsync(iv0, a.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                if (p0) PFB_HIP(hipMemcpyAsync(p0, c.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                if (flip) PFB_HIP(hipMemcpyAsync(flip, f.p, n, hipMemcpyDeviceToHost, st));
+            }
+            if (!src.empty()) PFB_HIP(hipMemcpyAsync(src.data(), g->d_src.p, src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        });
+        for (size_t j = 0; j < src.size(); ++j) order[j] = int64_t(src[j] & 0x7FFFFFFFu);
     });
 }
 
@@ -2512,9 +2491,7 @@ int pfbhip_gridder_vis2dirty_dev(pfbhip_gridder *g, const double *vis_host, cons
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && (vis_host || g->nvis == 0), "NULL argument");
-        g->upload_vis_wgt(vis_host, wgt_host);
-        vis2dirty_device(g, wgt_host != nullptr, dirty_dev);
-        PFB_HIP(hipStreamSynchronize(g->stream));
+        synced(g->stream, [&] { vis2dirty_upload(g, vis_host, wgt_host, dirty_dev); });
     });
 }
 
@@ -2525,17 +2502,18 @@ int pfbhip_gridder_grid_plane(pfbhip_gridder *g, const double *vis_host, const d
         PFB_REQUIRE(g && grid_host && vis_host, "NULL argument");
         PFB_REQUIRE(plane >= 0 && plane < g->info.nplanes, "plane %lld out of range", (long long)plane);
         hipStream_t st = g->stream;
-        g->upload_vis_wgt(vis_host, wgt_host);
-        PFB_HIP(hipMemsetAsync(g->d_grid.p, 0, g->plane_stride * sizeof(double2), st));
-        if (g->info.nactive && g->info.nwork) {
-            permute_in(g, wgt_host != nullptr);
-            g->launch_grid(ApplyState{g->d_grid.p}, int(plane), 1, g->d_sval.p);
-            PFB_HIP(hipGetLastError());
-        }
-        // the plan's plane is (nv, nu) in the caller's terms: transpose on the host (debug entry)
         std::vector<double2> tmp(g->plane_stride);
-        PFB_HIP(hipMemcpyAsync(tmp.data(), g->d_grid.p, g->plane_stride * sizeof(double2), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        synced(st, [&] {
+            g->upload_vis_wgt(vis_host, wgt_host);
+            PFB_HIP(hipMemsetAsync(g->d_grid.p, 0, g->plane_stride * sizeof(double2), st));
+            if (g->info.nactive && g->info.nwork) {
+                permute_in(g, wgt_host != nullptr);
+                g->launch_grid(ApplyState{g->d_grid.p}, int(plane), 1, g->d_sval.p);
+                PFB_HIP(hipGetLastError());
+            }
+            PFB_HIP(hipMemcpyAsync(tmp.data(), g->d_grid.p, g->plane_stride * sizeof(double2), hipMemcpyDeviceToHost, st));
+        });
+        // the plan's plane is (nv, nu) in the caller's terms: transpose on the host (debug entry)
         const int64_t pu = g->info.nu, pv = g->info.nv;  // plan rows / columns = caller's nv / nu
         double2 *out = reinterpret_cast<double2 *>(grid_host);
         for (int64_t a0 = 0; a0 < pu; a0 += 32)
@@ -2555,7 +2533,7 @@ int pfbhip_gridder_dirty2vis_dev(pfbhip_gridder *g, const double *dirty_dev, con
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && (vis_host || g->nvis == 0), "NULL argument");
-        degrid_to_host<double>(g, dirty_dev, wgt_host, vis_host);
+        synced(g->stream, [&] { degrid_to_host<double>(g, dirty_dev, wgt_host, vis_host); });
     });
 }
 
@@ -2565,14 +2543,14 @@ int pfbhip_gridder_set_weights(pfbhip_gridder *g, const double *wgt_host)
 }
 
 // ---- row-ordered DEVICE arrays: one correlation of a resident (ncorr, nrow, nchan) chunk (vischunk.hip).  Each entry checks
-// its arguments, then enqueues everything inside one stream_scope: it returns with the plan's stream idle. ----
+// its arguments, then enqueues everything inside one synced(), like every entry of this file. ----
 
-// vis2dirty of gridder.py:587-614 of the reference: vis2dirty_device without upload_vis_wgt
+// vis2dirty of gridder.py:587-614 of the reference: vis2dirty_upload without the upload
 int pfbhip_gridder_vis2dirty_rows_dev(pfbhip_gridder *g, const double *vis_dev, const double *wgt_dev, double *dirty_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && (vis_dev || g->nvis == 0), "NULL argument");
-        stream_scope(g->stream, [&] {
+        synced(g->stream, [&] {
             permute_in_rows(g, reinterpret_cast<const double2 *>(vis_dev), wgt_dev);
             g->grid_and_finalize(ApplyState{g->d_grid.p}, g->d_sval.p, nullptr, 1.0, 0.0, nullptr, dirty_dev);
         });
@@ -2590,7 +2568,7 @@ int pfbhip_gridder_psf_rows_signed_dev(pfbhip_gridder *g, const double *wgt_dev,
         const double x0 = g->uprm.center_x, y0 = g->uprm.center_y;
         PFB_REQUIRE(x0 * x0 + y0 * y0 < 1.0, "phase centre (%g, %g) is not on the sphere", x0, y0);
         const double nm1 = std::sqrt(1.0 - x0 * x0 - y0 * y0) - 1.0;
-        stream_scope(g->stream, [&] {
+        synced(g->stream, [&] {
             if (g->info.nactive)
                 hipLaunchKernelGGL(k_permute_in_psf, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->map, g->d_src.p,
                                    g->info.nactive, wgt_dev, int(x0 != 0.0 || y0 != 0.0), ramp_sign * x0, ramp_sign * y0, ramp_sign * nm1,
@@ -2611,13 +2589,7 @@ int pfbhip_gridder_set_weights_dev(pfbhip_gridder *g, const double *wgt_dev)
 {
     return guarded([&] {
         PFB_REQUIRE(g, "NULL handle");
-        g->d_swgt.ensure(size_t(std::max<int64_t>(g->info.nactive, 1)));
-        stream_scope(g->stream, [&] {
-            if (g->info.nactive)
-                hipLaunchKernelGGL(k_gather_f64, blocks1d(g->info.nactive), dim3(256), 0, g->stream, g->d_src.p, g->info.nactive, wgt_dev,
-                                   g->d_swgt.p);
-            PFB_HIP(hipGetLastError());
-        });
+        synced(g->stream, [&] { bind_weights(g, wgt_dev); });
         g->weights_bound = true;
     });
 }
@@ -2628,7 +2600,7 @@ int pfbhip_gridder_dirty2vis_rows_dev(pfbhip_gridder *g, const double *dirty_dev
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && (vis_dev || g->nvis == 0), "NULL argument");
-        stream_scope(g->stream, [&] {
+        synced(g->stream, [&] {
             ApplyState a{g->d_grid.p};
             g->prepare_and_degrid(a, dirty_dev, nullptr, g->d_sacc.p);
             if (g->nvis)
@@ -2649,8 +2621,7 @@ int pfbhip_gridder_residual_dev(pfbhip_gridder *g, const double *model_dev, cons
     return guarded([&] {
         PFB_REQUIRE(g && model_dev && acc_dev && out_dev, "NULL argument");
         PFB_REQUIRE(model_dev != out_dev, "the residual cannot overwrite the model image");
-        apply_op(g, model_dev, beam_dev, nullptr, -1.0, 1.0, acc_dev, out_dev);
-        PFB_HIP(hipStreamSynchronize(g->stream));
+        synced(g->stream, [&] { apply_op(g, model_dev, beam_dev, nullptr, -1.0, 1.0, acc_dev, out_dev); });
     });
 }
 
@@ -2660,8 +2631,7 @@ int pfbhip_gridder_hessian_dev(pfbhip_gridder *g, const double *x_dev, const dou
     return guarded([&] {
         PFB_REQUIRE(g && x_dev && out_dev, "NULL argument");
         PFB_REQUIRE(x_dev != out_dev, "in-place Hessian is not supported");
-        hessian_dev_impl(g, x_dev, beam_dev, eta, wsum, out_dev);
-        PFB_HIP(hipStreamSynchronize(g->stream));
+        synced(g->stream, [&] { hessian_dev_impl(g, x_dev, beam_dev, eta, wsum, out_dev); });
     });
 }
 
@@ -2699,24 +2669,16 @@ int pfbhip_gridder_cg(pfbhip_gridder *g, const double *beam_host, double eta, do
 {
     return guarded([&] {
         PFB_REQUIRE(g && rhs_host && x_host, "NULL argument");
-        PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the CG solve");
         hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        DevBuf<double> b{size_t(npix)}, x{size_t(npix)};
-        PFB_HIP(hipMemcpyAsync(b.p, rhs_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-        if (has_x0) PFB_HIP(hipMemcpyAsync(x.p, x_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-        else PFB_HIP(hipMemsetAsync(x.p, 0, size_t(npix) * sizeof(double), st));
-        const double *beam = nullptr;
-        if (beam_host) {
-            g->d_beam.ensure(size_t(npix));
-            PFB_HIP(hipMemcpyAsync(g->d_beam.p, beam_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-            beam = g->d_beam.p;
-        }
-        DevCG cg(npix, st);
-        cg.solve([&](const double *in, double *out) { hessian_dev_impl(g, in, beam, eta, wsum, out); }, b.p, x.p, tol,
-                 maxit, minit, info);
-        PFB_HIP(hipMemcpyAsync(x_host, x.p, size_t(npix) * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        const size_t npix = size_t(g->prm.nx * g->prm.ny);
+        DevBuf<double> b{npix}, x{npix};
+        DevCG cg(int64_t(npix), st);
+        synced(st, [&] {
+            g->upload(rhs_host, npix, b.p);
+            if (has_x0) g->upload(x_host, npix, x.p);
+            cg_solve(g, cg, g->bind_beam(beam_host), eta, wsum, b.p, x.p, has_x0, tol, maxit, minit, info);
+            g->download(x.p, npix, x_host);
+        });
     });
 }
 
@@ -2725,14 +2687,8 @@ int pfbhip_gridder_cg_dev(pfbhip_gridder *g, const double *beam_dev, double eta,
 {
     return guarded([&] {
         PFB_REQUIRE(g && rhs_dev && x_dev, "NULL argument");
-        PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the CG solve");
-        hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        if (!has_x0) PFB_HIP(hipMemsetAsync(x_dev, 0, size_t(npix) * sizeof(double), st));
-        DevCG cg(npix, st);
-        cg.solve([&](const double *in, double *out) { hessian_dev_impl(g, in, beam_dev, eta, wsum, out); }, rhs_dev, x_dev, tol,
-                 maxit, minit, info);
-        PFB_HIP(hipStreamSynchronize(st));
+        DevCG cg(g->prm.nx * g->prm.ny, g->stream);
+        synced(g->stream, [&] { cg_solve(g, cg, beam_dev, eta, wsum, rhs_dev, x_dev, has_x0, tol, maxit, minit, info); });
     });
 }
 
@@ -2743,20 +2699,14 @@ int pfbhip_gridder_power_method(pfbhip_gridder *g, const double *beam_host, doub
         PFB_REQUIRE(g && b_host && maxit >= 0, "bad arguments");
         PFB_REQUIRE(g->weights_bound, "call pfbhip_gridder_set_weights before the power method");
         hipStream_t st = g->stream;
-        const int64_t npix = g->prm.nx * g->prm.ny;
-        DevBuf<double> bp{size_t(npix)};
-        PFB_HIP(hipMemcpyAsync(bp.p, b_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-        const double *beam = nullptr;
-        if (beam_host) {
-            g->d_beam.ensure(size_t(npix));
-            PFB_HIP(hipMemcpyAsync(g->d_beam.p, beam_host, size_t(npix) * sizeof(double), hipMemcpyHostToDevice, st));
-            beam = g->d_beam.p;
-        }
-        DevPower pm(npix, st);
-        pm.run([&](const double *in, double *out) { hessian_dev_impl(g, in, beam, eta, wsum, out); }, [](double *) {}, bp.p, tol,
-               maxit, info);
-        PFB_HIP(hipMemcpyAsync(b_host, bp.p, size_t(npix) * sizeof(double), hipMemcpyDeviceToHost, st));
-        PFB_HIP(hipStreamSynchronize(st));
+        const size_t npix = size_t(g->prm.nx * g->prm.ny);
+        DevBuf<double> bp{npix};
+        DevPower pm(int64_t(npix), st);
+        synced(st, [&] {
+            g->upload(b_host, npix, bp.p);
+            pm.run(hessian_op(g, g->bind_beam(beam_host), eta, wsum), [](double *) {}, bp.p, tol, maxit, info);
+            g->download(bp.p, npix, b_host);
+        });
     });
 }
 
@@ -2764,9 +2714,10 @@ int pfbhip_gridder_degrid_dev(pfbhip_gridder *g, const double *dirty_dev, double
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && vis_sorted_dev, "NULL argument");
-        ApplyState a{g->d_grid.p};
-        g->prepare_and_degrid(a, dirty_dev, nullptr, reinterpret_cast<double2 *>(vis_sorted_dev));
-        PFB_HIP(hipStreamSynchronize(g->stream));
+        synced(g->stream, [&] {
+            ApplyState a{g->d_grid.p};
+            g->prepare_and_degrid(a, dirty_dev, nullptr, reinterpret_cast<double2 *>(vis_sorted_dev));
+        });
     });
 }
 
@@ -2774,8 +2725,10 @@ int pfbhip_gridder_grid_dev(pfbhip_gridder *g, const double *vis_sorted_dev, dou
 {
     return guarded([&] {
         PFB_REQUIRE(g && dirty_dev && vis_sorted_dev, "NULL argument");
-        g->grid_and_finalize(ApplyState{g->d_grid.p}, reinterpret_cast<const double2 *>(vis_sorted_dev), nullptr, 1.0, 0.0, nullptr, dirty_dev);
-        PFB_HIP(hipStreamSynchronize(g->stream));
+        synced(g->stream, [&] {
+            g->grid_and_finalize(ApplyState{g->d_grid.p}, reinterpret_cast<const double2 *>(vis_sorted_dev), nullptr, 1.0, 0.0, nullptr,
+                                 dirty_dev);
+        });
     });
 }
 
@@ -2783,7 +2736,7 @@ int pfbhip_gridder_profile(pfbhip_gridder *g, int enable)
 {
     return guarded([&] {
         PFB_REQUIRE(g, "NULL handle");
-        g->timer.collect();
+        g->timer.collect(g->stage_ms, g->stage_calls);
         g->timer.enabled = enable != 0;
     });
 }
@@ -2792,13 +2745,13 @@ int pfbhip_gridder_profile_get(pfbhip_gridder *g, double *ms, int64_t *calls, in
 {
     return guarded([&] {
         PFB_REQUIRE(g, "NULL handle");
-        g->timer.collect();
+        g->timer.collect(g->stage_ms, g->stage_calls);
         for (int s = 0; s < PFBHIP_NSTAGES; ++s) {
-            if (ms) ms[s] = g->timer.ms[s];
-            if (calls) calls[s] = g->timer.calls[s];
+            if (ms) ms[s] = g->stage_ms[s];
+            if (calls) calls[s] = g->stage_calls[s];
             if (reset) {
-                g->timer.ms[s] = 0;
-                g->timer.calls[s] = 0;
+                g->stage_ms[s] = 0;
+                g->stage_calls[s] = 0;
             }
         }
     });
