@@ -405,6 +405,22 @@ int pfbhip_imaging_weights_dev(const double *uvw_host, const double *freq_host, 
                                int64_t ncorr, int64_t nrow, int64_t nchan, int64_t nx, int64_t ny, double cell_x, double cell_y,
                                double usign, double vsign, double robust, double filter_level, int64_t npix_super,
                                double *counts_out_host /* or NULL */);
+/* Weighted averaging of a resident chunk over channel bins of fixed width and caller-supplied row bins (csrc/chunkavg.hip):
+ * steps 2 to 4 of utils/stokes2vis.py:196-286 (drop flagged rows, time_and_channel, bda with min_nchan = nchan) in one
+ * out-of-place pass.  vis_dev (ncorr, nrow, nchan) complex128, wgt_dev the same shape float64, mask_dev (nrow, nchan) uint8.
+ * Output channel q covers input channels [q chan_bin, min((q + 1) chan_bin, nchan)), nchan_out = ceil(nchan / chan_bin).
+ * Row bins are a CSR on the HOST: row_start_host (nrow_out + 1) and members_host (nkept) input rows, strictly ascending inside
+ * a bin; both NULL: the identity (nrow_out == nkept == nrow).  With K the unmasked input samples of output sample (R, q):
+ * wgt_out = sum_K wgt, vis_out = sum_K wgt vis / wgt_out, mask_out = (K not empty); an empty K or wgt_out == 0 gives exact
+ * zeros, a K of one sample its visibility unchanged.  No atomics: bit-identical from call to call.  The outputs
+ * (ncorr, nrow_out, nchan_out) / (nrow_out, nchan_out) are the caller's and may not overlap the inputs or each other.
+ * Everything is validated on the host before anything is launched (PFBHIP_ERR_INVALID): ncorr in [1, 65535], chan_bin >= 1,
+ * row_start[0] == 0, non-decreasing, row_start[nrow_out] == nkept, every member in [0, nrow), pointers non-NULL unless
+ * their arrays are empty. */
+int pfbhip_chunk_average_dev(const double *vis_dev, const double *wgt_dev, const uint8_t *mask_dev, int64_t ncorr, int64_t nrow,
+                             int64_t nchan, int64_t chan_bin, const int64_t *row_start_host /* or NULL */,
+                             const int64_t *members_host /* or NULL */, int64_t nkept, int64_t nrow_out, double *vis_out_dev,
+                             double *wgt_out_dev, uint8_t *mask_out_dev);
 
 /* ---- one `pfb hci` snapshot on a resident chunk (csrc/snapshot.hip): the array steps of
  * src/pfb_imaging/utils/stokes2im.py::stokes_image around its two vis2dirty calls per Stokes.  Every entry validates first and

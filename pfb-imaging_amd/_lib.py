@@ -145,7 +145,7 @@ SYMBOLS = (
     "pfbhip_gridder_vis2dirty_rows_dev", "pfbhip_gridder_psf_rows_dev", "pfbhip_gridder_set_weights_dev",
     "pfbhip_gridder_dirty2vis_rows_dev", "pfbhip_chunk_wsum_dev", "pfbhip_chunk_l2_reweight_dev", "pfbhip_imaging_weights_dev",
     "pfbhip_chunk_rephase_residual_dev", "pfbhip_chunk_l2_reweight_joint_dev", "pfbhip_gridder_psf_rows_signed_dev",
-    "pfbhip_snapshot_finish_dev",
+    "pfbhip_snapshot_finish_dev", "pfbhip_chunk_average_dev",
 )
 
 _lib = None
@@ -169,6 +169,8 @@ def lib():
         L.pfbhip_hash64.restype = ct.c_uint64
         L.pfbhip_hash64.argtypes = [ct.c_void_p, ct.c_size_t]
         L.pfbhip_psfconv_uses_rowfft.argtypes = [ct.c_void_p, ct.POINTER(cint)]
+        if hasattr(L, "pfbhip_chunk_average_dev"):  # (a stale library is reported by name where SYMBOLS is checked)
+            L.pfbhip_chunk_average_dev.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -39,6 +39,69 @@ def _adopt(a, shape, dtype, name):
     return a
 
 
+def _check_chan_bin(chan_bin, name="chan_bin"):
+    if isinstance(chan_bin, bool) or not isinstance(chan_bin, (int, np.integer)):
+        raise TypeError(f"{name} must be an integer, not {type(chan_bin).__name__}")
+    if chan_bin < 1:
+        raise ValueError(f"{name} = {chan_bin} must be at least 1")
+    return int(chan_bin)
+
+
+def _check_chan_width(chan_width, nchan):
+    if chan_width is None:
+        return None
+    chan_width = np.asarray(chan_width)
+    if chan_width.dtype.kind not in "fiu":
+        raise TypeError(f"chan_width must be real, not {chan_width.dtype}")
+    if chan_width.shape != (nchan,):
+        raise ValueError(f"chan_width shape {chan_width.shape} != {(nchan,)}")
+    return as_c(chan_width, np.float64)
+
+
+def row_bins(row_map, nrow, nrow_out=None):
+    """``(row_start (nrow_out + 1), members (nkept), nrow_out)`` int64: the CSR of ``row_map (nrow)``, whose entry ``r`` is the
+    output row of input row ``r`` in ``[0, nrow_out)`` or ``-1`` to drop it.  A stable sort keeps the members of a bin in
+    ascending input-row order.  ``nrow_out`` defaults to ``row_map.max() + 1``.  Host work only."""
+    row_map = np.asarray(row_map)
+    if row_map.dtype.kind not in "iu":
+        raise TypeError(f"row_map must be of an integer type, not {row_map.dtype}")
+    if row_map.shape != (nrow,):
+        raise ValueError(f"row_map shape {row_map.shape} != {(nrow,)}")
+    row_map = row_map.astype(np.int64, copy=False)
+    if nrow_out is None:
+        nrow_out = int(row_map.max()) + 1 if nrow else 0
+    elif isinstance(nrow_out, bool) or not isinstance(nrow_out, (int, np.integer)) or nrow_out < 0:
+        raise ValueError(f"nrow_out = {nrow_out!r} must be a non-negative integer")
+    nrow_out = max(int(nrow_out), 0)
+    if nrow and (row_map.min() < -1 or row_map.max() >= nrow_out):
+        raise ValueError(f"row_map entries must lie in [-1, {nrow_out}), got [{row_map.min()}, {row_map.max()}]")
+    kept = np.flatnonzero(row_map >= 0)
+    members = kept[np.argsort(row_map[kept], kind="stable")].astype(np.int64)
+    row_start = np.zeros(nrow_out + 1, dtype=np.int64)
+    np.cumsum(np.bincount(row_map[kept], minlength=nrow_out), out=row_start[1:])
+    return row_start, members, nrow_out
+
+
+def channel_bins(freq, chan_bin, chan_width=None):
+    """``(freq_out, chan_width_out)`` of channel bins ``[q chan_bin, min((q + 1) chan_bin, nchan))``: the mean of a bin's
+    frequencies and the sum of its widths (``None`` without ``chan_width``)."""
+    starts = np.arange(0, freq.size, chan_bin)
+    counts = np.minimum(starts + chan_bin, freq.size) - starts
+    freq_out = np.add.reduceat(freq, starts) / counts
+    return freq_out, None if chan_width is None else np.add.reduceat(chan_width, starts)
+
+
+def mean_uvw(uvw, row_start, members):
+    """``(nrow_out, 3)``: the plain mean of every bin's member rows, masked or not, in float64; zeros for a bin without members"""
+    counts = np.diff(row_start)
+    out = np.zeros((counts.size, 3))
+    rows = np.repeat(np.arange(counts.size), counts)
+    for j in range(3):
+        out[:, j] = np.bincount(rows, weights=uvw[members, j], minlength=counts.size)
+    out[counts > 0] /= counts[counts > 0, None]
+    return out
+
+
 class VisChunk:
     """``uvw (nrow, 3)``, ``freq (nchan)`` (host), ``vis, wgt (ncorr, nrow, nchan)`` and ``mask (nrow, nchan)``: each of the
     last three a host array, uploaded once (``vis`` as complex128, ``wgt`` as float64, ``mask`` as uint8, non-zero = keep), or
@@ -69,6 +132,7 @@ class VisChunk:
         self.uvw, self.freq = as_c(uvw, np.float64), as_c(freq, np.float64)
         self.ncorr, self.nrow, self.nchan = ncorr, nrow, nchan
         self.nvis = nrow * nchan
+        self.chan_width = None
         self.vis = self.wgt = self.mask = None
         try:
             self.vis = vis if isinstance(vis, DeviceArray) else DeviceArray.from_host(as_c(vis, np.complex128))
@@ -83,19 +147,37 @@ class VisChunk:
             raise
 
     @classmethod
-    def from_weight_data(cls, uvw, freq, data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode):
+    def from_weight_data(cls, uvw, freq, data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode,
+                         chan_average=1, drop_flagged_rows=False, chan_width=None):
         """The chunk of raw correlations: ``weight_data_dev(corr_first=True, with_mask=True)`` (weighting.py:274-468 of the
-        reference) leaves Stokes visibilities, weights and the mask ``~flag.any(-1)`` in HBM, and the chunk adopts them."""
+        reference) leaves Stokes visibilities, weights and the mask ``~flag.any(-1)`` in HBM, and the chunk adopts them.
+
+        ``chan_average > 1`` and ``drop_flagged_rows`` are steps 2 and 3 of ``pfb init`` (utils/stokes2vis.py:215-260): the
+        chunk is averaged over ``chan_average`` channels and loses the rows without an unmasked sample
+        (:meth:`average` with :meth:`rows_with_data`), and the chunk that comes back is the averaged one; the first is closed.
+        ``chan_width (nchan)`` is kept as ``.chan_width`` and summed over the bins."""
         from .utils.weighting import weight_data_dev
 
+        chan_average = _check_chan_bin(chan_average, "chan_average")
+        chan_width = _check_chan_width(chan_width, np.size(freq))
         vis, wgt, mask = weight_data_dev(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, ant2, pol, product, nc, wgt_mode,
                                          corr_first=True, with_mask=True)
         try:
-            return cls(uvw, freq, vis, wgt, mask)
+            first = cls(uvw, freq, vis, wgt, mask)
         except Exception:
             for d in (vis, wgt, mask):
                 d.free()
             raise
+        first.chan_width = chan_width
+        row_map = first.rows_with_data() if drop_flagged_rows else None
+        if row_map is not None and (row_map >= 0).all():
+            row_map = None
+        if chan_average == 1 and row_map is None:
+            return first
+        try:
+            return first.average(chan_average, row_map, chan_width=chan_width)
+        finally:
+            first.close()
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -120,6 +202,63 @@ class VisChunk:
         if not 0 <= c < self.ncorr:
             raise ValueError(f"correlation {c} of {self.ncorr}")
         return c * self.nvis
+
+    # -- averaging (utils/stokes2vis.py:215-286; csrc/chunkavg.hip) -------------------------------------------------------
+    def rows_with_data(self):
+        """The ``row_map`` that keeps, in order, the rows with at least one unmasked sample and drops the others: the
+        reference's ``mrow`` (stokes2vis.py:217) for :meth:`average`.  From the host copy of the mask; no device call."""
+        keep = self.mask_host.any(axis=1)
+        return np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+
+    def average(self, chan_bin=1, row_map=None, nrow_out=None, uvw_out=None, chan_width=None):
+        """A NEW chunk: this one averaged over channel bins of ``chan_bin`` channels (the last may be partial) and over the row
+        bins of ``row_map (nrow)``, whose entry ``r`` is the output row of input row ``r`` or ``-1`` to drop it (``None``: every
+        row stays where it is); ``nrow_out`` defaults to ``row_map.max() + 1``.  With ``K`` the unmasked samples of an output
+        sample: ``wgt = sum_K wgt``, ``vis = sum_K wgt vis / wgt``, ``mask = K not empty``; an empty ``K`` or a zero weight sum
+        gives exact zeros.  ``freq`` becomes the mean of each bin's frequencies, ``chan_width`` (``.chan_width`` of the new
+        chunk, ``None`` if not given) the sum of its widths, ``uvw`` the plain mean of a bin's member rows unless ``uvw_out
+        (nrow_out, 3)`` is given.  This chunk is untouched and stays the caller's to close."""
+        chan_bin = _check_chan_bin(chan_bin)
+        chan_width = _check_chan_width(chan_width, self.nchan)
+        ident = row_map is None
+        if ident:
+            if nrow_out is not None and nrow_out != self.nrow:
+                raise ValueError(f"nrow_out = {nrow_out} without a row_map must be nrow = {self.nrow}")
+            nrow_out = self.nrow
+        else:
+            row_start, members, nrow_out = row_bins(row_map, self.nrow, nrow_out)
+            ident = nrow_out == self.nrow and np.array_equal(members, np.arange(self.nrow)) and (np.diff(row_start) == 1).all()
+        if ident and chan_bin == 1:
+            raise ValueError("average(chan_bin=1) with the identity row map is a no-op: it would only copy the chunk")
+        if uvw_out is not None:
+            uvw_out = np.asarray(uvw_out)
+            if uvw_out.dtype.kind not in "fiu":
+                raise TypeError(f"uvw_out must be real, not {uvw_out.dtype}")
+            if uvw_out.shape != (nrow_out, 3):
+                raise ValueError(f"uvw_out shape {uvw_out.shape} != {(nrow_out, 3)}")
+        elif ident:
+            uvw_out = self.uvw
+        else:
+            uvw_out = mean_uvw(self.uvw, row_start, members)
+        freq_out, width_out = channel_bins(self.freq, chan_bin, chan_width)
+        self._open()
+        # -- every argument has passed: the device from here on
+        shape = (self.ncorr, nrow_out, freq_out.size)
+        made = []
+        try:
+            for shp, dtype in ((shape, np.complex128), (shape, np.float64), (shape[1:], np.uint8)):
+                made.append(DeviceArray(shp, dtype))
+            vis, wgt, mask = made
+            check(lib().pfbhip_chunk_average_dev(self.vis.ptr, self.wgt.ptr, self.mask.ptr, self.ncorr, self.nrow, self.nchan,
+                                                 chan_bin, None if ident else ptr(row_start), None if ident else ptr(members),
+                                                 self.nrow if ident else members.size, nrow_out, vis.ptr, wgt.ptr, mask.ptr))
+            out = VisChunk(uvw_out, freq_out, vis, wgt, mask)
+        except Exception:
+            for d in made:
+                d.free()
+            raise
+        out.chan_width = width_out
+        return out
 
     # -- the weights, where they lie ----------------------------------------
     def wsum(self):
