@@ -2,16 +2,23 @@
 
 The library is built in-tree by ``pfb-imaging_amd/csrc/Makefile`` (hipcc, gfx950).  There is
 no fallback: if it is missing, importing any operator raises ImportError telling how to build.
+
+Every C signature comes from ``include/pfbhip.h``: the prototypes are parsed when this module is imported and ``lib()``
+sets ``restype`` and ``argtypes`` on every entry point, so call sites pass plain Python values and ctypes refuses a wrong
+count or a float where the header says integer.  A new entry point is declared in the header and nowhere else on the Python
+side; only a new struct needs its mirror below.
 """
 
 import ctypes as ct
 import os
+import re
 import threading
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpfbhip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pfbhip.h")
 
 i32 = ct.c_int32
 i64 = ct.c_int64
@@ -101,58 +108,60 @@ class StokesSpec(ct.Structure):
                 ("reserved", i32)]
 
 
-# every symbol include/pfbhip.h declares (tests check the library exports all of them)
-SYMBOLS = (
-    "pfbhip_last_error", "pfbhip_device_count", "pfbhip_set_device", "pfbhip_get_device", "pfbhip_device_name",
-    "pfbhip_mem_info", "pfbhip_device_cache", "pfbhip_resize_thread_pool", "pfbhip_thread_pool_size", "pfbhip_good_size",
-    "pfbhip_hash64", "pfbhip_host_alloc", "pfbhip_host_free", "pfbhip_malloc", "pfbhip_free", "pfbhip_memcpy_h2d", "pfbhip_memcpy_d2h", "pfbhip_memcpy_d2d", "pfbhip_memset",
-    "pfbhip_synchronize",
-    "pfbhip_gridder_create", "pfbhip_gridder_destroy", "pfbhip_gridder_get_info", "pfbhip_gridder_get_binmap",
-    "pfbhip_gridder_get_planes",
-    "pfbhip_gridder_vis2dirty", "pfbhip_gridder_vis2dirty_dev", "pfbhip_gridder_dirty2vis", "pfbhip_gridder_grid_plane",
-    "pfbhip_gridder_set_weights", "pfbhip_gridder_hessian", "pfbhip_gridder_hessian_dev", "pfbhip_gridder_residual_dev",
-    "pfbhip_gridder_vis2dirty_sp", "pfbhip_gridder_dirty2vis_sp", "pfbhip_gridder_set_weights_sp", "pfbhip_gridder_hessian_sp",
-    "pfbhip_gridder_degrid_dev", "pfbhip_gridder_grid_dev", "pfbhip_gridder_profile", "pfbhip_gridder_profile_get",
-    "pfbhip_gridder_cg", "pfbhip_gridder_cg_dev",
-    "pfbhip_r2c_2d", "pfbhip_r2c_2d_centred", "pfbhip_c2r_2d", "pfbhip_debug_rowfft", "pfbhip_debug_rowfft_shape",
-    "pfbhip_psi_create", "pfbhip_psi_destroy", "pfbhip_psi_shape", "pfbhip_psi_dot", "pfbhip_psi_hdot",
-    "pfbhip_psi_dot_dev", "pfbhip_psi_hdot_dev", "pfbhip_dual_update", "pfbhip_l21_vtilde_sum_dev",
-    "pfbhip_l21_scale_dev", "pfbhip_prox_21m", "pfbhip_positivity", "pfbhip_positivity_dev", "pfbhip_primal_dual",
-    "pfbhip_psfconv_power_method", "pfbhip_gridder_power_method",
-    "pfbhip_psfconv_create", "pfbhip_psfconv_destroy", "pfbhip_psfconv_set_psfhat", "pfbhip_psfconv_set_beam",
-    "pfbhip_psfconv_apply", "pfbhip_psfconv_apply_dev", "pfbhip_psfconv_direct", "pfbhip_psfconv_cg", "pfbhip_psfconv_uses_rowfft",
-    "pfbhip_uvcell_index", "pfbhip_compute_counts", "pfbhip_counts_divide", "pfbhip_box_sum_counts",
-    "pfbhip_filter_extreme_counts", "pfbhip_imaging_weights",
-    "pfbhip_comm_unique_id", "pfbhip_comm_create", "pfbhip_comm_destroy", "pfbhip_comm_reduce_sum",
-    "pfbhip_comm_allreduce_sum", "pfbhip_comm_allgather", "pfbhip_comm_allreduce_sum_host", "pfbhip_comm_reduce_sum_host",
-    "pfbhip_comm_allgather_host", "pfbhip_comm_barrier",
-    "pfbhip_clean_create", "pfbhip_clean_destroy", "pfbhip_clean_hogbom", "pfbhip_clean_clark",
-    "pfbhip_fb_create", "pfbhip_fb_run", "pfbhip_fb_set_weight", "pfbhip_fb_destroy",
-    "pfbhip_fb_set_weight_dev", "pfbhip_fb_iterate_dev",
-    "pfbhip_pd_create", "pfbhip_pd_run", "pfbhip_pd_set_weight", "pfbhip_pd_set_weight_dev", "pfbhip_pd_iterate_dev",
-    "pfbhip_pd_get_dual", "pfbhip_pd_get_traffic", "pfbhip_pd_destroy",
-    "pfbhip_l21_reweight_dev", "pfbhip_l21_rms_dev", "pfbhip_l21_reweight", "pfbhip_l21_rms",
-    "pfbhip_comps_create", "pfbhip_comps_destroy", "pfbhip_comps_fit", "pfbhip_comps_shape", "pfbhip_comps_get",
-    "pfbhip_comps_set_region", "pfbhip_comps_render", "pfbhip_comps_render_dev", "pfbhip_comps_regrid",
-    "pfbhip_comps_regrid_dev", "pfbhip_gridder_dirty2vis_dev",
-    "pfbhip_gaussconv_create", "pfbhip_gaussconv_destroy", "pfbhip_gaussconv_shape", "pfbhip_gaussconv_apply",
-    "pfbhip_gaussconv_apply_dev", "pfbhip_gaussconv_restore", "pfbhip_gaussconv_restore_dev", "pfbhip_gaussconv_debug_fill",
-    "pfbhip_cleanbeam_fit", "pfbhip_cleanbeam_fit_dev",
-    "pfbhip_dft_create", "pfbhip_dft_destroy", "pfbhip_dft_predict", "pfbhip_dft_predict_dev", "pfbhip_dft_predict_comps",
-    "pfbhip_dft_predict_comps_dev", "pfbhip_dft_image", "pfbhip_dft_image_dev",
-    "pfbhip_beam_regrid", "pfbhip_beam_rotate_mean",
-    "pfbhip_weight_data", "pfbhip_weight_data_sp", "pfbhip_weight_data_dev", "pfbhip_debug_copy16",
-    "pfbhip_gridder_vis2dirty_rows_dev", "pfbhip_gridder_psf_rows_dev", "pfbhip_gridder_set_weights_dev",
-    "pfbhip_gridder_dirty2vis_rows_dev", "pfbhip_chunk_wsum_dev", "pfbhip_chunk_l2_reweight_dev", "pfbhip_imaging_weights_dev",
-    "pfbhip_chunk_rephase_residual_dev", "pfbhip_chunk_l2_reweight_joint_dev", "pfbhip_gridder_psf_rows_signed_dev",
-    "pfbhip_snapshot_finish_dev", "pfbhip_chunk_average_dev",
-)
+_C_SCALARS = {"int": ct.c_int, "int32_t": i32, "int64_t": i64, "size_t": ct.c_size_t, "double": f64}
+_C_RETURNS = {"int": ct.c_int, "int64_t": i64, "uint64_t": ct.c_uint64, "const char *": ct.c_char_p}
+
+
+def parse_prototypes(text):
+    """{name: (return type, [parameter types])} of every ``RET pfbhip_name(PARAMS);`` of a header, as C type strings with
+    single spaces (``"const double *"``).  The header is regular: no struct by value, no function pointers."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    protos = {}
+    for m in re.finditer(r"([^;{}()]*?)\b(pfbhip_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret, name, params = (" ".join(g.split()) for g in m.groups())
+        # a parameter is its type followed by its name; the type keeps what is left (an unnamed one keeps nothing, and fails below)
+        types = [] if params == "void" else [re.sub(r"\w+$", "", q.strip()).strip() for q in params.split(",")]
+        protos[name] = (ret, types)
+    return protos
+
+
+def ctypes_signature(name, ret, params):
+    """(restype, argtypes) of one parsed prototype.  Anything with a ``*`` is a ``c_void_p`` (handles, out-handles, struct
+    pointers, arrays); a scalar is its own ctypes type; a type that is neither fails the import, naming the declaration."""
+    decl = f"{ret} {name}({', '.join(params) or 'void'})"
+    if ret not in _C_RETURNS:
+        raise ImportError(f"{HEADER_PATH}: unknown return type {ret!r} in `{decl}`")
+    argtypes = []
+    for t in params:
+        if "*" not in t and t not in _C_SCALARS:
+            raise ImportError(f"{HEADER_PATH}: unknown parameter type {t!r} in `{decl}`")
+        argtypes.append(vp if "*" in t else _C_SCALARS[t])
+    return _C_RETURNS[ret], argtypes
+
+
+def signatures(text):
+    """{name: (restype, argtypes)} of every prototype of the header ``text``."""
+    return {name: ctypes_signature(name, *p) for name, p in parse_prototypes(text).items()}
+
+
+def _header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f"{HEADER_PATH} not found: pfb-imaging_amd takes every C signature from it and is only ever built and "
+                          "run in its source tree.")
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+_SIGNATURES = signatures(_header())
+SYMBOLS = tuple(_SIGNATURES)  # every symbol include/pfbhip.h declares (tests check the library exports all of them)
 
 _lib = None
 
 
 def lib():
-    """The loaded library; raises ImportError (loudly) when it has not been built."""
+    """The loaded library, every entry point with the ``restype`` and ``argtypes`` its prototype in the header states;
+    raises ImportError (loudly) when it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -162,15 +171,10 @@ def lib():
                 "pfb-imaging_amd has no CPU fallback."
             )
         L = ct.CDLL(LIB_PATH)
-        L.pfbhip_last_error.restype = ct.c_char_p
-        L.pfbhip_good_size.restype = i64
-        L.pfbhip_good_size.argtypes = [i64, cint]
-        L.pfbhip_thread_pool_size.restype = cint
-        L.pfbhip_hash64.restype = ct.c_uint64
-        L.pfbhip_hash64.argtypes = [ct.c_void_p, ct.c_size_t]
-        L.pfbhip_psfconv_uses_rowfft.argtypes = [ct.c_void_p, ct.POINTER(cint)]
-        if hasattr(L, "pfbhip_chunk_average_dev"):  # (a stale library is reported by name where SYMBOLS is checked)
-            L.pfbhip_chunk_average_dev.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            f = getattr(L, name, None)  # (a stale library is reported by name where SYMBOLS is checked)
+            if f is not None:
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -202,14 +206,14 @@ def get_device():
 
 
 def set_device(device):
-    check(lib().pfbhip_set_device(cint(int(device))))
+    check(lib().pfbhip_set_device(int(device)))
 
 
 def device_cache(flush=False):
     """Bytes of released device blocks the library keeps for the next plan of the same sizes (``pfbhip_device_cache``);
     ``flush=True`` returns them to the driver.  Returns the cached bytes before the flush."""
     n = ct.c_size_t(0)
-    check(lib().pfbhip_device_cache(ct.byref(n), cint(1 if flush else 0)))
+    check(lib().pfbhip_device_cache(ct.byref(n), 1 if flush else 0))
     return n.value
 
 
@@ -297,9 +301,9 @@ def _pinned_take(nbytes):
         if _pinned_live[0] + nbytes > _pinned_cap():
             return None
     p = vp()
-    if lib().pfbhip_host_alloc(ct.byref(p), ct.c_size_t(nbytes)) != 0:
+    if lib().pfbhip_host_alloc(ct.byref(p), nbytes) != 0:
         _pinned_trim(0)
-        if lib().pfbhip_host_alloc(ct.byref(p), ct.c_size_t(nbytes)) != 0:
+        if lib().pfbhip_host_alloc(ct.byref(p), nbytes) != 0:
             return None
     _pinned_live[0] += nbytes
     return p.value
@@ -334,7 +338,7 @@ class DeviceArray:
         self.dtype = np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
         p = vp()
-        check(lib().pfbhip_malloc(ct.byref(p), ct.c_size_t(max(self.nbytes, 1))))
+        check(lib().pfbhip_malloc(ct.byref(p), max(self.nbytes, 1)))
         self.ptr = p
 
     @classmethod
@@ -347,17 +351,17 @@ class DeviceArray:
     def upload(self, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)
         assert a.nbytes == self.nbytes
-        check(lib().pfbhip_memcpy_h2d(self.ptr, ptr(a), ct.c_size_t(self.nbytes)))
+        check(lib().pfbhip_memcpy_h2d(self.ptr, ptr(a), self.nbytes))
 
     def download(self, out=None):
         if out is None:
             out = result_empty(self.shape, self.dtype)
         assert out.nbytes == self.nbytes and out.flags.c_contiguous
-        check(lib().pfbhip_memcpy_d2h(ptr(out), self.ptr, ct.c_size_t(self.nbytes)))
+        check(lib().pfbhip_memcpy_d2h(ptr(out), self.ptr, self.nbytes))
         return out
 
     def zero(self):
-        check(lib().pfbhip_memset(self.ptr, 0, ct.c_size_t(self.nbytes)))
+        check(lib().pfbhip_memset(self.ptr, 0, self.nbytes))
 
     def free(self):
         if self.ptr is not None and self.ptr.value:
@@ -455,7 +459,7 @@ def content_key(a):
                 _ro_memo_bytes[0] -= hit[0].nbytes
                 del _ro_memo[mk]
     c = np.ascontiguousarray(a)
-    key = (c.shape, c.dtype.str, int(lib().pfbhip_hash64(c.ctypes.data_as(ct.c_void_p), ct.c_size_t(c.nbytes))))
+    key = (c.shape, c.dtype.str, int(lib().pfbhip_hash64(c.ctypes.data_as(ct.c_void_p), c.nbytes)))
     if ro and a.nbytes <= _RO_MEMO_BYTES:
         with _ro_lock:
             if mk not in _ro_memo:

@@ -13,7 +13,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import CleanInfo, as_c, check, f64, i64, lib, ptr
+from ._lib import CleanInfo, as_c, check, lib, ptr
 
 INFO_FIELDS = tuple(name for name, _ in CleanInfo._fields_)
 
@@ -36,8 +36,8 @@ class CleanPlan:
         self.has_psfhat = hat is not None
         self.info = None
         self._h = ct.c_void_p()
-        check(lib().pfbhip_clean_create(i64(self.nband), i64(self.nx), i64(self.ny), i64(self.nx_psf), i64(self.ny_psf),
-                                        ptr(psf), ptr(hat), ct.byref(self._h)))
+        check(lib().pfbhip_clean_create(self.nband, self.nx, self.ny, self.nx_psf, self.ny_psf, ptr(psf), ptr(hat),
+                                        ct.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -66,8 +66,7 @@ class CleanPlan:
         model = np.empty_like(d)
         res = np.empty_like(d) if residual else None
         info = CleanInfo()
-        check(lib().pfbhip_clean_hogbom(self._h, ptr(d), f64(threshold), f64(gamma), f64(pf), i64(int(maxit)), ptr(model),
-                                        ptr(res), ct.byref(info)))
+        check(lib().pfbhip_clean_hogbom(self._h, ptr(d), threshold, gamma, pf, int(maxit), ptr(model), ptr(res), ct.byref(info)))
         status = self._finish(info)
         return (model, status, res) if residual else (model, status)
 
@@ -82,8 +81,8 @@ class CleanPlan:
         model = np.empty_like(d)
         res = np.empty_like(d) if residual else None
         info = CleanInfo()
-        check(lib().pfbhip_clean_clark(self._h, ptr(d), ptr(w), ptr(m), f64(threshold), f64(gamma), f64(pf), i64(int(maxit)),
-                                       f64(subpf), i64(int(submaxit)), ptr(model), ptr(res), ct.byref(info)))
+        check(lib().pfbhip_clean_clark(self._h, ptr(d), ptr(w), ptr(m), threshold, gamma, pf, int(maxit), subpf, int(submaxit),
+                                       ptr(model), ptr(res), ct.byref(info)))
         status = self._finish(info)
         return (model, status, res) if residual else (model, status)
 

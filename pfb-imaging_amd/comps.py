@@ -12,7 +12,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import as_c, check, cint, f64, i32, i64, lib, ptr
+from ._lib import as_c, check, cint, i64, lib, ptr
 
 _EPS = 2.0**-53
 
@@ -55,8 +55,8 @@ class Comps:
         if coeffs.shape[0] < 1:
             raise ValueError("a component model needs at least one parameter")
         self._h = ct.c_void_p()
-        check(lib().pfbhip_comps_create(i64(int(nx)), i64(int(ny)), i64(x_index.size), i32(coeffs.shape[0]), ptr(x_index),
-                                        ptr(y_index), ptr(coeffs), ct.byref(self._h)))
+        check(lib().pfbhip_comps_create(int(nx), int(ny), x_index.size, coeffs.shape[0], ptr(x_index), ptr(y_index), ptr(coeffs),
+                                        ct.byref(self._h)))
         self.nx, self.ny, self.ncomps, self.nparam = int(nx), int(ny), int(x_index.size), int(coeffs.shape[0])
         self.x_index, self.y_index, self.coeffs = x_index, y_index, coeffs
         self.host_renders = 0  # renders a caller had to make on the host (nonlinear modelf): see operators.gridder.comps2vis
@@ -84,8 +84,8 @@ class Comps:
         self = cls.__new__(cls)
         self._h = ct.c_void_p()
         n = i64(0)
-        check(lib().pfbhip_comps_fit(None if dev else ptr(cube), cube.ptr if dev else None, i64(ns), i64(nx), i64(ny), ptr(A),
-                                     i32(A.shape[0]), ct.byref(self._h), ct.byref(n)))
+        check(lib().pfbhip_comps_fit(None if dev else ptr(cube), cube.ptr if dev else None, ns, nx, ny, ptr(A), A.shape[0],
+                                     ct.byref(self._h), ct.byref(n)))
         self.nx, self.ny, self.ncomps, self.nparam = nx, ny, int(n.value), int(A.shape[0])
         self.x_index, self.y_index = np.empty(self.ncomps, np.int64), np.empty(self.ncomps, np.int64)
         self.coeffs = np.empty((self.nparam, self.ncomps), np.float64)
@@ -127,19 +127,18 @@ class Comps:
             out = _lib.result_empty((self.nx, self.ny), np.float64)
         elif out.shape != (self.nx, self.ny) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float64 array of the image shape")
-        check(lib().pfbhip_comps_render(self._h, ptr(self._basis(b)), cint(int(bool(region))), ptr(out)))
+        check(lib().pfbhip_comps_render(self._h, ptr(self._basis(b)), int(bool(region)), ptr(out)))
         return out
 
     def render_dev(self, b, out_dev, region=False):
         """:meth:`render` into a ``DeviceArray`` of the image shape (every pixel is written)."""
         if tuple(out_dev.shape) != (self.nx, self.ny) or out_dev.dtype != np.float64:
             raise ValueError(f"out_dev must be a float64 DeviceArray of shape {(self.nx, self.ny)}")
-        check(lib().pfbhip_comps_render_dev(self._h, ptr(self._basis(b)), cint(int(bool(region))), out_dev.ptr))
+        check(lib().pfbhip_comps_render_dev(self._h, ptr(self._basis(b)), int(bool(region)), out_dev.ptr))
 
 
 def _regrid_args(nxi, nyi, cellxi, cellyi, x0i, y0i, nxo, nyo, cellxo, cellyo, x0o, y0o):
-    return (i64(int(nxi)), i64(int(nyi)), f64(cellxi), f64(cellyi), f64(x0i), f64(y0i), i64(int(nxo)), i64(int(nyo)), f64(cellxo),
-            f64(cellyo), f64(x0o), f64(y0o))
+    return (int(nxi), int(nyi), cellxi, cellyi, x0i, y0i, int(nxo), int(nyo), cellxo, cellyo, x0o, y0o)
 
 
 def regrid(image, cellxi, cellyi, x0i, y0i, nxo, nyo, cellxo, cellyo, x0o, y0o):

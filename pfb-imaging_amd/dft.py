@@ -14,7 +14,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import DFTConv, DeviceArray, as_c, check, cint, f64, i64, lib, ptr
+from ._lib import DFTConv, DeviceArray, as_c, check, lib, ptr
 
 
 def _shifts_and_signs(center_x, center_y, flip_u, flip_v, flip_w):
@@ -60,7 +60,7 @@ class DFT:
         _lib.require_gpu()
         self.nrow, self.nchan = int(uvw.shape[0]), int(freq.size)
         self._h = ct.c_void_p()
-        check(lib().pfbhip_dft_create(i64(self.nrow), i64(self.nchan), ptr(uvw), ptr(freq), ptr(mask), ct.byref(self._h)))
+        check(lib().pfbhip_dft_create(self.nrow, self.nchan, ptr(uvw), ptr(freq), ptr(mask), ct.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -160,7 +160,7 @@ class DFT:
         out, dev = self._target(out, nsel, accumulate)
         wgt = self._wgt(wgt, nsel, dev)
         f = lib().pfbhip_dft_predict_dev if dev else lib().pfbhip_dft_predict
-        check(f(self._h, ct.byref(cv), i64(nsrc), ptr(lm), ptr(amp), ptr(rowf), ptr(chanf), ptr(off), self._p(wgt, dev),
+        check(f(self._h, ct.byref(cv), nsrc, ptr(lm), ptr(amp), ptr(rowf), ptr(chanf), ptr(off), self._p(wgt, dev),
                 self._p(out, dev)))
         return out
 
@@ -179,7 +179,7 @@ class DFT:
         out, dev = self._target(out, nsel, accumulate)
         wgt = self._wgt(wgt, nsel, dev)
         f = lib().pfbhip_dft_predict_comps_dev if dev else lib().pfbhip_dft_predict_comps
-        check(f(self._h, ct.byref(cv), comps._h, ptr(bvec), cint(int(bool(region))), f64(cellx), f64(celly), f64(lshift), f64(mshift),
+        check(f(self._h, ct.byref(cv), comps._h, ptr(bvec), int(bool(region)), cellx, celly, lshift, mshift,
                 ptr(off), self._p(wgt, dev), self._p(out, dev)))
         return out
 
@@ -200,7 +200,7 @@ class DFT:
         off = self._off(off)
         out = np.zeros(lm.shape[0], dtype=np.float64)
         f = lib().pfbhip_dft_image_dev if dev else lib().pfbhip_dft_image
-        check(f(self._h, ct.byref(cv), i64(lm.shape[0]), ptr(lm), ptr(off), self._p(wgt, dev), self._p(vis, dev), ptr(out)))
+        check(f(self._h, ct.byref(cv), lm.shape[0], ptr(lm), ptr(off), self._p(wgt, dev), self._p(vis, dev), ptr(out)))
         return out
 
 

@@ -10,7 +10,7 @@ NotImplementedError rather than silently computing on the CPU (the reference has
 import numpy as np
 
 from . import _lib
-from ._lib import as_c, check, i64, lib, ptr
+from ._lib import as_c, check, lib, ptr
 
 
 def good_size(n, real=False):
@@ -58,7 +58,7 @@ def r2c(a, axes=(-2, -1), forward=True, inorm=0, out=None, nthreads=1, centred=F
     nbatch = int(np.prod(src.shape[:-2], dtype=np.int64))
     res = _lib.result_empty(src.shape[:-2] + (n0, n1 // 2 + 1), np.complex128)  # (page-locked: the download runs at the PCIe rate)
     fn = lib().pfbhip_r2c_2d_centred if centred else lib().pfbhip_r2c_2d
-    check(fn(ptr(src), i64(nbatch), i64(n0), i64(n1), ptr(res)))
+    check(fn(ptr(src), nbatch, n0, n1, ptr(res)))
     if not forward:
         np.conjugate(res, out=res)
     s = _norm(inorm, n0 * n1)
@@ -92,7 +92,7 @@ def c2r(a, axes=(-2, -1), forward=False, lastsize=None, inorm=2, out=None, nthre
         raise ValueError(f"lastsize={lastsize} is inconsistent with a half-complex axis of {nh}")
     nbatch = int(np.prod(src.shape[:-2], dtype=np.int64))
     res = _lib.result_empty(src.shape[:-2] + (n0, int(lastsize)), np.float64)
-    check(lib().pfbhip_c2r_2d(ptr(src), i64(nbatch), i64(n0), i64(lastsize), ptr(res)))   # (scaled by 1 / N on the device)
+    check(lib().pfbhip_c2r_2d(ptr(src), nbatch, n0, lastsize, ptr(res)))   # (scaled by 1 / N on the device)
     s = _norm(inorm, n0 * int(lastsize)) * float(n0 * int(lastsize))
     if abs(s - 1.0) > 1e-15:
         res *= s

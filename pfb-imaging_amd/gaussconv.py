@@ -12,7 +12,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import as_c, check, cint, f64, i64, lib, ptr
+from ._lib import as_c, check, i64, lib, ptr
 
 
 def _pars(p, name):
@@ -33,7 +33,7 @@ class GaussConvPlan:
     def __init__(self, nband, nx, ny, pfrac=0.5):
         self.nband, self.nx, self.ny, self.pfrac = int(nband), int(nx), int(ny), float(pfrac)
         self._h = ct.c_void_p()
-        st = lib().pfbhip_gaussconv_create(i64(self.nband), i64(self.nx), i64(self.ny), f64(self.pfrac), ct.byref(self._h))
+        st = lib().pfbhip_gaussconv_create(self.nband, self.nx, self.ny, self.pfrac, ct.byref(self._h))
         if st == 2:  # a geometry error (status 1) is reported as such with or without a device
             _lib.require_gpu()
         check(st)
@@ -72,7 +72,7 @@ class GaussConvPlan:
     def _par_args(self, gaussparf, gausspari):
         pf = _pars(gaussparf, "gaussparf")
         pi = None if gausspari is None else _pars(gausspari, "gausspari")
-        return pf, pi, (ptr(pf), i64(pf.shape[0]), ptr(pi), i64(0 if pi is None else pi.shape[0]))
+        return pf, pi, (ptr(pf), pf.shape[0], ptr(pi), 0 if pi is None else pi.shape[0])
 
     def apply(self, image, gaussparf, gausspari=None, norm_kernel=False, scale=(1.0, 1.0), kernf=None, kerni=None, out=None):
         """Host cube in, host cube out.  ``scale``: the coordinate step of each axis (kernels are rendered on
@@ -85,8 +85,8 @@ class GaussConvPlan:
             kerni = self._host_cube(kerni, "kerni")
         if out is None:
             out = _lib.result_empty(self.shape, np.float64)
-        check(lib().pfbhip_gaussconv_apply(self._h, ptr(image), *pargs, cint(int(bool(norm_kernel))), f64(scale[0]), f64(scale[1]),
-                                           ptr(kernf), ptr(kerni), ptr(out)))
+        check(lib().pfbhip_gaussconv_apply(self._h, ptr(image), *pargs, int(bool(norm_kernel)), scale[0], scale[1], ptr(kernf),
+                                           ptr(kerni), ptr(out)))
         return out
 
     def apply_dev(self, image_dev, out_dev, gaussparf, gausspari=None, norm_kernel=False, scale=(1.0, 1.0), kernf_dev=None,
@@ -99,15 +99,15 @@ class GaussConvPlan:
             self._dev_cube(kernf_dev, "kernf_dev", pf.shape[0])
         if kerni_dev is not None:
             self._dev_cube(kerni_dev, "kerni_dev")
-        check(lib().pfbhip_gaussconv_apply_dev(self._h, image_dev.ptr, *pargs, cint(int(bool(norm_kernel))), f64(scale[0]),
-                                               f64(scale[1]), _dptr(kernf_dev), _dptr(kerni_dev), out_dev.ptr))
+        check(lib().pfbhip_gaussconv_apply_dev(self._h, image_dev.ptr, *pargs, int(bool(norm_kernel)), scale[0], scale[1],
+                                               _dptr(kernf_dev), _dptr(kerni_dev), out_dev.ptr))
 
     def _restore_args(self, wsum, gausspari, gaussparf):
         w = as_c(wsum, np.float64).reshape(-1)
         if w.size != self.nband:
             raise ValueError(f"wsum holds {w.size} values for {self.nband} bands")
         pf, pi, _ = self._par_args(gaussparf, gausspari)
-        return w, pi, pf, (ptr(w), ptr(pi), i64(pi.shape[0]), ptr(pf), i64(pf.shape[0]))
+        return w, pi, pf, (ptr(w), ptr(pi), pi.shape[0], ptr(pf), pf.shape[0])
 
     def restore(self, model, residual, wsum, gausspari, gaussparf, out=None):
         """``conv(model; gaussparf) + rconv`` in one call (host cubes); see ``utils.restoration.restore_arrays``."""
@@ -126,7 +126,7 @@ class GaussConvPlan:
 
     def debug_fill(self, byte=0xFF):
         """Test hook: every buffer of the plan filled with ``byte`` (0xFF: NaNs)."""
-        check(lib().pfbhip_gaussconv_debug_fill(self._h, cint(int(byte))))
+        check(lib().pfbhip_gaussconv_debug_fill(self._h, int(byte)))
 
 
 _plans = collections.OrderedDict()

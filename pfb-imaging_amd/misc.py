@@ -3,12 +3,12 @@
 
 import numpy as np
 
-from ._lib import cint, lib
+from ._lib import lib
 
 
 def resize_thread_pool(nthreads):
     """The compute pool is the GPU; the value is only remembered so callers need no change."""
-    lib().pfbhip_resize_thread_pool(cint(int(nthreads)))
+    lib().pfbhip_resize_thread_pool(int(nthreads))
 
 
 def thread_pool_size():

@@ -13,7 +13,7 @@ import ctypes as ct
 import numpy as np
 
 from .. import _lib
-from .._lib import as_c, check, cint, i64, lib, ptr
+from .._lib import as_c, check, lib, ptr
 
 
 def _basis_code(name):
@@ -32,8 +32,7 @@ class PsiBand:
         self.nx, self.ny, self.nbasis, self.nlevel = int(nx), int(ny), len(bases), int(nlevel)
         codes = np.array([_basis_code(b) for b in bases], dtype=np.int32)
         self._h = ct.c_void_p()
-        check(lib().pfbhip_psi_create(i64(self.nx), i64(self.ny), ct.c_int32(self.nbasis), ptr(codes), ct.c_int32(self.nlevel),
-                                      ct.byref(self._h)))
+        check(lib().pfbhip_psi_create(self.nx, self.ny, self.nbasis, ptr(codes), self.nlevel, ct.byref(self._h)))
         a, b = ct.c_int64(), ct.c_int64()
         check(lib().pfbhip_psi_shape(self._h, ct.byref(a), ct.byref(b)))
         self.nxmax, self.nymax = int(a.value), int(b.value)
@@ -59,7 +58,7 @@ class PsiBand:
         if alphao.shape != self._shape(transposed):
             raise ValueError(f"alpha shape {alphao.shape} != {self._shape(transposed)}")
         target = alphao if (alphao.flags.c_contiguous and alphao.dtype == np.float64) else np.empty(alphao.shape)
-        check(lib().pfbhip_psi_dot(self._h, ptr(x), ptr(target), cint(int(transposed))))
+        check(lib().pfbhip_psi_dot(self._h, ptr(x), ptr(target), int(transposed)))
         if target is not alphao:
             alphao[...] = target
         return alphao
@@ -71,7 +70,7 @@ class PsiBand:
         if xo.shape != (self.nx, self.ny):
             raise ValueError(f"x shape {xo.shape} != {(self.nx, self.ny)}")
         target = xo if (xo.flags.c_contiguous and xo.dtype == np.float64) else np.empty(xo.shape)
-        check(lib().pfbhip_psi_hdot(self._h, ptr(alpha), ptr(target), cint(int(transposed))))
+        check(lib().pfbhip_psi_hdot(self._h, ptr(alpha), ptr(target), int(transposed)))
         if target is not xo:
             xo[...] = target
         return xo

@@ -19,7 +19,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import FBInfo, PDInfo, PDTraffic, PMInfo, check, cint, f64, i64, lib, ptr
+from ._lib import FBInfo, PDInfo, PDTraffic, PMInfo, check, lib, ptr
 from .operators.psi import Psi, PsiNocopyt
 from .prox import dual_update_numba_fast, prox_21m_numba
 
@@ -114,7 +114,7 @@ class L21:
         if h is not None:
             xdev, keep = self._image_dev(update)
             got, count = np.zeros(self.psi.nbasis), np.zeros(self.psi.nbasis, dtype=np.int64)
-            check(lib().pfbhip_l21_rms_dev(h, xdev, i64(self.psi.nband), self._scratch_dev().ptr, ptr(got), ptr(count)))
+            check(lib().pfbhip_l21_rms_dev(h, xdev, self.psi.nband, self._scratch_dev().ptr, ptr(got), ptr(count)))
             rms[count > 0] = got[count > 0]
             del keep
         else:
@@ -133,8 +133,8 @@ class L21:
         if h is not None:
             xdev, keep = self._image_dev(x)
             wdev = self._wdev if self._wdev is not None else _lib.DeviceArray((self.psi.nbasis, self.psi.nxmax, self.psi.nymax))
-            check(lib().pfbhip_l21_reweight_dev(h, xdev, i64(self.psi.nband), ptr(self._rms_comps), f64(self.rmsfactor),
-                                                f64(self.alpha), self._scratch_dev().ptr, wdev.ptr))
+            check(lib().pfbhip_l21_reweight_dev(h, xdev, self.psi.nband, ptr(self._rms_comps), self.rmsfactor, self.alpha,
+                                                self._scratch_dev().ptr, wdev.ptr))
             self._l1weight, self._wdev = None, wdev
             del keep
             return
@@ -221,7 +221,7 @@ def _band_args(bands):
     beam_slots = np.array([s for b in bands for s in b[2]], dtype=np.int64)
     scale = np.array([b[3] for b in bands], dtype=np.float64)
     eta = np.array([b[4] for b in bands], dtype=np.float64)
-    return handles, i64(len(bands)), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale), ptr(eta)
+    return handles, len(bands), ptr(nparts), ptr(psf_slots), ptr(beam_slots), ptr(scale), ptr(eta)
 
 
 def _device_weight(reg, psi, transposed):
@@ -266,7 +266,7 @@ def _run_with_events(h, run, set_weight, set_weight_dev, iterate_dev, info, lam,
     resume_weight(False)  # (the create uploaded the host weight)
     while True:
         out = np.empty_like(x0)  # (a fresh array per run: on_converge may keep the one it was handed)
-        check(run(h, f64(lam), f64(tol), cint(maxit), ptr(out), ct.byref(info)))
+        check(run(h, lam, tol, maxit, ptr(out), ct.byref(info)))
         if info.status != 0 or on_converge is None:
             return out
         if lend:
@@ -355,8 +355,8 @@ class PrimalDual:
         w0 = _device_weight(reg, psi, transposed) if reg._wdev is None else None
         uploaded0 = reg._h2d_bytes
         L = lib()
-        check(L.pfbhip_pd_create(psi._band._h, *_band_args(bands), ptr(xt), f64(g.gamma), ptr(x0), ptr(v), ptr(w0), f64(self.sigma),
-                                 f64(self.tau), cint(mode), ct.byref(h)))
+        check(L.pfbhip_pd_create(psi._band._h, *_band_args(bands), ptr(xt), g.gamma, ptr(x0), ptr(v), ptr(w0), self.sigma,
+                                 self.tau, mode, ct.byref(h)))
         info, traffic = PDInfo(), PDTraffic()
         try:
             out = _run_with_events(h, L.pfbhip_pd_run, L.pfbhip_pd_set_weight, L.pfbhip_pd_set_weight_dev, L.pfbhip_pd_iterate_dev,
@@ -384,9 +384,9 @@ class PrimalDual:
         xs = np.ascontiguousarray(np.asarray(x, dtype=np.float64)[local])
         xt = np.ascontiguousarray(self._grad.xtilde[local])
         info = PDInfo()
-        check(lib().pfbhip_primal_dual(psi._band._h, *_band_args(bands), ptr(xt), f64(self._grad.gamma), ptr(xs), ptr(v),
-                                       ptr(w), f64(lam), f64(self.sigma), f64(self.tau), cint(mode), f64(self.tol),
-                                       cint(self.maxit), None if comm is None else comm._h, ct.byref(info)))
+        check(lib().pfbhip_primal_dual(psi._band._h, *_band_args(bands), ptr(xt), self._grad.gamma, ptr(xs), ptr(v), ptr(w), lam,
+                                       self.sigma, self.tau, mode, self.tol, self.maxit, None if comm is None else comm._h,
+                                       ct.byref(info)))
         if comm is None:
             xall, vall = xs, v
         else:  # every rank holds the full cubes again: each band was produced by exactly one rank
@@ -561,8 +561,8 @@ class ForwardBackward:
         # (an L21 weight left in HBM by an earlier update goes to the loop from there)
         w0 = None if getattr(reg, "_wdev", None) is not None else _device_weight(reg, psi, transposed)
         L = lib()
-        check(L.pfbhip_fb_create(handle, *_band_args(bands), ptr(xt), f64(g.gamma), ptr(x0), ptr(w0), cint(0 if isinstance(reg, L21) else 1),
-                                 f64(reg.nu), f64(self.step), cint(mode), cint(1 if self.acceleration else 0), ct.byref(h)))
+        check(L.pfbhip_fb_create(handle, *_band_args(bands), ptr(xt), g.gamma, ptr(x0), ptr(w0), 0 if isinstance(reg, L21) else 1,
+                                 reg.nu, self.step, mode, 1 if self.acceleration else 0, ct.byref(h)))
         info = FBInfo()
         try:
             out = _run_with_events(h, L.pfbhip_fb_run, L.pfbhip_fb_set_weight, L.pfbhip_fb_set_weight_dev, L.pfbhip_fb_iterate_dev,
@@ -739,8 +739,7 @@ def _pm_device(aop, imsize, b):
     fn = getattr(aop, "__func__", None)
     if isinstance(owner, Gridder) and fn is Gridder.hessian and tuple(imsize) == (owner.nx, owner.ny):
         def call(b, tol, maxit, info):
-            check(lib().pfbhip_gridder_power_method(owner._h, None, f64(0.0), f64(0.0), ptr(b), f64(tol), cint(maxit),
-                                                    ct.byref(info)))
+            check(lib().pfbhip_gridder_power_method(owner._h, None, 0.0, 0.0, ptr(b), tol, maxit, ct.byref(info)))
             return b
         return call
     if isinstance(owner, (HessPSF, HessTreeRay)) and fn is type(owner).dot and len(imsize) == 3:
@@ -751,8 +750,8 @@ def _pm_device(aop, imsize, b):
 
         def call(b, tol, maxit, info):
             bs = np.ascontiguousarray(b[local])
-            check(lib().pfbhip_psfconv_power_method(*_band_args(bands), ptr(bs), f64(tol), cint(maxit),
-                                                    None if comm is None else comm._h, ct.byref(info)))
+            check(lib().pfbhip_psfconv_power_method(*_band_args(bands), ptr(bs), tol, maxit, None if comm is None else comm._h,
+                                                    ct.byref(info)))
             if comm is None:
                 return bs
             out = np.zeros(b.shape)

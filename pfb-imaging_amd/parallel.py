@@ -25,7 +25,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import DeviceArray, check, cint, i64, lib, ptr
+from ._lib import DeviceArray, check, lib, ptr
 
 
 class HostGroup:
@@ -217,7 +217,7 @@ class BandComm:
         self = cls(rank, world, local_rank, transport, host)
         if transport == "rccl" and set_device:
             ndev = _lib.device_count()
-            check(lib().pfbhip_set_device(cint(local_rank % max(ndev, 1))))
+            check(lib().pfbhip_set_device(local_rank % max(ndev, 1)))
         if world > 1 and self._host is None:
             # one TCP group per process and job: a second communicator (bench.py's fallback when RCCL fails on SOME rank)
             # must not make the ranks rendezvous again -- the ranks that did not fail would not come
@@ -232,7 +232,7 @@ class BandComm:
             if world > 1:  # RCCL's unique id travels rank 0 -> all over the TCP group
                 uid = np.frombuffer(self._host.bcast_bytes(uid.tobytes(), src=0), dtype=np.uint8).copy()
             h = ct.c_void_p()
-            check(lib().pfbhip_comm_create(ptr(uid), cint(world), cint(rank), ct.byref(h)))
+            check(lib().pfbhip_comm_create(ptr(uid), world, rank, ct.byref(h)))
             self._h = h
         return self
 
@@ -257,12 +257,12 @@ class BandComm:
         n = int(np.prod(send.shape, dtype=np.int64))
         # non-root ranks pass their send buffer as the (unused) receive buffer, the usual NCCL idiom
         rptr = send.ptr if recv is None else recv.ptr
-        check(lib().pfbhip_comm_reduce_sum(self._h, send.ptr, rptr, i64(n), cint(root)))
+        check(lib().pfbhip_comm_reduce_sum(self._h, send.ptr, rptr, n, root))
 
     def allreduce_sum_dev(self, send, recv):
         assert self.transport == "rccl"
         n = int(np.prod(send.shape, dtype=np.int64))
-        check(lib().pfbhip_comm_allreduce_sum(self._h, send.ptr, recv.ptr, i64(n)))
+        check(lib().pfbhip_comm_allreduce_sum(self._h, send.ptr, recv.ptr, n))
 
     def reduce_sum(self, arr, root=0):
         """Sum a float64 host array over ranks; the root gets the total, others get None."""
@@ -271,7 +271,7 @@ class BandComm:
             return arr
         if self.transport == "rccl":  # upload -> ncclReduce -> download on the communicator's persistent staging buffer
             out = _lib.result_empty(arr.shape, np.float64) if self.rank == root else None
-            check(lib().pfbhip_comm_reduce_sum_host(self._h, ptr(arr), ptr(out), i64(arr.size), cint(root)))
+            check(lib().pfbhip_comm_reduce_sum_host(self._h, ptr(arr), ptr(out), arr.size, root))
             return out
         tot = self._host.allgather(arr).sum(axis=0)
         return tot if self.rank == root else None
@@ -282,7 +282,7 @@ class BandComm:
             return arr
         if self.transport == "rccl":
             out = arr.copy()
-            check(lib().pfbhip_comm_allreduce_sum_host(self._h, ptr(out), i64(out.size)))
+            check(lib().pfbhip_comm_allreduce_sum_host(self._h, ptr(out), out.size))
             return out
         return self._host.allgather(arr).sum(axis=0)
 
@@ -293,7 +293,7 @@ class BandComm:
             return arr[None]
         if self.transport == "rccl":
             out = _lib.result_empty((self.world_size,) + arr.shape, np.float64)
-            check(lib().pfbhip_comm_allgather_host(self._h, ptr(arr), ptr(out), i64(arr.size)))
+            check(lib().pfbhip_comm_allgather_host(self._h, ptr(arr), ptr(out), arr.size))
             return out
         return self._host.allgather(arr)
 

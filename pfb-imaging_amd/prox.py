@@ -8,7 +8,7 @@ coefficient cubes / ``(nband, nx, ny)`` image cubes on the host; ``v`` / ``x`` a
 import numpy as np
 
 from . import _lib
-from ._lib import as_c, check, cint, f64, i64, lib, ptr
+from ._lib import as_c, check, lib, ptr
 
 
 def _inplace(arr):
@@ -27,7 +27,7 @@ def dual_update_numba_fast(vp, v, lam, sigma=1.0, weight=None):
     if vp.shape != v.shape:
         raise ValueError(f"vp shape {vp.shape} != v shape {v.shape}")
     w = np.ones(v.shape[1:]) if weight is None else as_c(np.broadcast_to(weight, v.shape[1:]), np.float64)
-    check(lib().pfbhip_dual_update(ptr(vp), ptr(v), i64(nband), i64(n), f64(lam), f64(sigma), ptr(w)))
+    check(lib().pfbhip_dual_update(ptr(vp), ptr(v), nband, n, lam, sigma, ptr(w)))
 
 
 # the numerically fragile original (prox_21m.py:73-102) computes the same update
@@ -42,7 +42,7 @@ def _vtilde_sum_gpu(vp_loc, v_loc, sigma):
     n = v_loc.size // max(nb, 1)
     dvp, dv = DeviceArray.from_host(vp_loc), DeviceArray.from_host(v_loc)
     ds = DeviceArray((n,), np.float64)
-    check(lib().pfbhip_l21_vtilde_sum_dev(dvp.ptr, dv.ptr, i64(nb), i64(n), f64(sigma), ds.ptr))
+    check(lib().pfbhip_l21_vtilde_sum_dev(dvp.ptr, dv.ptr, nb, n, sigma, ds.ptr))
     dv.download(v_loc)
     s = ds.download()
     for d in (dvp, dv, ds):
@@ -57,7 +57,7 @@ def _scale_gpu(v_loc, lam, weight, total):
     nb = v_loc.shape[0]
     n = v_loc.size // max(nb, 1)
     dv, dw, ds = DeviceArray.from_host(v_loc), DeviceArray.from_host(weight), DeviceArray.from_host(total)
-    check(lib().pfbhip_l21_scale_dev(dv.ptr, i64(nb), i64(n), f64(lam), dw.ptr, ds.ptr))
+    check(lib().pfbhip_l21_scale_dev(dv.ptr, nb, n, lam, dw.ptr, ds.ptr))
     dv.download(v_loc)
     for d in (dv, dw, ds):
         d.free()
@@ -102,7 +102,7 @@ def prox_21m(v, sigma, weight=1.0, axis=0):
     n = v.size // max(nband, 1)
     w = as_c(np.broadcast_to(weight, v.shape[1:]), np.float64)
     out = _lib.result_empty(v.shape, np.float64)
-    check(lib().pfbhip_prox_21m(ptr(v), i64(nband), i64(n), f64(sigma), ptr(w), ptr(out)))
+    check(lib().pfbhip_prox_21m(ptr(v), nband, n, sigma, ptr(w), ptr(out)))
     return out
 
 
@@ -116,7 +116,7 @@ def positivity(x):
     """Clamp negative values to zero, in place (positivity.py:12-19)."""
     _lib.require_gpu()
     x = _inplace(x)
-    check(lib().pfbhip_positivity(ptr(x), i64(1), i64(x.size), cint(1)))
+    check(lib().pfbhip_positivity(ptr(x), 1, x.size, 1))
 
 
 def positivity_band(x):
@@ -124,7 +124,7 @@ def positivity_band(x):
     _lib.require_gpu()
     x = _inplace(x)
     nband = x.shape[0]
-    check(lib().pfbhip_positivity(ptr(x), i64(nband), i64(x.size // max(nband, 1)), cint(2)))
+    check(lib().pfbhip_positivity(ptr(x), nband, x.size // max(nband, 1), 2))
 
 
 def positivity_prox(mode):
@@ -148,7 +148,7 @@ def l21_reweight(band, x, rms, rmsfactor, alpha, return_bandsum=False):
         raise ValueError(f"x {x.shape} / rms {rms.shape}: expected (nband, {band.nx}, {band.ny}) and ({band.nbasis},)")
     w = np.empty((band.nbasis, band.nxmax, band.nymax))
     s = np.empty_like(w) if return_bandsum else None
-    check(lib().pfbhip_l21_reweight(band._h, ptr(x), i64(x.shape[0]), ptr(rms), f64(rmsfactor), f64(alpha), ptr(w), ptr(s)))
+    check(lib().pfbhip_l21_reweight(band._h, ptr(x), x.shape[0], ptr(rms), rmsfactor, alpha, ptr(w), ptr(s)))
     return (w, s) if return_bandsum else w
 
 
@@ -159,5 +159,5 @@ def l21_rms(band, update):
     if update.ndim != 3 or update.shape[1:] != (band.nx, band.ny):
         raise ValueError(f"update {update.shape}: expected (nband, {band.nx}, {band.ny})")
     rms, count = np.zeros(band.nbasis), np.zeros(band.nbasis, dtype=np.int64)
-    check(lib().pfbhip_l21_rms(band._h, ptr(update), i64(update.shape[0]), ptr(rms), ptr(count)))
+    check(lib().pfbhip_l21_rms(band._h, ptr(update), update.shape[0], ptr(rms), ptr(count)))
     return rms, count

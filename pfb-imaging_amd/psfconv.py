@@ -12,7 +12,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import CGInfo, as_c, check, cint, f64, i64, lib, ptr
+from ._lib import CGInfo, as_c, check, cint, lib, ptr
 
 
 class PsfConv:
@@ -21,8 +21,7 @@ class PsfConv:
         self.nx, self.ny, self.nx_psf, self.ny_psf = int(nx), int(ny), int(nx_psf), int(ny_psf)
         self.nyo2 = self.ny_psf // 2 + 1
         self._h = ct.c_void_p()
-        check(lib().pfbhip_psfconv_create(i64(self.nx), i64(self.ny), i64(self.nx_psf), i64(self.ny_psf),
-                                          ct.byref(self._h)))
+        check(lib().pfbhip_psfconv_create(self.nx, self.ny, self.nx_psf, self.ny_psf, ct.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -49,14 +48,14 @@ class PsfConv:
             raise ValueError(f"psfhat shape {psfhat.shape} != {(self.nx_psf, self.nyo2)}")
         is_complex = np.iscomplexobj(psfhat)
         a = as_c(psfhat, np.complex128 if is_complex else np.float64)
-        check(lib().pfbhip_psfconv_set_psfhat(self._h, i64(slot), ptr(a), cint(int(is_complex))))
+        check(lib().pfbhip_psfconv_set_psfhat(self._h, slot, ptr(a), int(is_complex)))
 
     def set_beam(self, slot, beam):
         if beam is not None:
             beam = as_c(beam, np.float64)
             if beam.shape != (self.nx, self.ny):
                 raise ValueError(f"beam shape {beam.shape} != {(self.nx, self.ny)}")
-        check(lib().pfbhip_psfconv_set_beam(self._h, i64(slot), ptr(beam)))
+        check(lib().pfbhip_psfconv_set_beam(self._h, slot, ptr(beam)))
 
     def apply(self, x, psf_slot, beam_slot=-1, mode=0, shift=0.0, scale=1.0, eta=0.0, out=None, accumulate=False):
         x = as_c(x, np.float64)
@@ -67,8 +66,8 @@ class PsfConv:
                 raise ValueError("accumulate needs an output array")
             out = _lib.result_empty(x.shape, np.float64)
         target = out if (out.flags.c_contiguous and out.dtype == np.float64) else np.array(out, dtype=np.float64)
-        check(lib().pfbhip_psfconv_apply(self._h, ptr(x), i64(psf_slot), i64(beam_slot), cint(mode), f64(shift),
-                                         f64(scale), f64(eta or 0.0), cint(int(accumulate)), ptr(target)))
+        check(lib().pfbhip_psfconv_apply(self._h, ptr(x), psf_slot, beam_slot, mode, shift, scale, eta or 0.0, int(accumulate),
+                                         ptr(target)))
         if target is not out:
             out[...] = target
         return out
@@ -80,8 +79,7 @@ class PsfConv:
         x = as_c(x, np.float64)
         out = _lib.result_empty(x.shape, np.float64) if out is None else out
         assert out.flags.c_contiguous and out.dtype == np.float64 and (raw is None or (raw.flags.c_contiguous and raw.dtype == np.float64))
-        check(lib().pfbhip_psfconv_direct(self._h, ptr(x), i64(psf_slot), i64(taper_slot), f64(shift), i64(beam_slot), f64(min_beam),
-                                          ptr(raw), ptr(out)))
+        check(lib().pfbhip_psfconv_direct(self._h, ptr(x), psf_slot, taper_slot, shift, beam_slot, min_beam, ptr(raw), ptr(out)))
         return out
 
     def cg(self, rhs, psf_slots, beam_slots, scale=1.0, eta=0.0, x0=None, tol=1e-5, maxit=500, minit=100):
@@ -90,9 +88,8 @@ class PsfConv:
         ps = np.ascontiguousarray(psf_slots, dtype=np.int64)
         bs = np.ascontiguousarray(beam_slots, dtype=np.int64)
         info = CGInfo()
-        check(lib().pfbhip_psfconv_cg(self._h, i64(ps.size), ptr(ps), ptr(bs), f64(scale), f64(eta or 0.0), ptr(rhs),
-                                      ptr(x), cint(0 if x0 is None else 1), f64(tol), cint(maxit), cint(minit),
-                                      ct.byref(info)))
+        check(lib().pfbhip_psfconv_cg(self._h, ps.size, ptr(ps), ptr(bs), scale, eta or 0.0, ptr(rhs), ptr(x),
+                                      0 if x0 is None else 1, tol, maxit, minit, ct.byref(info)))
         self.last_cg = dict(iters=info.iters, status=info.status, eps=info.eps, phi=info.phi)
         return x
 

@@ -10,7 +10,7 @@ import ctypes as ct
 import numpy as np
 
 from .. import _lib
-from .._lib import as_c, check, cint, f64, i32, i64, lib, ptr
+from .._lib import as_c, check, f64, lib, ptr
 
 DEFAULT_ANGLES = np.linspace(0, 359, 25)  # stokes2vis_msv4.py:405-406
 
@@ -52,9 +52,8 @@ def eval_beam(beam_image, l_in, m_in, l_out, m_out, info=None):
     l_out, m_out = as_c(l_out, np.float64), as_c(m_out, np.float64)
     out = _lib.result_empty((ncorr, nx, ny) if stack else (nx, ny), np.float64)
     ms = f64(0.0)
-    check(lib().pfbhip_beam_regrid(ptr(beam), i32(ncorr), i64(l_in.size), i64(m_in.size), ptr(l_in), ptr(m_in), ptr(l_out),
-                                   ptr(m_out), cint(int(general)), i64(nx), i64(ny), ptr(out),
-                                   ct.byref(ms) if info is not None else None))
+    check(lib().pfbhip_beam_regrid(ptr(beam), ncorr, l_in.size, m_in.size, ptr(l_in), ptr(m_in), ptr(l_out), ptr(m_out),
+                                   int(general), nx, ny, ptr(out), ct.byref(ms) if info is not None else None))
     if info is not None:
         info["device_ms"] = ms.value
     return out
@@ -74,8 +73,8 @@ def rotate_mean(beam0, angles=DEFAULT_ANGLES, info=None):
     ncorr = beam.shape[0] if beam.ndim == 3 else 1
     out = _lib.result_empty(beam.shape, np.float64)
     ms = f64(0.0)
-    check(lib().pfbhip_beam_rotate_mean(ptr(beam), i32(ncorr), i64(beam.shape[-2]), i64(beam.shape[-1]), ptr(angles),
-                                        i32(angles.size), ptr(out), ct.byref(ms) if info is not None else None))
+    check(lib().pfbhip_beam_rotate_mean(ptr(beam), ncorr, beam.shape[-2], beam.shape[-1], ptr(angles), angles.size, ptr(out),
+                                        ct.byref(ms) if info is not None else None))
     if info is not None:
         info["device_ms"] = ms.value
     return out

@@ -168,8 +168,8 @@ def _cleanbeam_raw(psf, level=0.5, nsigma=10.0):
     pars = np.empty((nband, 3), dtype=np.float64)
     info = (_lib.CleanbeamInfo * nband)()
     call = _lib.lib().pfbhip_cleanbeam_fit_dev if on_dev else _lib.lib().pfbhip_cleanbeam_fit
-    _lib.check(call(psf.ptr if on_dev else _lib.ptr(psf), _lib.i64(nband), _lib.i64(nx), _lib.i64(ny), _lib.f64(level),
-                    _lib.f64(nsigma), _lib.ptr(pars), ct.cast(info, _lib.vp)))
+    _lib.check(call(psf.ptr if on_dev else _lib.ptr(psf), nband, nx, ny, level,
+                    nsigma, _lib.ptr(pars), ct.cast(info, _lib.vp)))
     recs = [dict(status=_lib.CB_STATUS_NAMES[r.status], window=r.window, nit=r.nit, nlobe=r.nlobe, nfit=r.nfit, f=r.f,
                  p0=np.array(r.p0[:])) for r in info]
     return pars, recs

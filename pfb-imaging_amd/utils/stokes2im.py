@@ -36,7 +36,7 @@ import ctypes as ct
 import numpy as np
 
 from .. import _lib
-from .._lib import DeviceArray, DeviceView, check, cint, f64, i64, lib, ptr
+from .._lib import DeviceArray, DeviceView, check, f64, lib, ptr
 
 PSF_MIN_SIZE = 128  # stokes2im.py:606
 
@@ -149,8 +149,8 @@ def snapshot_finish(residual_dev, psf_dev, wsum, pbeam_dev=None, eta=1e-5, psf_o
     if pbeam_dev is not None:
         out["beam_weight"] = _lib.result_empty((ns, ny, nx), out_dtype)
     check(lib().pfbhip_snapshot_finish_dev(residual_dev.ptr, psf_dev.ptr, None if pbeam_dev is None else pbeam_dev.ptr, ptr(wsum),
-                                           i64(ns), i64(nx), i64(ny), i64(nxp), i64(nyp), f64(float(eta)),
-                                           cint(int(out_dtype == np.float64)), ptr(out["cube"]), ptr(out.get("psf")),
+                                           ns, nx, ny, nxp, nyp, float(eta),
+                                           int(out_dtype == np.float64), ptr(out["cube"]), ptr(out.get("psf")),
                                            ptr(out.get("beam_weight")), ptr(out["psf_max"]), ptr(out["rms"]),
                                            ct.byref(ms) if info is not None else None))
     if info is not None:

@@ -12,7 +12,7 @@ import ctypes as ct
 import numpy as np
 
 from .. import _lib
-from .._lib import as_c, check, f64, i32, i64, lib, ptr
+from .._lib import as_c, check, f64, i32, lib, ptr
 
 
 def uvcell_index(uvw, freq, mask, nx, ny, cell_size_x, cell_size_y, usign=1.0, vsign=-1.0):
@@ -21,8 +21,8 @@ def uvcell_index(uvw, freq, mask, nx, ny, cell_size_x, cell_size_y, usign=1.0, v
     uvw, freq, mask = as_c(uvw, np.float64), as_c(freq, np.float64), as_c(mask, np.uint8)
     nrow, nchan = mask.shape
     cell = np.empty((nrow, nchan), dtype=np.int64)
-    check(lib().pfbhip_uvcell_index(ptr(uvw), ptr(freq), ptr(mask), i64(nrow), i64(nchan), i64(nx), i64(ny),
-                                    f64(cell_size_x), f64(cell_size_y), f64(usign), f64(vsign), ptr(cell)))
+    check(lib().pfbhip_uvcell_index(ptr(uvw), ptr(freq), ptr(mask), nrow, nchan, nx, ny, cell_size_x, cell_size_y, usign, vsign,
+                                    ptr(cell)))
     return cell
 
 
@@ -33,9 +33,8 @@ def _compute_counts(uvw, freq, mask, wgt, nx, ny, cell_size_x, cell_size_y, dtyp
     wgt = as_c(wgt, np.float64)
     ncorr, nrow, nchan = wgt.shape
     counts = np.zeros((ncorr, nx, ny), dtype=np.float64)
-    check(lib().pfbhip_compute_counts(ptr(uvw), ptr(freq), ptr(mask), ptr(wgt), i64(ncorr), i64(nrow), i64(nchan),
-                                      i64(nx), i64(ny), f64(cell_size_x), f64(cell_size_y), f64(usign), f64(vsign),
-                                      ptr(counts)))
+    check(lib().pfbhip_compute_counts(ptr(uvw), ptr(freq), ptr(mask), ptr(wgt), ncorr, nrow, nchan, nx, ny, cell_size_x,
+                                      cell_size_y, usign, vsign, ptr(counts)))
     return counts.astype(dtype, copy=False)
 
 
@@ -56,9 +55,8 @@ def counts_to_weights(counts, uvw, freq, weight, mask, nx, ny, cell_size_x, cell
     uvw, freq, mask = as_c(uvw, np.float64), as_c(freq, np.float64), as_c(mask, np.uint8)
     w = weight if (weight.flags.c_contiguous and weight.dtype == np.float64) else np.array(weight, dtype=np.float64)
     c = as_c(counts, np.float64)
-    check(lib().pfbhip_counts_divide(ptr(uvw), ptr(freq), ptr(mask), ptr(c), i64(ncorr), i64(nrow), i64(nchan),
-                                     i64(nx), i64(ny), f64(cell_size_x), f64(cell_size_y), f64(usign), f64(vsign),
-                                     ptr(w)))
+    check(lib().pfbhip_counts_divide(ptr(uvw), ptr(freq), ptr(mask), ptr(c), ncorr, nrow, nchan, nx, ny, cell_size_x, cell_size_y,
+                                     usign, vsign, ptr(w)))
     if w is not weight:
         weight[...] = w
     return weight
@@ -70,7 +68,7 @@ def filter_extreme_counts(counts, level=10.0):
         return counts
     _lib.require_gpu()
     c = counts if (counts.flags.c_contiguous and counts.dtype == np.float64) else np.array(counts, dtype=np.float64)
-    check(lib().pfbhip_filter_extreme_counts(ptr(c), i64(c.size), f64(level), None))
+    check(lib().pfbhip_filter_extreme_counts(ptr(c), c.size, level, None))
     if c is not counts:
         counts[...] = c
     return counts
@@ -87,7 +85,7 @@ def box_sum_counts(counts, npix_super):
     c = as_c(counts, np.float64)
     ncorr, nx, ny = c.shape
     out = _lib.result_empty(c.shape, np.float64)
-    check(lib().pfbhip_box_sum_counts(ptr(c), i64(ncorr), i64(nx), i64(ny), i64(int(npix_super)), ptr(out)))
+    check(lib().pfbhip_box_sum_counts(ptr(c), ncorr, nx, ny, int(npix_super), ptr(out)))
     return out.astype(counts.dtype, copy=False)
 
 
@@ -102,9 +100,8 @@ def imaging_weights(uvw, freq, mask, weight, nx_pad, ny_pad, cell_size_x, cell_s
     ncorr, nrow, nchan = weight.shape
     w = weight if (weight.flags.c_contiguous and weight.dtype == np.float64) else np.array(weight, dtype=np.float64)
     counts = _lib.result_empty((ncorr, nx_pad, ny_pad), np.float64) if return_counts else None
-    check(lib().pfbhip_imaging_weights(ptr(uvw), ptr(freq), ptr(mask), ptr(w), i64(ncorr), i64(nrow), i64(nchan), i64(nx_pad),
-                                       i64(ny_pad), f64(cell_size_x), f64(cell_size_y), f64(usign), f64(vsign), f64(robust),
-                                       f64(filter_level or 0.0), i64(int(npix_super or 0)), ptr(counts)))
+    check(lib().pfbhip_imaging_weights(ptr(uvw), ptr(freq), ptr(mask), ptr(w), ncorr, nrow, nchan, nx_pad, ny_pad, cell_size_x,
+                                       cell_size_y, usign, vsign, robust, filter_level or 0.0, int(npix_super or 0), ptr(counts)))
     if w is not weight:
         weight[...] = w
     return (weight, counts) if return_counts else weight
@@ -180,7 +177,7 @@ def _weight_data_args(data, weight, flag, jones, tbin_idx, tbin_counts, ant1, an
     real = np.float32 if single else np.float64
     arrays = (as_c(data, data.dtype), as_c(weight, real), as_c(flag != 0 if flag.dtype != np.bool_ else flag, np.uint8),
               as_c(jones[:, :, :, 0], np.complex128), tbin_idx, tbin_counts, _antennas(ant1, nrow, "ant1"), _antennas(ant2, nrow, "ant2"))
-    sizes = (i64(nrow), i64(nchan), i64(nant), i64(ntime), i64(tbin_idx.size))
+    sizes = (nrow, nchan, nant, ntime, tbin_idx.size)
     return spec, sizes, arrays, (nrow, nchan, len(chosen)), single
 
 

@@ -16,7 +16,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import DeviceArray, as_c, check, f64, i64, lib, ptr
+from ._lib import DeviceArray, as_c, check, f64, lib, ptr
 
 
 def _adopt(a, shape, dtype, name):
@@ -265,7 +265,7 @@ class VisChunk:
         """``wgt[:, mask != 0].sum(-1)`` (gridder.py:584); bit-identical from call to call."""
         self._open()
         out = np.empty(self.ncorr, dtype=np.float64)
-        check(lib().pfbhip_chunk_wsum_dev(self.wgt.ptr, self.mask.ptr, i64(self.ncorr), i64(self.nvis), ptr(out)))
+        check(lib().pfbhip_chunk_wsum_dev(self.wgt.ptr, self.mask.ptr, self.ncorr, self.nvis, ptr(out)))
         return out
 
     def l2_reweight(self, resvis_dev, dof, wgtp=1.0):
@@ -289,8 +289,8 @@ class VisChunk:
             scalar = 1.0
         ovar = np.empty(self.ncorr, dtype=np.float64)
         try:
-            check(lib().pfbhip_chunk_l2_reweight_dev(resvis_dev.ptr, None if wp is None else wp.ptr, f64(scalar), self.mask.ptr,
-                                                     self.wgt.ptr, i64(self.ncorr), i64(self.nvis), f64(float(dof)), ptr(ovar)))
+            check(lib().pfbhip_chunk_l2_reweight_dev(resvis_dev.ptr, None if wp is None else wp.ptr, scalar, self.mask.ptr,
+                                                     self.wgt.ptr, self.ncorr, self.nvis, float(dof), ptr(ovar)))
         finally:
             if own is not None:
                 own.free()
@@ -326,8 +326,8 @@ class VisChunk:
             if model is not None:
                 md = model if isinstance(model, DeviceArray) else DeviceArray.from_host(as_c(model, np.complex128))
             check(lib().pfbhip_chunk_rephase_residual_dev(self.vis.ptr, None if md is None else md.ptr, self.mask.ptr,
-                                                          None if wd is None else wd.ptr, ptr(self.freq), i64(self.ncorr),
-                                                          i64(self.nrow), i64(self.nchan)))
+                                                          None if wd is None else wd.ptr, ptr(self.freq), self.ncorr, self.nrow,
+                                                          self.nchan))
         finally:
             if wd is not None:
                 wd.free()
@@ -344,8 +344,8 @@ class VisChunk:
             raise ValueError(f"dof = {dof} must be positive and finite")
         self._open()
         ovar = f64(0.0)
-        check(lib().pfbhip_chunk_l2_reweight_joint_dev(self.vis.ptr, self.mask.ptr, self.wgt.ptr, i64(self.ncorr), i64(self.nvis),
-                                                       f64(dof), ct.byref(ovar)))
+        check(lib().pfbhip_chunk_l2_reweight_joint_dev(self.vis.ptr, self.mask.ptr, self.wgt.ptr, self.ncorr, self.nvis, dof,
+                                                       ct.byref(ovar)))
         return ovar.value
 
     def inject_transients(self, uvw, freq, time, sources, all_times, all_freqs, w_diff=None, beam=None):
@@ -380,10 +380,9 @@ class VisChunk:
         final counts ``(ncorr, nx_pad, ny_pad)`` come back with ``return_counts``."""
         self._open()
         counts = _lib.result_empty((self.ncorr, nx_pad, ny_pad), np.float64) if return_counts else None
-        check(lib().pfbhip_imaging_weights_dev(ptr(self.uvw), ptr(self.freq), self.mask.ptr, self.wgt.ptr, i64(self.ncorr),
-                                               i64(self.nrow), i64(self.nchan), i64(nx_pad), i64(ny_pad), f64(cellx), f64(celly),
-                                               f64(usign), f64(vsign), f64(robust), f64(filter_level or 0.0),
-                                               i64(int(npix_super or 0)), ptr(counts)))
+        check(lib().pfbhip_imaging_weights_dev(ptr(self.uvw), ptr(self.freq), self.mask.ptr, self.wgt.ptr, self.ncorr, self.nrow,
+                                               self.nchan, nx_pad, ny_pad, cellx, celly, usign, vsign, robust,
+                                               filter_level or 0.0, int(npix_super or 0), ptr(counts)))
         return counts
 
     def weights(self):

@@ -18,7 +18,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import CGInfo, PMInfo, GridderInfo, GridderParams, as_c, check, cint, f64, i64, lib, ptr
+from ._lib import CGInfo, PMInfo, GridderInfo, GridderParams, as_c, check, f64, i64, lib, ptr
 
 
 class Gridder:
@@ -193,7 +193,7 @@ class Gridder:
         if ramp_sign not in (1.0, -1.0):
             raise ValueError(f"ramp_sign must be +1 or -1, not {ramp_sign}")
         w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
-        check(lib().pfbhip_gridder_psf_rows_signed_dev(self._h, w, f64(float(ramp_sign)), self._img_dev(psf_dev, "psf_dev")))
+        check(lib().pfbhip_gridder_psf_rows_signed_dev(self._h, w, float(ramp_sign), self._img_dev(psf_dev, "psf_dev")))
 
     def set_weights_dev(self, wgt_dev, wgt_offset=0):
         w = self._rows(wgt_dev, wgt_offset, np.float64, "wgt_dev", optional=True)
@@ -218,7 +218,7 @@ class Gridder:
                 out = _lib.result_empty(x.shape, np.float32)
             elif out.shape != x.shape or out.dtype != np.float32 or not out.flags.c_contiguous or np.shares_memory(out, x):
                 raise ValueError("out must be a C-contiguous float32 array of the image shape that does not alias x")
-            check(lib().pfbhip_gridder_hessian_sp(self._h, ptr(x), ptr(beam), f64(eta or 0.0), f64(wsum or 0.0), ptr(out)))
+            check(lib().pfbhip_gridder_hessian_sp(self._h, ptr(x), ptr(beam), eta or 0.0, wsum or 0.0, ptr(out)))
             return out
         x = self._img(x, "x")
         beam = None if beam is None else self._img(beam, "beam")
@@ -226,12 +226,12 @@ class Gridder:
             out = _lib.result_empty(x.shape, np.float64)
         elif out.shape != x.shape or out.dtype != np.float64 or not out.flags.c_contiguous or np.shares_memory(out, x):
             raise ValueError("out must be a C-contiguous float64 array of the image shape that does not alias x")
-        check(lib().pfbhip_gridder_hessian(self._h, ptr(x), ptr(beam), f64(eta or 0.0), f64(wsum or 0.0), ptr(out)))
+        check(lib().pfbhip_gridder_hessian(self._h, ptr(x), ptr(beam), eta or 0.0, wsum or 0.0, ptr(out)))
         return out
 
     def hessian_dev(self, x_dev, out_dev, beam_dev=None, eta=0.0, wsum=0.0):
-        check(lib().pfbhip_gridder_hessian_dev(self._h, x_dev.ptr, None if beam_dev is None else beam_dev.ptr,
-                                               f64(eta or 0.0), f64(wsum or 0.0), out_dev.ptr))
+        check(lib().pfbhip_gridder_hessian_dev(self._h, x_dev.ptr, None if beam_dev is None else beam_dev.ptr, eta or 0.0,
+                                               wsum or 0.0, out_dev.ptr))
 
     def residual_dev(self, model_dev, acc_dev, out_dev, beam_dev=None):
         """``out = acc - R^H W R (beam * model)`` with every image a ``DeviceArray`` (``out`` may be ``acc``): the exact
@@ -251,18 +251,16 @@ class Gridder:
         x = np.zeros_like(rhs) if x0 is None else self._img(x0, "x0").copy()
         beam = None if beam is None else self._img(beam, "beam")
         info = CGInfo()
-        check(lib().pfbhip_gridder_cg(self._h, ptr(beam), f64(eta or 0.0), f64(wsum or 0.0), ptr(rhs), ptr(x),
-                                      cint(0 if x0 is None else 1), f64(tol), cint(maxit), cint(minit),
-                                      ct.byref(info)))
+        check(lib().pfbhip_gridder_cg(self._h, ptr(beam), eta or 0.0, wsum or 0.0, ptr(rhs), ptr(x), 0 if x0 is None else 1, tol,
+                                      maxit, minit, ct.byref(info)))
         self.last_cg = dict(iters=info.iters, status=info.status, eps=info.eps, phi=info.phi)
         return x
 
     def cg_dev(self, rhs_dev, x_dev, beam_dev=None, eta=0.0, wsum=0.0, has_x0=False, tol=1e-5, maxit=500, minit=100):
         """The same solve with rhs / x (and beam) resident in HBM (``DeviceArray``); returns the CG info dict."""
         info = CGInfo()
-        check(lib().pfbhip_gridder_cg_dev(self._h, None if beam_dev is None else beam_dev.ptr, f64(eta or 0.0), f64(wsum or 0.0),
-                                          rhs_dev.ptr, x_dev.ptr, cint(int(bool(has_x0))), f64(tol), cint(maxit), cint(minit),
-                                          ct.byref(info)))
+        check(lib().pfbhip_gridder_cg_dev(self._h, None if beam_dev is None else beam_dev.ptr, eta or 0.0, wsum or 0.0,
+                                          rhs_dev.ptr, x_dev.ptr, int(bool(has_x0)), tol, maxit, minit, ct.byref(info)))
         self.last_cg = dict(iters=info.iters, status=info.status, eps=info.eps, phi=info.phi)
         return self.last_cg
 
@@ -271,8 +269,7 @@ class Gridder:
         b = self._img(b0, "b0").copy()
         beam = None if beam is None else self._img(beam, "beam")
         info = PMInfo()
-        check(lib().pfbhip_gridder_power_method(self._h, ptr(beam), f64(eta or 0.0), f64(wsum or 0.0), ptr(b), f64(tol),
-                                                cint(maxit), ct.byref(info)))
+        check(lib().pfbhip_gridder_power_method(self._h, ptr(beam), eta or 0.0, wsum or 0.0, ptr(b), tol, maxit, ct.byref(info)))
         self.last_pm = dict(iters=info.iters, status=info.status, eps=info.eps)
         return float(info.beta), b
 
@@ -290,16 +287,16 @@ class Gridder:
     def grid_plane(self, vis, wgt, plane):
         vis, wgt = self._vis(vis), self._wgt(wgt)
         out = np.empty((self.info["nu"], self.info["nv"]), dtype=np.complex128)
-        check(lib().pfbhip_gridder_grid_plane(self._h, ptr(vis), ptr(wgt), i64(plane), ptr(out)))
+        check(lib().pfbhip_gridder_grid_plane(self._h, ptr(vis), ptr(wgt), plane, ptr(out)))
         return out
 
     def profile(self, enable=True):
-        check(lib().pfbhip_gridder_profile(self._h, cint(int(enable))))
+        check(lib().pfbhip_gridder_profile(self._h, int(enable)))
 
     def profile_get(self, reset=True):
         ms = (f64 * _lib.NSTAGES)()
         calls = (i64 * _lib.NSTAGES)()
-        check(lib().pfbhip_gridder_profile_get(self._h, ms, calls, cint(int(reset))))
+        check(lib().pfbhip_gridder_profile_get(self._h, ms, calls, int(reset)))
         return {n: (ms[i], calls[i]) for i, n in enumerate(_lib.STAGE_NAMES)}
 
     def oracle_params(self):

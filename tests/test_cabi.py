@@ -1,5 +1,6 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads without a GPU, exports every symbol
-include/pfbhip.h declares, its structs match the ctypes mirror, and it fails loudly without a GPU."""
+include/pfbhip.h declares, the signatures the binding takes from that header are the compiler's, every call site passes what
+they say, its structs match the ctypes mirror, and it fails loudly without a GPU."""
 
 import ctypes as ct
 import os
@@ -31,33 +32,201 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SYMBOLS) == declared
 
 
-def test_struct_layout_matches_header(tmp_path):
+def _gcc(tmp_path, source, *flags):
+    src = tmp_path / "probe.c"
+    src.write_text(source)
+    return subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), *flags, str(src)], capture_output=True, text=True)
+
+
+def test_parsed_prototypes_match_the_compiler(tmp_path):
+    """The loader's parser against an independent reader of the header: for every prototype it found, a function pointer
+    spelled from the PARSED return and parameter types must take the address of the function as pfbhip.h declares it."""
     from pfb_imaging_amd import _lib
 
-    src = tmp_path / "layout.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "pfbhip.h"\n'
-        "int main(void){\n"
-        'printf("%zu %zu %zu %zu %zu\\n", sizeof(pfbhip_gridder_params), offsetof(pfbhip_gridder_params, epsilon),'
-        " offsetof(pfbhip_gridder_params, flip_u), offsetof(pfbhip_gridder_params, force_wmode),"
-        " offsetof(pfbhip_gridder_params, force_sigma));\n"
-        'printf("%zu %zu %zu %zu %zu\\n", sizeof(pfbhip_gridder_info), offsetof(pfbhip_gridder_info, W),'
-        " offsetof(pfbhip_gridder_info, beta), offsetof(pfbhip_gridder_info, wmode),"
-        " offsetof(pfbhip_gridder_info, device_bytes));\n"
-        'printf("%zu %zu\\n", sizeof(pfbhip_cg_info), offsetof(pfbhip_cg_info, eps));\n'
-        'printf("%zu %zu %zu %d\\n", sizeof(pfbhip_pd_info), offsetof(pfbhip_pd_info, stage_ms),'
-        " offsetof(pfbhip_pd_info, stage_calls), PFBHIP_PD_NSTAGES);\n"
-        "return 0;}\n"
-    )
+    protos = _lib.parse_prototypes(open(HEADER).read())
+    assert sorted(protos) == _declared_symbols() and len(protos) >= 45   # one prototype per name, none missed
+
+    def pointer(name, ret, params):
+        return f"{ret} (*const p_{name})({', '.join(params) or 'void'}) = &{name};\n"
+
+    strict = ("-fsyntax-only", "-Wall", "-Werror", "-Werror=incompatible-pointer-types")
+    head = '#include "pfbhip.h"\n'
+    r = _gcc(tmp_path, head + "".join(pointer(n, *p) for n, p in protos.items()), *strict)
+    assert r.returncode == 0, r.stderr
+    # the same flags do refuse a wrong width, a wrong count and a dropped qualifier (so a pass above means agreement)
+    for wrong in (("int64_t", ["int", "int"]), ("int64_t", ["int64_t"]), ("int64_t", ["int64_t", "int", "int"])):
+        assert _gcc(tmp_path, head + pointer("pfbhip_good_size", *wrong), *strict).returncode != 0, wrong
+    assert _gcc(tmp_path, head + pointer("pfbhip_hash64", "uint64_t", ["void *", "size_t"]), *strict).returncode != 0
+
+
+def test_ctypes_signatures_by_example():
+    """The C-to-ctypes mapping, pinned by hand on one entry point of each kind, as the loaded library carries it."""
+    from pfb_imaging_amd import _lib
+
+    L = _lib.lib()
+    vp, i64, f64, cint, size_t = ct.c_void_p, ct.c_int64, ct.c_double, ct.c_int, ct.c_size_t
+    expect = {
+        "pfbhip_last_error": (ct.c_char_p, []),
+        "pfbhip_thread_pool_size": (cint, []),
+        "pfbhip_good_size": (i64, [i64, cint]),
+        "pfbhip_hash64": (ct.c_uint64, [vp, size_t]),
+        "pfbhip_gridder_create": (cint, [vp] * 5),
+        "pfbhip_gridder_hessian_sp": (cint, [vp, vp, vp, f64, f64, vp]),
+        "pfbhip_psfconv_power_method": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, f64, cint, vp, vp]),
+        "pfbhip_pd_iterate_dev": (cint, [vp, vp]),
+        "pfbhip_psi_create": (cint, [i64, i64, ct.c_int32, vp, ct.c_int32, vp]),
+        "pfbhip_chunk_average_dev": (cint, [vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp]),
+    }
+    for name, (restype, argtypes) in expect.items():
+        f = getattr(L, name)
+        assert (f.restype, list(f.argtypes)) == (restype, argtypes), name
+    for name in _lib.SYMBOLS:   # every entry point got a signature of the right length, not only the examples
+        assert getattr(L, name).argtypes is not None, name
+
+
+def test_wrong_arguments_fail_before_the_call():
+    """A float for an integer parameter and a wrong argument count are refused by ctypes, on entries that validate before they
+    touch a device."""
+    from pfb_imaging_amd import _lib
+
+    L = _lib.lib()
+    # (fetched by name: the audit of the call sites below reads every literal call, and these are wrong on purpose)
+    good_size, get_info = getattr(L, "pfbhip_good_size"), getattr(L, "pfbhip_gridder_get_info")
+    assert good_size(10, 0) == 10 and good_size(np.int64(127), True) == 128
+    for bad in (10.5, ct.c_double(10.0), ct.c_int(10), "10", None):
+        with pytest.raises(ct.ArgumentError):
+            good_size(bad, 0)
+    with pytest.raises(ct.ArgumentError):
+        get_info(None, 1.5)
+    # ctypes reports a wrong type as ArgumentError and a missing argument as TypeError.  It passes SURPLUS arguments of a
+    # cdecl function on, as C does for a variadic one: those only the audit of the call sites below finds.
+    with pytest.raises(TypeError, match="takes at least 2 arguments"):
+        get_info(None)
+    with pytest.raises(TypeError, match="takes at least 2 arguments"):
+        good_size(10)
+
+
+def test_unknown_c_type_fails_the_load():
+    from pfb_imaging_amd import _lib
+
+    header = "int pfbhip_fine(int64_t n, const double *x);\nint pfbhip_odd(float level, int n);\n"
+    with pytest.raises(ImportError, match=r"unknown parameter type 'float' in `int pfbhip_odd\(float, int\)`"):
+        _lib.signatures(header)
+    with pytest.raises(ImportError, match=r"unknown return type 'void' in `void pfbhip_odd\(int\)`"):
+        _lib.signatures("void pfbhip_odd(int n);\n")
+    with pytest.raises(ImportError, match="pfbhip_odd"):     # an unnamed parameter is not guessed at either
+        _lib.signatures("int pfbhip_odd(int);\n")
+    assert _lib.signatures(header.splitlines()[0]) == {"pfbhip_fine": (ct.c_int, [ct.c_int64, ct.c_void_p])}
+
+
+MIRRORS = {"gridder_params": "GridderParams", "gridder_info": "GridderInfo", "cg_info": "CGInfo", "pm_info": "PMInfo",
+           "pd_info": "PDInfo", "pd_traffic": "PDTraffic", "clean_info": "CleanInfo", "fb_info": "FBInfo", "dft_conv": "DFTConv",
+           "cleanbeam_info": "CleanbeamInfo", "stokes_spec": "StokesSpec"}
+CONSTANTS = {"PFBHIP_NSTAGES": "NSTAGES", "PFBHIP_PD_NSTAGES": "PD_NSTAGES", "PFBHIP_FB_NSTAGES": "FB_NSTAGES",
+             "PFBHIP_UNIQUE_ID_BYTES": "UNIQUE_ID_BYTES"}
+
+
+def _declared_structs():
+    """{struct name without the prefix: [field names in order]} of every struct body in the header."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*pfbhip_(\w+)\s*;", text):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            declarators = decl.split(None, 1)[1]            # "int64_t nu, nv" / "double f, p0[3]": a one-word type, then names
+            fields += [re.sub(r"\[.*\]", "", d).strip() for d in declarators.split(",")]
+        structs[name] = fields
+    return structs
+
+
+def test_struct_layout_matches_header(tmp_path):
+    """Every field of every struct of the header: size and offset as gcc lays them out against the ctypes mirror, the mirror
+    having the same field names in the same order; and the array-length constants the mirrors are built with."""
+    from pfb_imaging_amd import _lib
+
+    structs = _declared_structs()
+    assert sorted(structs) == sorted(MIRRORS) and len(structs) == 11
+    lines = ['#include <stdio.h>\n#include <stddef.h>\n#include "pfbhip.h"\nint main(void){\n']
+    for c in CONSTANTS:
+        lines.append(f'printf("%d\\n", (int){c});\n')
+    for s, fields in structs.items():
+        lines.append(f'printf("%zu\\n", sizeof(pfbhip_{s}));\n')
+        for f in fields:
+            lines.append(f'printf("%zu %zu\\n", offsetof(pfbhip_{s}, {f}), sizeof(((pfbhip_{s} *)0)->{f}));\n')
     exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split()
-    P, I, C, D = _lib.GridderParams, _lib.GridderInfo, _lib.CGInfo, _lib.PDInfo
-    expect = [ct.sizeof(P), P.epsilon.offset, P.flip_u.offset, P.force_wmode.offset, P.force_sigma.offset,
-              ct.sizeof(I), I.W.offset, I.beta.offset, I.wmode.offset, I.device_bytes.offset, ct.sizeof(C), C.eps.offset,
-              ct.sizeof(D), D.stage_ms.offset, D.stage_calls.offset, _lib.PD_NSTAGES]
-    assert len(_lib.PD_STAGE_NAMES) == _lib.PD_NSTAGES
-    assert [int(v) for v in out] == expect
+    r = _gcc(tmp_path, "".join(lines) + "return 0;}\n", "-o", str(exe))
+    assert r.returncode == 0, r.stderr
+    got = [int(v) for v in subprocess.check_output([str(exe)]).decode().split()]
+    expect = [getattr(_lib, py) for py in CONSTANTS.values()]
+    for s, fields in structs.items():
+        mirror = getattr(_lib, MIRRORS[s])
+        assert [n for n, _ in mirror._fields_] == fields, s
+        expect.append(ct.sizeof(mirror))
+        for f in fields:
+            expect += [getattr(mirror, f).offset, getattr(mirror, f).size]
+    assert got == expect
+    assert len(_lib.STAGE_NAMES) == _lib.NSTAGES and len(_lib.PD_STAGE_NAMES) == _lib.PD_NSTAGES
+    assert len(_lib.FB_STAGE_NAMES) == _lib.FB_NSTAGES
+
+
+# calls that splat an argument tuple cannot be counted statically (argtypes check them when the GPU suite runs them); a new
+# one has to be added here on purpose
+SPLAT_CALLS = sorted([
+    ("pfb-imaging_amd/comps.py", "pfbhip_comps_regrid"), ("pfb-imaging_amd/comps.py", "pfbhip_comps_regrid_dev"),
+    ("pfb-imaging_amd/opt.py", "pfbhip_pd_create"), ("pfb-imaging_amd/opt.py", "pfbhip_primal_dual"),
+    ("pfb-imaging_amd/opt.py", "pfbhip_fb_create"), ("pfb-imaging_amd/opt.py", "pfbhip_psfconv_power_method"),
+    ("pfb-imaging_amd/gaussconv.py", "pfbhip_gaussconv_shape"),
+    ("pfb-imaging_amd/gaussconv.py", "pfbhip_gaussconv_apply"), ("pfb-imaging_amd/gaussconv.py", "pfbhip_gaussconv_apply_dev"),
+    ("pfb-imaging_amd/gaussconv.py", "pfbhip_gaussconv_restore"), ("pfb-imaging_amd/gaussconv.py", "pfbhip_gaussconv_restore_dev"),
+    ("pfb-imaging_amd/utils/weighting.py", "pfbhip_weight_data_dev"),
+    ("tests/test_gpu_beam.py", "pfbhip_beam_regrid"), ("tests/test_gpu_beam.py", "pfbhip_beam_regrid"),
+    ("tests/test_gpu_restore.py", "pfbhip_gaussconv_apply_dev"), ("tests/test_gpu_restore.py", "pfbhip_gaussconv_restore_dev"),
+])
+# a ctypes constructor written in place as an argument, by its last name, and the C type it states
+CONSTRUCTORS = {"cint": "int", "c_int": "int", "i32": "int32_t", "c_int32": "int32_t", "i64": "int64_t", "c_int64": "int64_t",
+                "c_longlong": "int64_t", "c_long": "int64_t", "f64": "double", "c_double": "double", "c_size_t": "size_t",
+                "c_uint64": "uint64_t", "c_ulong": "uint64_t", "c_float": "float", "c_uint32": "uint32_t", "c_uint": "uint32_t",
+                "c_int16": "int16_t", "c_short": "int16_t", "c_int8": "int8_t", "c_uint8": "uint8_t", "c_bool": "bool"}
+SAME = {"int32_t": "int", "uint64_t": "size_t"}
+
+
+def test_call_sites_match_the_header():
+    """Every literal ``.pfbhip_name(...)`` call in the product, the tests, the tools and the benchmark passes the declared
+    number of positional arguments and no keywords, and a ctypes constructor written as an argument names the declared type."""
+    import ast
+    import glob
+
+    from pfb_imaging_amd import _lib
+
+    protos = _lib.parse_prototypes(open(HEADER).read())
+    files = [os.path.join(ROOT, "bench.py")]
+    for d in ("pfb-imaging_amd", "tests", "tools"):
+        files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
+    splats, wrong, ncalls = [], [], 0
+    for path in sorted(files):
+        rel = os.path.relpath(path, ROOT)
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in protos):
+                continue
+            name, where = node.func.attr, f"{rel}:{node.lineno}"
+            params = protos[name][1]
+            ncalls += 1
+            if node.keywords:
+                wrong.append(f"{where} {name}: keyword arguments")
+            if any(isinstance(a, ast.Starred) for a in node.args):
+                splats.append((rel, name))
+                continue
+            if len(node.args) != len(params):
+                wrong.append(f"{where} {name}: {len(node.args)} arguments, the header declares {len(params)}")
+                continue
+            for k, (a, declared) in enumerate(zip(node.args, params)):
+                f = a.func if isinstance(a, ast.Call) else None
+                stated = CONSTRUCTORS.get(getattr(f, "id", None) or getattr(f, "attr", None))
+                if stated is not None and SAME.get(stated, stated) != SAME.get(declared, declared):
+                    wrong.append(f"{where} {name}: argument {k} is written as {stated}, the header declares {declared}")
+    assert not wrong, "\n".join(wrong)
+    assert sorted(splats) == SPLAT_CALLS
+    assert ncalls >= 150   # (the walk did find the call sites: about 200 in the product alone)
 
 
 def test_no_gpu_paths_fail_loudly_or_work_on_host():
@@ -202,7 +371,7 @@ def test_pinned_results_are_capped(monkeypatch):
 
     class FakeLib:
         def pfbhip_host_alloc(self, pp, nbytes):
-            b = ct.create_string_buffer(nbytes.value)
+            b = ct.create_string_buffer(nbytes)
             bufs.append(b)
             ct.cast(pp, ct.POINTER(ct.c_void_p))[0] = ct.addressof(b)
             return 0
