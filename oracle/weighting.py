@@ -45,7 +45,8 @@ def counts_to_weights(counts, uvw, freq, weight, mask, nx, ny, cell_x, cell_y, r
         num = np.zeros(ncorr)
         den = np.zeros(ncorr)
         lib().pfbo_briggs_sums(i64(ncorr), i64(nx * ny), ptr(counts), ptr(num), ptr(den))
-        ssq = numsqrt * numsqrt * den / num
+        with np.errstate(invalid="ignore", divide="ignore"):  # a dead plane is 0 / 0 = NaN (weighting.py:172)
+            ssq = numsqrt * numsqrt * den / num
         counts *= ssq[:, None, None]
         counts += 1
     cell = uvcell_index(uvw, freq, mask, nx, ny, cell_x, cell_y, usign, vsign)

@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
+#include <limits>
 #include <vector>
 
 #include "common.hpp"
@@ -53,13 +54,57 @@ __global__ void k_uvcell(CellArgs a, int64_t *cell)
     if (i < a.nvis) cell[i] = uv_cell(a, i);
 }
 
-__global__ void k_counts(CellArgs a, const double *wgt, int ncorr, double *counts)
+// The counts scatter without atomics, so that the order of the additions depends on the input alone and a result is
+// bit-identical from call to call: samples are sorted by cell (stable radix sort: a cell's samples stay in sample order), the
+// sorted list is cut into chunks of SEG_CHUNK positions, and a cell's samples are summed serially inside each chunk.
+//   k_cell_keys   key = cell, or `per` (sorts last) for a sample that is masked or off the grid
+//   k_seg_sum     one thread per run of equal keys inside a chunk: a run that starts a cell adds to counts (one writer per
+//                 cell), a run that continues the previous chunk's cell goes to head[chunk]
+//   k_seg_heads   the first such chunk of a cell adds the heads of that cell's chunks to counts, in chunk order
+constexpr int64_t SEG_CHUNK = 1024;
+
+__global__ void k_cell_keys(CellArgs a, uint32_t *key, uint32_t *idx)
 {
     int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
     if (i >= a.nvis) return;
     int64_t c = uv_cell(a, i);
-    if (c < 0) return;
-    for (int k = 0; k < ncorr; ++k) unsafeAtomicAdd(&counts[size_t(k) * a.nx * a.ny + c], wgt[size_t(k) * a.nvis + i]);
+    key[i] = c < 0 ? uint32_t(a.nx * a.ny) : uint32_t(c);
+    idx[i] = uint32_t(i);
+}
+
+__global__ void k_seg_sum(const uint32_t *skey, const uint32_t *sidx, int64_t nvis, int64_t per, const double *wgt, int ncorr,
+                          double *counts, double *head)
+{
+    int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (i >= nvis) return;
+    const uint32_t key = skey[i];
+    if (int64_t(key) >= per) return;
+    const int64_t chunk = i / SEG_CHUNK, begin = chunk * SEG_CHUNK;
+    const int64_t end = begin + SEG_CHUNK < nvis ? begin + SEG_CHUNK : nvis;
+    const bool starts = i == 0 || skey[i - 1] != key;
+    if (!starts && i != begin) return;
+    for (int k = 0; k < ncorr; ++k) {
+        double acc = 0.0;
+        for (int64_t j = i; j < end && skey[j] == key; ++j) acc += wgt[size_t(k) * nvis + sidx[j]];
+        if (starts)
+            counts[size_t(k) * per + key] += acc;
+        else
+            head[size_t(chunk) * ncorr + k] = acc;
+    }
+}
+
+__global__ void k_seg_heads(const uint32_t *skey, int64_t nvis, int64_t per, int ncorr, const double *head, double *counts)
+{
+    const int64_t c = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    const int64_t nchunks = (nvis + SEG_CHUNK - 1) / SEG_CHUNK;
+    if (c < 1 || c >= nchunks) return;
+    const uint32_t key = skey[c * SEG_CHUNK];
+    if (int64_t(key) >= per || skey[c * SEG_CHUNK - 1] != key) return;  // no cell runs on into this chunk
+    // the cell's first continued chunk owns it: the cell starts inside chunk c - 1
+    const int64_t pb = (c - 1) * SEG_CHUNK;
+    if (skey[pb] == key && pb > 0 && skey[pb - 1] == key) return;
+    for (int64_t cc = c; cc < nchunks && skey[cc * SEG_CHUNK] == key; ++cc)
+        for (int k = 0; k < ncorr; ++k) counts[size_t(k) * per + key] += head[size_t(cc) * ncorr + k];
 }
 
 __global__ void k_counts_divide(CellArgs a, const double *counts, int ncorr, double *wgt)
@@ -110,6 +155,29 @@ struct CellSetup {
     dim3 grid() const { return dim3(uint32_t(std::max<int64_t>(ceil_div(a.nvis, 256), 1))); }
 };
 
+// counts_dev (ncorr, nx, ny) += the weights wgt_dev (ncorr, nvis) of every sample in its cell (null stream); see k_cell_keys
+static void dev_counts(const CellSetup &s, const double *wgt_dev, int64_t ncorr, double *counts_dev)
+{
+    const int64_t n = s.a.nvis, per = s.a.nx * s.a.ny;
+    if (!n) return;
+    PFB_REQUIRE(n < (int64_t(1) << 31) && per < (int64_t(1) << 31), "too many samples or cells for the counts scatter");
+    DevBuf<uint32_t> key{size_t(n)}, idx{size_t(n)}, skey{size_t(n)}, sidx{size_t(n)};
+    hipLaunchKernelGGL(k_cell_keys, s.grid(), dim3(256), 0, 0, s.a, key.p, idx.p);
+    PFB_HIP(hipGetLastError());
+    int bits = 1;  // the keys are 0 ... per
+    while ((int64_t(1) << bits) <= per) ++bits;
+    size_t tb = 0;
+    PFB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key.p, skey.p, idx.p, sidx.p, int(n), 0, bits));
+    DevBuf<char> tmp(std::max<size_t>(tb, 1));
+    PFB_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, key.p, skey.p, idx.p, sidx.p, int(n), 0, bits));
+    const int64_t nchunks = ceil_div(n, SEG_CHUNK);
+    DevBuf<double> head(size_t(nchunks) * size_t(ncorr));
+    hipLaunchKernelGGL(k_seg_sum, s.grid(), dim3(256), 0, 0, skey.p, sidx.p, n, per, wgt_dev, int(ncorr), counts_dev, head.p);
+    hipLaunchKernelGGL(k_seg_heads, dim3(uint32_t(ceil_div(nchunks, 256))), dim3(256), 0, 0, skey.p, n, per, int(ncorr), head.p,
+                       counts_dev);
+    PFB_HIP(hipGetLastError());
+}
+
 // box sum along one axis with zero padding: out[r][c] = sum_{|d| <= s} in[r][c + d]   (axis 1)
 //                                              or  sum_{|d| <= s} in[r + d][c]   (axis 0)
 __global__ void k_box_sum_axis(const double *in, int64_t nplanes, int nx, int ny, int s, int axis, double *out)
@@ -145,8 +213,9 @@ __global__ void k_floor_positive(double *a, int64_t n, double lowval)
     if (i < n && a[i] > 0.0 && a[i] < lowval) a[i] = lowval;
 }
 
-// per-plane sum and sum of squares (Briggs normalisation): out[2 k] += sum, out[2 k + 1] += sum of squares
-__global__ void k_sum_sumsq(const double *a, int64_t per, double *out)
+// per-plane sum and sum of squares (Briggs normalisation), two stages without atomics so that the order of the additions
+// depends on the sizes alone: part[(k * gridDim.x + b) * 2] = block b's sum of plane k, [... + 1] its sum of squares
+__global__ void k_sum_sumsq(const double *a, int64_t per, double *part)
 {
     __shared__ double s1[256], s2[256];
     const int k = blockIdx.y;
@@ -167,8 +236,34 @@ __global__ void k_sum_sumsq(const double *a, int64_t per, double *out)
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        unsafeAtomicAdd(&out[2 * k], s1[0]);
-        unsafeAtomicAdd(&out[2 * k + 1], s2[0]);
+        part[(size_t(k) * gridDim.x + blockIdx.x) * 2] = s1[0];
+        part[(size_t(k) * gridDim.x + blockIdx.x) * 2 + 1] = s2[0];
+    }
+}
+
+// one block per plane: out[2 k] = sum of plane k's nb block sums, out[2 k + 1] = of its sums of squares, along a fixed tree
+__global__ void k_sum_partials(const double *part, int nb, double *out)
+{
+    __shared__ double s1[256], s2[256];
+    const int k = blockIdx.x;
+    double t1 = 0.0, t2 = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+        t1 += part[(size_t(k) * nb + b) * 2];
+        t2 += part[(size_t(k) * nb + b) * 2 + 1];
+    }
+    s1[threadIdx.x] = t1;
+    s2[threadIdx.x] = t2;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (int(threadIdx.x) < s) {
+            s1[threadIdx.x] += s1[threadIdx.x + s];
+            s2[threadIdx.x] += s2[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[2 * k] = s1[0];
+        out[2 * k + 1] = s2[0];
     }
 }
 
@@ -222,8 +317,7 @@ static bool imaging_weights_resident(const CellSetup &s, double *wgt_dev, int64_
         if (counts_out_host) PFB_HIP(hipMemcpy(counts_out_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
         return false;
     }
-    hipLaunchKernelGGL(k_counts, s.grid(), dim3(256), 0, 0, s.a, wgt_dev, int(ncorr), counts.p);
-    PFB_HIP(hipGetLastError());
+    dev_counts(s, wgt_dev, ncorr, counts.p);
     if (filter_level > 0.0) (void)dev_filter_extreme(counts.p, int64_t(ncnt), filter_level);
     if (npix_super > 0) {
         dim3 grid(uint32_t(ceil_div(int64_t(ncnt), 256)));
@@ -231,11 +325,15 @@ static bool imaging_weights_resident(const CellSetup &s, double *wgt_dev, int64_
         hipLaunchKernelGGL(k_box_sum_axis, grid, dim3(256), 0, 0, tmp.p, ncorr, int(nx), int(ny), int(npix_super), 0, counts.p);
         PFB_HIP(hipGetLastError());
     }
-    // Briggs: counts <- counts * (5 * 10^-R)^2 * sum(c) / sum(c^2) + 1 when R > -2; all-zero counts leave the weights alone
+    // Briggs: counts <- counts * (5 * 10^-R)^2 * sum(c) / sum(c^2) + 1 when R > -2; all-zero counts leave the weights alone.
+    // A dead plane (all-zero counts: a Stokes product without weight) beside a live one gets the reference's 0 / 0
+    // (weighting.py:172-174): its counts come out NaN when R > -2 and stay zero otherwise; no NaN is > 0, so k_counts_divide
+    // leaves that plane's weights untouched either way.
     DevBuf<double> sums(size_t(2 * ncorr));
-    PFB_HIP(hipMemset(sums.p, 0, sums.bytes()));
-    hipLaunchKernelGGL(k_sum_sumsq, dim3(uint32_t(std::min<int64_t>(ceil_div(per, 256), 1024)), uint32_t(ncorr)), dim3(256), 0, 0,
-                       counts.p, per, sums.p);
+    const int nb = int(std::min<int64_t>(ceil_div(per, 256), 1024));
+    DevBuf<double> part(size_t(2 * ncorr) * size_t(nb));
+    hipLaunchKernelGGL(k_sum_sumsq, dim3(uint32_t(nb), uint32_t(ncorr)), dim3(256), 0, 0, counts.p, per, part.p);
+    hipLaunchKernelGGL(k_sum_partials, dim3(uint32_t(ncorr)), dim3(256), 0, 0, part.p, nb, sums.p);
     PFB_HIP(hipGetLastError());
     std::vector<double> hs(size_t(2 * ncorr));
     PFB_HIP(hipMemcpy(hs.data(), sums.p, sums.bytes(), hipMemcpyDeviceToHost));
@@ -246,7 +344,8 @@ static bool imaging_weights_resident(const CellSetup &s, double *wgt_dev, int64_
             const double numsqrt = 5.0 * std::pow(10.0, -robust);
             std::vector<double> ssq(static_cast<size_t>(ncorr), 0.0);
             for (int64_t k = 0; k < ncorr; ++k)
-                ssq[size_t(k)] = hs[size_t(2 * k + 1)] > 0.0 ? numsqrt * numsqrt * hs[size_t(2 * k)] / hs[size_t(2 * k + 1)] : 0.0;
+                ssq[size_t(k)] = hs[size_t(2 * k + 1)] > 0.0 ? numsqrt * numsqrt * hs[size_t(2 * k)] / hs[size_t(2 * k + 1)]
+                                                             : std::numeric_limits<double>::quiet_NaN();
             DevBuf<double> d_ssq{size_t(ncorr)};
             PFB_HIP(hipMemcpy(d_ssq.p, ssq.data(), d_ssq.bytes(), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_scale_plus_one, dim3(uint32_t(ceil_div(per, 256)), uint32_t(ncorr)), dim3(256), 0, 0, counts.p,
@@ -333,8 +432,7 @@ int pfbhip_compute_counts(const double *uvw_host, const double *freq_host, const
         if (s.a.nvis) {
             DevBuf<double> wgt(size_t(ncorr) * size_t(s.a.nvis));
             PFB_HIP(hipMemcpy(wgt.p, wgt_host, wgt.bytes(), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_counts, s.grid(), dim3(256), 0, 0, s.a, wgt.p, int(ncorr), counts.p);
-            PFB_HIP(hipGetLastError());
+            dev_counts(s, wgt.p, ncorr, counts.p);
         }
         PFB_HIP(hipMemcpy(counts_host, counts.p, counts.bytes(), hipMemcpyDeviceToHost));
     });

@@ -2,7 +2,8 @@
 
 Mirrors /root/reference/src/pfb_imaging/utils/weighting.py: ``_compute_counts`` (:81-140) and
 ``counts_to_weights`` (:143-208).  The integer uv-cell index is bit-exact against the CPU
-oracle; the scatter-add uses hardware f64 atomics, so counts agree to summation order.
+oracle; the counts are a sorted, segmented sum without atomics: they agree with the reference to summation order and are
+bit-identical from call to call.
 
 ``weight_data`` (:274-468) forms the Stokes visibilities and weights the rest consumes (csrc/stokes.hip).
 """
@@ -49,7 +50,9 @@ def counts_to_weights(counts, uvw, freq, weight, mask, nx, ny, cell_size_x, cell
         numsqrt = 5 * 10 ** (-robust)
         avgwnum = (counts.reshape(ncorr, -1) ** 2).sum(axis=1)
         avgwden = counts.reshape(ncorr, -1).sum(axis=1)
-        ssq = numsqrt * numsqrt * avgwden / avgwnum
+        # a dead plane (all-zero counts) beside a live one is the reference's 0 / 0: NaN counts, weights left alone
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ssq = numsqrt * numsqrt * avgwden / avgwnum
         counts *= ssq[:, None, None]
         counts += 1
     uvw, freq, mask = as_c(uvw, np.float64), as_c(freq, np.float64), as_c(mask, np.uint8)

@@ -542,3 +542,31 @@ def test_a_stokes_without_weight_is_reported_and_leaves_the_other_alone(snap):
     assert np.isnan([got["psf_maj"][1], got["psf_min"][1], got["psf_pa"][1]]).all()
     assert rel(got["cube"][0], alone["cube"][0]) < 1e-11 and rel(got["psf"][0], alone["psf"][0]) < 1e-11
     assert abs(got["psf_maj"][0] - alone["psf_maj"][0]) < 1e-6 * alone["psf_maj"][0]
+
+
+def test_a_stokes_without_weight_gets_a_zero_weight_grid(snap):
+    """With imaging weights (robustness 0) the dead plane's counts are the reference's 0 / 0 (weighting.py:172-174), so its
+    ``wgtgrid`` plane is zero (stokes2im.py:740-742), not ones; the live plane's is that of the one-plane chunk to 1e-6: the
+    float32 cast of both sides, and the joint-median filter sees the same positives."""
+    wgt = np.array(snap["wgt"])
+    wgt[1] = 0.0
+    from pfb_imaging_amd.utils.stokes2im import snapshot_image_chunk
+
+    kw = dict(robustness=0.0, weight_grid_out=True, psf_out=True, out_dtype=np.float64)
+    with chunk(snap["vis"], wgt, snap["mask"], snap["uvw"], snap["freq"]) as ch:
+        got = snapshot_image_chunk(ch, NPIX, NPIX, snap["cell"], **kw)
+    with chunk(snap["vis"][:1], wgt[:1], snap["mask"], snap["uvw"], snap["freq"]) as ch:
+        alone = snapshot_image_chunk(ch, NPIX, NPIX, snap["cell"], **kw)
+    npad = ref.pad_size(NPIX, 1.7)
+    err = np.abs(got["wgtgrid"][0] - alone["wgtgrid"][0])
+    print(f"wgtgrid: dead plane max {np.abs(got['wgtgrid'][1]).max()}, live plane vs the one-plane chunk "
+          f"{(err / np.maximum(alone['wgtgrid'][0], 1e-300)).max():.3e}, {int((got['wgtgrid'][0] > 0).sum())} cells")
+    assert got["wgtgrid"].shape == (2, npad, npad) and got["wgtgrid"].dtype == np.float32
+    assert not got["wgtgrid"][1].any()
+    assert got["wgtgrid"][0].any() and np.array_equal(got["wgtgrid"][0] > 0, alone["wgtgrid"][0] > 0)
+    assert (err <= 1e-6 * alone["wgtgrid"][0]).all()
+    assert list(got["nonzero"]) == [True, False] and got["weight"][1] == 0.0 and got["rms"][1] == 0.0
+    assert not got["cube"][1].any() and not got["psf"][1].any()
+    assert np.isnan([got["psf_maj"][1], got["psf_min"][1], got["psf_pa"][1]]).all()
+    assert rel(got["cube"][0], alone["cube"][0]) < 1e-11 and rel(got["psf"][0], alone["psf"][0]) < 1e-11
+    assert abs(got["psf_maj"][0] - alone["psf_maj"][0]) < 1e-6 * alone["psf_maj"][0]
